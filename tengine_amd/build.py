@@ -3,8 +3,8 @@
   tengine_amd/lib/libtengine_amd.so      HIP kernels + planner/executor + tm2 loader, C ABI of include/tengine_amd.h
   tengine_amd/lib/rccl_gather.bin        the C multi-GPU harness of INTEGRATION.md section F (tengine_amd/harness/rccl_gather.cpp)
   tengine_amd/lib/libtengine_hip_device.so   the Tengine device plugin (register_hip_device), only where the
-                                         reference headers are present (it compiles against source/*.h; the
-                                         prebuilt .so travels to the GPU box)
+                                         reference headers are present (it compiles against source/*.h); build()
+                                         also puts a copy under oracle/_ref/, which travels with the prebuilt reference
 
 -ffp-contract=off and no fast-math are REQUIRED: the requantising epilogues must round exactly like the
 reference's scalar C.
@@ -71,7 +71,8 @@ def build_core(verbose=False, force=False):
 
 
 def build_plugin(ref="/root/reference", verbose=False, force=False):
-    """Tengine device plugin; needs the reference headers at build time only."""
+    """Tengine device plugin; needs the reference headers at build time only.  It finds libtengine_amd.so beside itself or, as a
+    copy under oracle/_ref/, in tengine_amd/lib/ of the same tree."""
     src = os.path.join(HERE, "device", "hip_device.cc")
     if not os.path.isdir(os.path.join(ref, "source")) or not os.path.exists(src):
         return None
@@ -87,7 +88,7 @@ def build_plugin(ref="/root/reference", verbose=False, force=False):
     cmd = ["g++", "-O2", "-std=c++14", "-fPIC", "-shared", "-fvisibility=hidden", "-I" + os.path.join(ref, "source"),
            "-I" + os.path.join(ref, "source", "operator", "prototype"), "-I" + gen,
            "-I" + os.path.join(ROOT, "include"), src, "-o", lib,
-           "-L" + LIBDIR, "-ltengine_amd", "-Wl,-rpath,$ORIGIN"]
+           "-L" + LIBDIR, "-ltengine_amd", "-Wl,-rpath,$ORIGIN:$ORIGIN/../../tengine_amd/lib"]
     subprocess.check_call(cmd)
     return lib
 

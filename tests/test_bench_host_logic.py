@@ -150,3 +150,21 @@ def test_side_configs_have_a_reference_golden():
         assert sha is not None and len(sha) == want_outputs[key] and all(len(h) == 64 for h in sha), key
         assert gold[key]["seed"] == 1000 and gold[key]["outputs"][0]["shape"][0] == batch
     assert b.golden_sha("no_such_model", "int8", 1) is None
+
+
+def test_dump_outputs_writes_float32_within_the_size_limit(tmp_path):
+    """--dump-outputs: every output as output<i>.npy in float32 (float64 kept); a set over the limit is cut to a fixed seeded sample"""
+    import numpy as np
+    b = _bench()
+    outs = [np.arange(-128, 128, dtype=np.int8).reshape(2, 128), np.linspace(0, 1, 7)]
+    b.dump_outputs(outs, str(tmp_path / "a"))
+    a0, a1 = np.load(str(tmp_path / "a" / "output0.npy")), np.load(str(tmp_path / "a" / "output1.npy"))
+    assert a0.dtype == np.float32 and a0.shape == (2, 128) and np.array_equal(a0, outs[0])
+    assert a1.dtype == np.float64 and np.array_equal(a1, outs[1])
+    big = [np.arange(3000, dtype=np.int32), np.arange(1000, dtype=np.int16)]
+    for d in ("b", "c"):
+        b.dump_outputs(big, str(tmp_path / d), limit_bytes=4000)
+    s0, s1 = np.load(str(tmp_path / "b" / "output0.npy")), np.load(str(tmp_path / "b" / "output1.npy"))
+    assert s0.nbytes + s1.nbytes <= 4000 and (s0.size, s1.size) == (750, 250)
+    assert np.all(np.diff(s0) > 0) and np.isin(s1, big[1]).all()
+    assert np.array_equal(s0, np.load(str(tmp_path / "c" / "output0.npy")))

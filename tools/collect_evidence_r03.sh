@@ -10,12 +10,12 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 # ---- 1. bench lines
-python $R/bench.py --steps 20 --warmup 5 > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err
-python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 > $O/bench_b1.json 2>> $O/bench_b1.err
-python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
-python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
-python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
-python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
+python $R/bench.py --steps 20 --warmup 5 --full > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err
+python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 --full > $O/bench_b1.json 2>> $O/bench_b1.err
+python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 --full > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
+python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
+python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
+python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
 for f in $O/bench_*.json; do echo $f; tail -1 $f | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
@@ -24,8 +24,8 @@ print('  value %.0f img/s  %.4f ms/step  h2h %s  pipelined %s  prerun %s ms | %s
 "; done
 # ---- 2. kernel trace of the headline bench, autotune launches excluded through the plan cache
 export TAMD_PLAN_CACHE=$O/plan_mobilenet_v1_int8_b1.txt
-python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline > /dev/null 2>&1          # writes the plan
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --warmup 100 --no-cpu-baseline > $O/bench_b1_under_rocprofv3.json 2> $O/trace.err
+python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --full > /dev/null 2>&1          # writes the plan
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --warmup 100 --no-cpu-baseline --full > $O/bench_b1_under_rocprofv3.json 2> $O/trace.err
 find $O/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/rocprofv3_kernel_stats_bench_b1.csv
 head -12 $O/rocprofv3_kernel_stats_bench_b1.csv | cut -c1-150
 unset TAMD_PLAN_CACHE

@@ -37,15 +37,15 @@ for cfg in "mobilenet_v1 1 int8" "resnet50 32 int8" "mobilenet_v1 64 int8" "yolo
 done
 rm -f $O/pmc_plan.txt
 # ---- 2. bench lines (each seeds its plan file from tengine_amd/plans/)
-python $R/bench.py --steps 20 --warmup 5 > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err
-python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 > $O/bench_b1.json 2>> $O/bench_b1.err
-python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
-python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
-python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
-python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
-python $R/bench.py --model yolov3_tiny --dtype uint8 --u8-integer --batch 8 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_yolov3_tiny_uint8_int_b8.json 2> $O/bench_yolo_int.err
-python $R/bench.py --model mssd --dtype uint8 --u8-integer --batch 16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_mssd_uint8_int_b16.json 2> $O/bench_mssd_int.err
-python $R/bench.py --model resnet50 --batch 16 --streams 2 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_resnet50_int8_b16x2streams.json 2> $O/bench_rn2.err
+python $R/bench.py --steps 20 --warmup 5 --full > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err
+python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 --full > $O/bench_b1.json 2>> $O/bench_b1.err
+python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 --full > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
+python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
+python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
+python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
+python $R/bench.py --model yolov3_tiny --dtype uint8 --u8-integer --batch 8 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_yolov3_tiny_uint8_int_b8.json 2> $O/bench_yolo_int.err
+python $R/bench.py --model mssd --dtype uint8 --u8-integer --batch 16 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_mssd_uint8_int_b16.json 2> $O/bench_mssd_int.err
+python $R/bench.py --model resnet50 --batch 16 --streams 2 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/bench_resnet50_int8_b16x2streams.json 2> $O/bench_rn2.err
 for f in $O/bench_*.json; do echo $f; tail -1 $f | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
@@ -53,7 +53,7 @@ r = j.get('roofline') or {}
 print('  value %.0f img/s  %.4f ms/step  h2h %s  pipelined %s  prerun %s ms plan %s | %s %s frac %.4f avg %.2f us traffic %s mfma_util %.2f%%' % (j['value'], j['ms_per_step'], j.get('host_to_host_images_per_s'), j.get('host_to_host_pipelined_images_per_s'), j.get('prerun_ms'), j.get('shipped_plan'), r.get('kernel'), r.get('bound'), r.get('frac', 0), r.get('avg_launch_us', 0), r.get('traffic'), r.get('mfma_util_pct', 0)))
 "; done
 # ---- 3. kernel trace of the headline bench (the shipped plan keeps autotune launches out of it)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --warmup 100 --no-cpu-baseline > $O/bench_b1_under_rocprofv3.json 2> $O/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --warmup 100 --no-cpu-baseline --full > $O/bench_b1_under_rocprofv3.json 2> $O/trace.err
 find $O/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/rocprofv3_kernel_stats_bench_b1.csv
 head -12 $O/rocprofv3_kernel_stats_bench_b1.csv | cut -c1-150
 # ---- 4. per-launch tables, and ResNet-50 inside a pass

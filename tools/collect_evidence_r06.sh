@@ -48,14 +48,14 @@ for cfg in "resnet50 32" "mobilenet_v1 64"; do        # VALU / wait / issue coun
 done
 rm -f $O/pmc_plan.txt
 # ---- 2. bench lines (each seeds its plan file from tengine_amd/plans/)
-( time python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err ) 2> $O/bench_b1_driver_invocation_time.txt
-python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 --configs none > $O/bench_b1.json 2>> $O/bench_b1.err
-python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
-python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
-python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
-python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
-python $R/bench.py --model yolov3_tiny --dtype uint8 --u8-integer --batch 8 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_yolov3_tiny_uint8_int_b8.json 2> $O/bench_yolo_int.err
-python $R/bench.py --model mssd --dtype uint8 --u8-integer --batch 16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_mssd_uint8_int_b16.json 2> $O/bench_mssd_int.err
+( time python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_b1_driver_invocation.json 2> $O/bench_b1.err ) 2> $O/bench_b1_driver_invocation_time.txt
+python $R/bench.py --steps 2000 --warmup 100 --cpu-seconds 8 --configs none --full > $O/bench_b1.json 2>> $O/bench_b1.err
+python $R/bench.py --model resnet50 --batch 32 --steps 100 --warmup 10 --cpu-seconds 6 --full > $O/bench_resnet50_int8_b32.json 2> $O/bench_rn.err
+python $R/bench.py --model mobilenet_v1 --batch 64 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/bench_mobilenet_v1_int8_b64.json 2> $O/bench_mb64.err
+python $R/bench.py --model yolov3_tiny --dtype uint8 --batch 8 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_yolov3_tiny_uint8_b8.json 2> $O/bench_yolo.err
+python $R/bench.py --model mssd --dtype uint8 --batch 16 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_mssd_uint8_b16.json 2> $O/bench_mssd.err
+python $R/bench.py --model yolov3_tiny --dtype uint8 --u8-integer --batch 8 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_yolov3_tiny_uint8_int_b8.json 2> $O/bench_yolo_int.err
+python $R/bench.py --model mssd --dtype uint8 --u8-integer --batch 16 --steps 50 --warmup 5 --no-cpu-baseline --full > $O/bench_mssd_uint8_int_b16.json 2> $O/bench_mssd_int.err
 for f in $O/bench_*.json; do echo $f; tail -1 $f | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
@@ -68,7 +68,7 @@ for k, c in (j.get('configs') or {}).items():
 # ---- 3. kernel trace + stats of every config's bench run (hipGraph replay under the tool: rocprofv3 cannot see the direct queue)
 for cfg in "mobilenet_v1 1 int8 2000" "mobilenet_v1 64 int8 200" "resnet50 32 int8 200" "yolov3_tiny 8 uint8 100" "mssd 16 uint8 100"; do
   set -- $cfg
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --model $1 --dtype $3 --batch $2 --steps $4 --warmup 20 --no-cpu-baseline --configs none --min-seconds 0 > $O/bench_$1_$3_b$2_under_rocprofv3.json 2> $O/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --model $1 --dtype $3 --batch $2 --steps $4 --warmup 20 --no-cpu-baseline --configs none --min-seconds 0 --full > $O/bench_$1_$3_b$2_under_rocprofv3.json 2> $O/trace.err
   find $O/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/rocprofv3_kernel_stats_bench_$1_$3_b$2.csv
   rm -rf $O/trace
   echo "== $cfg"; head -6 $O/rocprofv3_kernel_stats_bench_$1_$3_b$2.csv | cut -c1-160

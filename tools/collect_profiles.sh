@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --steps 500 --warmup 50 > $O/bench_b1.json 2> $O/bench_b1.err
+python $R/bench.py --steps 500 --warmup 50 --full > $O/bench_b1.json 2> $O/bench_b1.err
 tail -1 $O/bench_b1.json | cut -c1-400
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 500 --warmup 50 --no-cpu-baseline > $O/bench_b1_traced.json 2> $O/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 500 --warmup 50 --no-cpu-baseline --full > $O/bench_b1_traced.json 2> $O/trace.err
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $O/calib_$c -- $R/tools/exp/hbm_calib.bin > $O/calib_$c.log 2>&1
   rocprofv3 --pmc $c --output-format csv -d $O/model_$c -- python $R/tools/run_model.py mobilenet_v1 1 10 int8 > $O/model_$c.log 2>&1
