@@ -208,16 +208,23 @@ namespace tamd {
 // planner helpers shared by graph_plan.hip (int8, NHWC) and graph_u8.hip (uint8, NCHW)
 PoolGeom pool_geom(const tamd_pool_param& p, int h, int w);
 int dev_alloc(tamd_graph* g, void** p, size_t bytes, bool zero);
-// plan-time autotune: candidates of a graph whose pass moves far more bytes than the L2s hold are timed COLD -- every timed
-// launch behind a fill of kL2FlushBytes (l2_flush_buffer(): one per device, kept for the life of the process) -- because that
-// is how they run inside a pass; small graphs (batch-1 classifiers live in the L2s from step to step) keep back-to-back timing
-constexpr size_t kL2FlushBytes = 64u << 20;
-void* l2_flush_buffer();
-bool autotune_cold(tamd_graph* g);
-// TAMD_PLAN_CACHE=<file>: "<site>|<node>|<shape>" -> what the plan-time autotune chose (plan_cache.hip)
-bool plan_cache_get(const std::string& key, std::string* v);
-void plan_cache_put(const std::string& key, const std::string& v);
-int time_cold(tamd_graph* g, void* flush, const std::function<hipError_t()>& launch, float* ms_out);      // graph_plan.hip
+// plan-time races (plan_cache.hip).  A candidate: the plan-cache tag that names it, how to launch it (one launch, or several
+// back to back: the two unfused steps of a pair, the three Winograd launches), the kernel name TAMD_DEBUG prints (empty: the
+// tag) and whether a cached tag may still pick it (unset: yes; a pinned site answers no, it never reads the plan file).
+struct RaceCand {
+    std::string tag;
+    std::function<hipError_t(hipStream_t)> fn;
+    std::string name;
+    std::function<bool()> live;
+};
+// plan_race: the winner's index.  cands[0] is the incumbent (the heuristic choice; also the answer when `tune` is false); a
+// candidate that does not launch is skipped; a later one wins when it beats the best so far by `margin` (ms < best * margin), so
+// in an ordered list the last to do so wins.  A non-empty `key` is looked up in the plan cache first (TAMD_PLAN_CACHE: a tag that
+// names a live candidate answers without timing) and gets the winner's tag; an empty key neither reads nor writes.  -1: HIP error.
+int plan_race(tamd_graph* g, const std::string& node, const std::vector<RaceCand>& cands, const std::string& key, float margin, bool tune);
+// the lookup alone: the index of the live candidate whose tag the cached entry of `key` holds, -1: none
+int plan_cached(const std::string& key, const std::vector<RaceCand>& cands);
+bool autotune_enabled();           // TAMD_AUTOTUNE=0: no site races, every one keeps its incumbent
 void nhwc_geom(HTensor& t);
 int count_consumers(const tamd_graph* g, int tensor);
 int priorbox_count(const tamd_priorbox_param& p);

@@ -63,28 +63,6 @@ static int plan_gemm_f32(tamd_graph* g, HNode& n, const float* xdev, int N, int 
     return 0;
 }
 
-// per-launch time of a list of launches run back to back (best of two bursts)
-static int time_steps(tamd_graph* g, const std::vector<std::function<hipError_t(hipStream_t)>>& fns, float* ms_out)
-{
-    hipEvent_t e0, e1;
-    *ms_out = 1e30f;
-    for (auto& f : fns)
-        if (f(g->stream) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    for (int round = 0; round < 2; round++) {
-        float t = 0;
-        HIPCHK(hipEventRecord(e0, g->stream));
-        for (int it = 0; it < 10; it++)
-            for (auto& f : fns) (void)f(g->stream);
-        HIPCHK(hipEventRecord(e1, g->stream));
-        HIPCHK(hipEventSynchronize(e1));
-        HIPCHK(hipEventElapsedTime(&t, e0, e1));
-        *ms_out = std::min(*ms_out, t / 10);
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return 0;
-}
-
 // Winograd F(2,3) form of the 3x3 / stride 1 convolution whose direct form is the LAST step of g->steps: replaces it when it
 // is faster (or when TAMD_F32_WINOGRAD=1).  U = G g G^T with G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], evaluated in double
 // and rounded once.
@@ -142,13 +120,16 @@ static int plan_winograd_f32(tamd_graph* g, HNode& n, const HTensor& x, const HT
     std::vector<std::function<hipError_t(hipStream_t)>> wino = {[a](hipStream_t s) { return launch_wino_in_f32(a, s); },
                                                                  [a](hipStream_t s) { return launch_wino_gemm_f32(a, s); },
                                                                  [a](hipStream_t s) { return launch_wino_out_f32(a, s); }};
-    bool use = mode == 1;
-    if (mode != 1) {
-        float tw = 0, td = 0;
-        if (time_steps(g, wino, &tw) || time_steps(g, {direct.fn}, &td)) { drop(); return -1; }
-        use = tw * 3.f < td * 0.97f;                              // time_steps reports per launch: three against one
-        if (getenv("TAMD_DEBUG")) fprintf(stderr, "tengine_amd: %s: winograd F(2,3) %.2f us vs direct %.2f us -> %s\n", n.name.c_str(), 3e3f * tw, 1e3f * td, use ? "winograd" : "direct");
-    }
+    // tw = the three Winograd launches together, td = the direct launch: Winograd when 3 tw < 0.97 td.  Not cached; timed even under
+    // TAMD_AUTOTUNE=0 (TAMD_F32_WINOGRAD alone governs this site)
+    const RaceCand direct_c{"direct", direct.fn, direct.kernel};
+    const RaceCand wino_c{"winograd", [wino](hipStream_t s) {
+                              for (auto& f : wino) { const hipError_t e = f(s); if (e != hipSuccess) return e; }
+                              return hipSuccess;
+                          }, "winograd F(2,3)"};
+    const int win = mode == 1 ? 1 : plan_race(g, n.name, {direct_c, wino_c}, "", 0.97f / 3.f, true);
+    if (win < 0) { drop(); return -1; }
+    const bool use = win == 1;
     if (!use) { HIPCHK(hipStreamSynchronize(g->stream)); drop(); return 0; }
     for (void* q : mine) g->dev_allocs.push_back(q);           // from here on the graph owns them (freed by tamd_graph_destroy)
     g->steps.pop_back();

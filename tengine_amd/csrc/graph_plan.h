@@ -12,9 +12,6 @@ struct RqFold { float m1, lo, hi, out_scale; std::vector<float> m2; };
 RqFold fold_requant(int mode, int act, float in_s, float out_s, const HTensor& w, int cout);
 int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, RqArgs* rq);
 bool exp_plain_kernels();
-// plan-time timing of one candidate launch; whether the plan-time races run at all (TAMD_AUTOTUNE)
-int time_fn(tamd_graph* g, const std::function<hipError_t(hipStream_t)>& fn, float* ms_out);
-bool autotune_enabled();
 std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps);
 
 // the arguments of the last depthwise 3x3 / implicit-GEMM convolution planned on this thread (dwpw.hip: depthwise -> pointwise in one

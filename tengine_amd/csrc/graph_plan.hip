@@ -161,105 +161,6 @@ int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, Rq
     return 0;
 }
 
-void* l2_flush_buffer()
-{
-    static std::mutex mu;
-    static std::map<int, void*> per_dev;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = per_dev.find(dev);
-    if (it != per_dev.end()) return it->second;
-    void* p = nullptr;
-    if (hipMalloc(&p, kL2FlushBytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
-    per_dev[dev] = p;
-    return p;
-}
-
-bool autotune_cold(tamd_graph* g)
-{
-    if (g->autotune_cold < 0) {
-        const char* e = exp_env("TAMD_AUTOTUNE_COLD");              // 0: always warm, 1: always cold
-        size_t bytes = 0;
-        for (const HTensor& t : g->tensors)
-            bytes += (t.ttype == TAMD_TT_VAR || t.ttype == TAMD_TT_INPUT) && t.n > 0 ? (size_t)t.n * t.h * t.w * (t.cs > 0 ? t.cs : t.c) : t.elems() * (t.dtype == TAMD_DT_FP32 ? 4 : 1);
-        g->autotune_cold = e ? (atoi(e) != 0) : bytes > (size_t)(48u << 20);      // tensors + weights of one pass vs 32 MB of L2
-    }
-    return g->autotune_cold == 1;
-}
-
-// one candidate the way it runs inside a pass: the fill evicts its weights (and everything else) from the L2s, the step planned
-// just before it -- as a rule the producer of its input -- runs again and leaves that input where a pass leaves it, then the
-// candidate is timed on its own.  Five samples, the slowest dropped.
-int time_cold(tamd_graph* g, void* flush, const std::function<hipError_t()>& launch, float* ms_out)
-{
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    const Step* prev = nullptr;
-    for (size_t i = g->steps.size(); i-- > 0 && !prev;)
-        if (!g->steps[i].once) prev = &g->steps[i];
-    float tot = 0.f, worst = 0.f;
-    const int reps = 5;
-    for (int it = 0; it < reps; it++) {
-        float t = 0;
-        HIPCHK(hipMemsetAsync(flush, it, kL2FlushBytes, g->stream));
-        if (prev) (void)prev->fn(g->stream);
-        HIPCHK(hipEventRecord(e0, g->stream));
-        (void)launch();
-        HIPCHK(hipEventRecord(e1, g->stream));
-        HIPCHK(hipEventSynchronize(e1));
-        HIPCHK(hipEventElapsedTime(&t, e0, e1));
-        tot += t;
-        worst = std::max(worst, t);
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    (void)hipGetLastError();
-    *ms_out = (tot - worst) / (reps - 1);
-    return 0;
-}
-
-// average duration of one launch of `fn` on the graph's stream (plan-time autotune): back to back, or each launch behind an
-// L2-evicting fill (autotune_cold)
-int time_fn(tamd_graph* g, const std::function<hipError_t(hipStream_t)>& fn, float* ms_out)
-{
-    hipEvent_t e0, e1;
-    *ms_out = 1e30f;
-    hipError_t err = fn(g->stream);
-    if (err == hipSuccess) err = fn(g->stream);
-    if (err != hipSuccess) { (void)hipGetLastError(); return 0; }
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    if (void* flush = autotune_cold(g) ? l2_flush_buffer() : nullptr) {
-        hipEventDestroy(e0); hipEventDestroy(e1);
-        return time_cold(g, flush, [&]() { return fn(g->stream); }, ms_out);
-    }
-    // best of two timed bursts (the ranking decides the plan: run-to-run noise of a single burst showed up as 5-10 % swings of
-    // whole-model times); short kernels (batch-1 layers are a few microseconds) get longer bursts
-    float ms = 1e30f;
-    int reps = 8;
-    for (int round = 0; round < 3; round++) {
-        float t = 0;
-        HIPCHK(hipEventRecord(e0, g->stream));
-        for (int it = 0; it < reps; it++) (void)fn(g->stream);
-        HIPCHK(hipEventRecord(e1, g->stream));
-        HIPCHK(hipEventSynchronize(e1));
-        HIPCHK(hipEventElapsedTime(&t, e0, e1));
-        t /= reps;
-        if (round == 0 && t <= 0.02f) { reps = 40; continue; }      // re-measure short kernels with a longer burst
-        ms = std::min(ms, t);
-        if (round == 0) round = 1;                                  // long kernel: bursts 0 and 2
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    *ms_out = ms;
-    return 0;
-}
-
-bool autotune_enabled()
-{
-    const char* at_env = getenv("TAMD_AUTOTUNE");
-    return !(at_env && atoi(at_env) == 0);
-}
-
-
 // pointwise weight panel in MFMA fragment order: [16-channel slice][64-deep K step][lane = (k block of 16) * 16 + channel][16 B];
 // `wd` = [C][K] int8 rows (1x1 conv: K = cin; first conv: K = cin*KH*KW in OIHW order), zero padded to nsteps * 64
 std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps)
@@ -447,8 +348,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
         }
         // candidates: every kernel of the family computes the same bytes (exact integer GEMM + the same epilogue), so
         // the choice is purely a matter of speed
-        struct Cand { std::string name; std::function<hipError_t(hipStream_t)> fn; };
-        std::vector<Cand> cands;
+        std::vector<RaceCand> cands;        // tag = kernel name
         // (the fused eltwise tail lives in the conv_igemm / conv_igemm2 / pw_stream epilogues)
         if (!fz && gemm_direct_applicable(a)) cands.push_back({"gemm_direct_i8", [a](hipStream_t s) { return launch_gemm_direct(a, s); }});
         if (pw_stream_applicable(a)) cands.push_back({"pw_stream_i8", [a](hipStream_t s) { return launch_pw_stream(a, s); }});
@@ -505,7 +405,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
                 int th = std::max(1, std::min(x.h, px / std::max(1, x.w)));
                 v.TH = th; v.tiles_y = (x.h + th - 1) / th;
                 bool dup = false;
-                for (auto& c : cands) dup |= c.name == "pw_small_i8<" + std::to_string(th) + ">";
+                for (auto& c : cands) dup |= c.tag == "pw_small_i8<" + std::to_string(th) + ">";
                 if (dup || !pwdw_config_ok(v, 256)) continue;
                 const PwDwArgs vc = v;
                 cands.push_back({"pw_small_i8<" + std::to_string(th) + ">", [vc](hipStream_t s) { return launch_pwdw(vc, 256, s); }});
@@ -526,37 +426,22 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
         }
         if (const char* force = getenv("TAMD_FORCE_GEMM")) {     // tests: pin one member of the family (read at every prerun)
             const std::string want = force;
-            std::vector<Cand> only;
+            std::vector<RaceCand> only;
             for (int c = 0; c < conv_igemm_num_cfgs(); c++) {
                 ConvArgs ac = a; ac.cfg = c;
                 if (want == "igemm" + std::to_string(c) && conv_igemm_cfg_ok(a, c)) only.push_back({conv_igemm_kernel_name(ac), [ac](hipStream_t s) { return launch_conv_igemm(ac, s); }});
             }
             for (auto& c : cands)
-                if (c.name.find(want) == 0) only.push_back(c);
+                if (c.tag.find(want) == 0) only.push_back(c);
             if (!only.empty()) cands = only;
         }
-        size_t best = 0;
         char ckey[256];
         snprintf(ckey, sizeof(ckey), "gemm|%s|%dx%dx%dx%d>%d k%dx%d s%d%s", n.name.c_str(), x.n, x.c, x.h, x.w, cout, KH, KW, p.stride_h, fz ? "+elt" : "");
-        std::string cached;
-        bool from_cache = false;
-        if (autotune && cands.size() > 1 && plan_cache_get(ckey, &cached))
-            for (size_t c = 0; c < cands.size() && !from_cache; c++)
-                if (cands[c].name == cached) { best = c; from_cache = true; }
-        if (autotune && cands.size() > 1 && !from_cache) {
-            // plan-time autotune: a few timed launches of each candidate on the real buffers (outputs are overwritten
-            // again by the first real run); the heuristics above remain the fallback (TAMD_AUTOTUNE=0)
-            float best_ms = 1e30f;
-            for (size_t c = 0; c < cands.size(); c++) {
-                float ms;
-                if (time_fn(g, cands[c].fn, &ms)) return -1;
-                if (ms > 1e29f) continue;
-                // the heuristic candidates come first: a later one has to win by more than the timing noise
-                if (best_ms > 1e29f || ms < best_ms * 0.96f) { best_ms = ms; best = c; }
-            }
-            plan_cache_put(ckey, cands[best].name);
-        }
-        st.kernel = cands[best].name + (fz ? (fz->relu ? "+eltwise+relu" : "+eltwise") : "");
+        // the heuristic candidates come first: a later one has to win by more than the timing noise; the heuristics remain the
+        // fallback (TAMD_AUTOTUNE=0)
+        const int best = plan_race(g, n.name, cands, ckey, 0.96f, autotune && cands.size() > 1);
+        if (best < 0) return -1;
+        st.kernel = cands[best].tag + (fz ? (fz->relu ? "+eltwise+relu" : "+eltwise") : "");
         st.fn = cands[best].fn;
     }
     if (!fz) {                           // reads its input, writes its output (constants aside), one launch: all a convolution / FC step touches

@@ -70,6 +70,14 @@ int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod)
     return -1;
 }
 
+// the incumbent of a fusion race: the pair's two planned steps, launched back to back
+static RaceCand two_launches(const std::string& tag, const Step& sa, const Step& sb)
+{
+    const std::function<hipError_t(hipStream_t)> fa = sa.fn, fb = sb.fn;
+    return {tag, [fa, fb](hipStream_t s) { const hipError_t e = fa(s); return e != hipSuccess ? e : fb(s); }, sa.kernel + " + " + sb.kernel};
+}
+
+
 // The two nodes were just planned as steps [s0, s0 + 2); build the fused launch, and keep whichever is faster
 // (plan-time measurement; without autotune: fuse the small-map cases where launches, not bytes, are the cost).
 // TAMD_FUSE_PWDW=0 never fuses, =2 always fuses; TAMD_PWDW_CFG="TH,TW,threads" pins the tile configuration (tests).
@@ -212,7 +220,6 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
     Step& sa = g->steps[s0];
     Step& sb = g->steps[s0 + 1];
     const bool autotune = autotune_enabled() && sa.macs >= 4e6;
-    size_t best = 0;
     // fused by construction (no race): a link of a LATENCY chain only -- batch 1.  Everything batched keeps the race against the two-launch
     // plan below (batch 8 at 56x56 or batch 16 at 19x19 are throughput launches; round 6's first evidence pass showed what the
     // wider rule costs where the race is skipped: MobileNet-v1 b64's 7x7 tail fused by construction ran conv6/sep + pool6 in 34.9 us
@@ -221,35 +228,40 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
     // cost model inputs below use the map the tail reads (a.H x a.W) and the reduction depth
     char ckey[256];
     snprintf(ckey, sizeof(ckey), "pwdw|%s|n%d %dx%d k%d m%d f%d c%zu", sa.node.c_str(), a.N, a.H, a.W, a.ktot, tmode, fmode, cfgs.size());
-    std::string cached;
-    int cf = 0, cb = 0;
-    bool from_cache = false;
-    if (autotune && plan_cache_get(ckey, &cached) && sscanf(cached.c_str(), "%d,%d", &cf, &cb) == 2 && cb >= 0 && cb < (int)cfgs.size()) {
-        // a cached index is only as good as the file it came from: the configuration must still launch here
-        const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[cb].th, cfgs[cb].tw, cfgs[cb].sl) : a;
-        if (!cf || launch_pwdw(v, cfgs[cb].threads, g->stream) == hipSuccess) { fuse = cf != 0; best = (size_t)cb; from_cache = true; }
-        else (void)hipGetLastError();
+    // one entry "<fuse>,<cfg>" answers both races below: "1,<c>" the fused launch in tile configuration c, which must still launch
+    // here (a cached index is only as good as the file it came from), "0,<c>" two launches
+    std::vector<RaceCand> tiles, answers;
+    for (size_t c = 0; c < cfgs.size(); c++) {
+        const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[c].th, cfgs[c].tw, cfgs[c].sl) : a;
+        const int threads = cfgs[c].threads;
+        hipStream_t stream = g->stream;
+        tiles.push_back({"1," + std::to_string(c), [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); }, "pwdw cfg " + std::to_string(c),
+                         [v, threads, stream]() {
+                             if (launch_pwdw(v, threads, stream) == hipSuccess) return true;
+                             (void)hipGetLastError();
+                             return false;
+                         }});
     }
-    if (from_cache) {
+    answers = tiles;
+    for (size_t c = 0; c < cfgs.size(); c++) answers.push_back({"0," + std::to_string(c), nullptr});
+    int best = 0;
+    const int hit = autotune ? plan_cached(ckey, answers) : -1;
+    if (hit >= 0) {
+        fuse = hit < (int)cfgs.size();
+        best = hit % (int)cfgs.size();
     } else if (autotune) {
-        float best_ms = 1e30f;
-        for (size_t c = 0; c < cfgs.size(); c++) {
-            const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[c].th, cfgs[c].tw, cfgs[c].sl) : a;
-            const int threads = cfgs[c].threads;
-            float ms;
-            if (time_fn(g, [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); }, &ms)) return -1;
-            if (ms < best_ms) { best_ms = ms; best = c; }
+        // the fastest tile configuration.  A small pair is a link of a latency chain (batch 1: 3.4 us per dependent launch whatever it
+        // does): one launch instead of two is right by construction there, and the race -- which times a launch back to back with
+        // ITSELF, i.e. its throughput -- gets exactly these wrong now and then (conv6/sep + pool6 left as two launches: 54.9 instead of
+        // 51.4 us per MobileNet-v1 pass, profiles/r05_ab_b1_call12_vs_now_v2.txt, r05_ab_firstdw_pingpong_mobilenet_v1_b1.txt).
+        // Timed against two launches: the batched pairs only.
+        const bool batched = fmode != 2 && !fuse;
+        if ((best = plan_race(g, sa.node, tiles, batched ? "" : ckey, 1.0f, true)) < 0) return -1;
+        if (batched) {
+            const int w = plan_race(g, sa.node, {two_launches("0," + std::to_string(best), sa, sb), tiles[best]}, ckey, 0.97f, true);
+            if (w < 0) return -1;
+            fuse = w == 1;
         }
-        // A small pair is a link of a latency chain (batch 1: 3.4 us per dependent launch whatever it does): one launch instead of two
-        // is right by construction there, and the race -- which times a launch back to back with ITSELF, i.e. its throughput -- gets
-        // exactly these wrong now and then (conv6/sep + pool6 left as two launches: 54.9 instead of 51.4 us per MobileNet-v1 pass,
-        // profiles/r05_ab_b1_call12_vs_now_v2.txt, r05_ab_firstdw_pingpong_mobilenet_v1_b1.txt).  Timed: the batched pairs only.
-        if (fmode != 2 && !fuse) {
-            float ta, tb;
-            if (time_fn(g, sa.fn, &ta) || time_fn(g, sb.fn, &tb)) return -1;
-            fuse = best_ms < 0.97f * (ta + tb);
-        }
-        plan_cache_put(ckey, std::to_string(fuse ? 1 : 0) + "," + std::to_string(best));
     }
     if (!fuse) return 0;
     const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[best].th, cfgs[best].tw, cfgs[best].sl) : a;
@@ -301,15 +313,10 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, size_t s0)
     if (fmode != 2) {
         char ckey[256];
         snprintf(ckey, sizeof(ckey), "dwpw|%s|n%d %dx%d c%d>%d", sa.node.c_str(), d.N, d.OH, d.OW, d.C, c.cout);
-        std::string cached;
-        if (autotune_enabled() && plan_cache_get(ckey, &cached)) fuse = cached == "1";
-        else if (autotune_enabled()) {
-            float tf, ta, tb;
-            if (time_fn(g, [a](hipStream_t s) { return launch_dwpw(a, s); }, &tf) || time_fn(g, sa.fn, &ta) || time_fn(g, sb.fn, &tb)) return -1;
-            fuse = tf < 0.97f * (ta + tb);
-            if (getenv("TAMD_DEBUG")) fprintf(stderr, "[tamd] %s + %s: dwpw %.2f us vs %.2f + %.2f us -> %s\n", sa.node.c_str(), sb.node.c_str(), 1e3 * tf, 1e3 * ta, 1e3 * tb, fuse ? "fused" : "two launches");
-            plan_cache_put(ckey, fuse ? "1" : "0");
-        }
+        const RaceCand fused{"1", [a](hipStream_t s) { return launch_dwpw(a, s); }, "dwpw_i8"};
+        const int w = plan_race(g, sa.node, {two_launches("0", sa, sb), fused}, ckey, 0.97f, autotune_enabled());
+        if (w < 0) return -1;
+        fuse = w == 1;
     }
     if (!fuse) return 0;
     Step st;

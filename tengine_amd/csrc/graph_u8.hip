@@ -270,46 +270,24 @@ static int plan_conv_u8(tamd_graph* g, HNode& n, const HNode* relu = nullptr, co
                         if (!done && bl > most) { most = bl; pick = c; }
                     }
                 }
-                const char* iat_env = getenv("TAMD_AUTOTUNE");
                 char ikey[256];
                 snprintf(ikey, sizeof(ikey), "u8iconv|%s|%dx%dx%dx%d>%d k%dx%d s%d d%d%s%s", n.name.c_str(), x.n, x.c, x.h, x.w, cout, p.kernel_h, p.kernel_w,
                          p.stride_h, p.dilation_h, relu ? "+relu" : "", pool ? "+pool" : "");
-                std::string icached;
-                const bool itune = !(iat_env && atoi(iat_env) == 0) && st.macs >= 4e6 && cands.size() > 1;
-                bool ifrom_cache = false;
-                if (itune && plan_cache_get(ikey, &icached) && icached.size() >= 2 && icached[0] == 'i') {
-                    const int c = atoi(icached.c_str() + 1);
-                    if (std::find(cands.begin(), cands.end(), c) != cands.end()) { pick = c; ifrom_cache = true; }
+                // the heuristic pick is timed first; another shape has to beat it by more than the timing noise
+                std::vector<int> order{pick};
+                for (int c : cands) if (c != pick) order.push_back(c);
+                std::vector<RaceCand> race;
+                for (int c : order) {
+                    U8ConvArgs ac = a;
+                    iprepare(ac, c);
+                    race.push_back({"i" + std::to_string(c), [&, c](hipStream_t s) {
+                                        U8ConvArgs ar = a;
+                                        return iready(ar, c) ? hipErrorOutOfMemory : ilaunch(ar, c, s);
+                                    }, iname(ac, c)});
                 }
-                if (itune && !ifrom_cache) {
-                    hipEvent_t e0, e1;
-                    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-                    void* flush = autotune_cold(g) ? l2_flush_buffer() : nullptr;
-                    float best_ms = 1e30f;
-                    std::vector<int> order{pick};
-                    for (int c : cands) if (c != pick) order.push_back(c);
-                    for (int c : order) {
-                        U8ConvArgs ac = a;
-                        if (iready(ac, c)) return -1;
-                        auto launch = [&]() { return ilaunch(ac, c, g->stream); };
-                        float ms = 1e30f;
-                        if (launch() != hipSuccess) { (void)hipGetLastError(); continue; }
-                        if (flush) { if (time_cold(g, flush, launch, &ms)) return -1; }
-                        else {
-                            const int reps = 10;
-                            HIPCHK(hipEventRecord(e0, g->stream));
-                            for (int it = 0; it < reps; it++) (void)launch();
-                            HIPCHK(hipEventRecord(e1, g->stream));
-                            HIPCHK(hipEventSynchronize(e1));
-                            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-                            ms /= reps;
-                        }
-                        if (getenv("TAMD_DEBUG")) fprintf(stderr, "[tamd] %s: %s %.2f us\n", n.name.c_str(), iname(ac, c), 1e3 * ms);
-                        if (best_ms > 1e29f || ms < best_ms * 0.96f) { best_ms = ms; pick = c; }
-                    }
-                    hipEventDestroy(e0); hipEventDestroy(e1);
-                    plan_cache_put(ikey, "i" + std::to_string(pick));
-                }
+                const int w = plan_race(g, n.name, race, ikey, 0.96f, autotune_enabled() && st.macs >= 4e6 && cands.size() > 1);
+                if (w < 0) return -1;
+                pick = order[w];
                 if (iready(a, pick)) return -1;
                 st.rd.push_back(access_of(x));
                 st.wr.push_back(access_of(y));
@@ -383,64 +361,30 @@ static int plan_conv_u8(tamd_graph* g, HNode& n, const HNode* relu = nullptr, co
         };
         bool use_rgb = false, use_pw = false;           // conv_u8_rgb3x3 / conv_u8_pw (shallow pointwise layers of large maps)
         const char* pw_env = tamd_pin("u8_pw");                     // 0: never, 1: wherever it applies (tests)
-        const char* at_env = getenv("TAMD_AUTOTUNE");
-        const bool tune = !(at_env && atoi(at_env) == 0) && st.macs >= 4e6 && !tamd_pin("u8_cfg");
-        // what the autotune decided last time (TAMD_PLAN_CACHE): "g<cfg>" GEMM family, "p<cfg>" patch kernel, "rgb"
-        char ckey[256];
-        snprintf(ckey, sizeof(ckey), "u8conv|%s|%dx%dx%dx%d>%d k%dx%d s%d d%d%s%s", n.name.c_str(), x.n, x.c, x.h, x.w, cout, p.kernel_h, p.kernel_w,
-                 p.stride_h, p.dilation_h, relu ? "+relu" : "", pool ? "+pool" : "");
-        std::string cached;
-        bool from_cache = false;
-        if (tune && !pk_force && !rgb_env && !pk_env && !pw_env && !c3_env && plan_cache_get(ckey, &cached) && cached.size() >= 2) {
-            const int c = atoi(cached.c_str() + 1);
-            if (cached == "rgb" && rgb_ok) { use_rgb = true; from_cache = true; }
-            else if (cached == "pw" && conv_u8_pw_applicable(a, p.kernel_h, p.kernel_w)) { use_pw = true; from_cache = true; }
-            else if (cached == "c3" && c3_ok) { use_c3 = true; from_cache = true; }
-            else if (cached[0] == 'g' && c >= 0 && c < conv_u8_gemm_num_cfgs()) {
-                U8ConvArgs ac = a; ac.cfg = c; ac.Kpad = rup(K, conv_u8_gemm_kc(c));
-                if (conv_u8_gemm_lds(ac) <= 150 * 1024) { a.cfg = c; from_cache = true; }      // the same filter the autotune applies
-            }
-            else if (cached[0] == 'p' && c >= 0 && c < conv_u8_patch_num_cfgs()) { U8ConvArgs ac = a; if (patch_for(ac, c) == 1) { pk_best = c; from_cache = true; } }
-        }
-        if (tune && !from_cache) {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            float best_ms = 1e30f;
-            int best_cfg = a.cfg;
-            // per-launch time of a candidate AS IT RUNS INSIDE A PASS (time_cold: weights evicted, input left by its producer);
-            // back-to-back launches of one layer flatter the latency-bound members by 30-60 % (profiles/r03_insitu_*).
-            // Small graphs / TAMD_AUTOTUNE_COLD=0: warm timing (a warm-up launch, then 5 back-to-back launches, 25 when that is
-            // under 20 us)
-            void* flush = autotune_cold(g) ? l2_flush_buffer() : nullptr;
-            auto time_of = [&](const std::function<hipError_t()>& launch, float* out) -> int {
-                if (launch() != hipSuccess) { (void)hipGetLastError(); *out = 1e30f; return 0; }
-                if (flush) return time_cold(g, flush, launch, out);
-                int reps = 5;
-                for (int round = 0; round < 2; round++) {
-                    HIPCHK(hipEventRecord(e0, g->stream));
-                    for (int it = 0; it < reps; it++) (void)launch();
-                    HIPCHK(hipEventRecord(e1, g->stream));
-                    HIPCHK(hipEventSynchronize(e1));
-                    HIPCHK(hipEventElapsedTime(out, e0, e1));
-                    *out /= reps;
-                    if (*out > 0.02f) break;
-                    reps = 25;
-                }
-                return 0;
-            };
-            // the heuristic choice is timed first; another shape has to beat it by more than the timing noise
+        const bool tune = autotune_enabled() && st.macs >= 4e6 && !tamd_pin("u8_cfg");
+        if (tune) {
+            // the race, one ordered list: the GEMM family's tile shapes (the heuristic one first), the patch kernel's configurations,
+            // conv_u8_pw, conv_u8_c3, conv_u8_rgb3x3 -- the last to beat the best so far by more than the timing noise wins.  Per-launch
+            // times as the candidates run inside a pass (plan_race's cold timing: back-to-back launches of one layer flatter the
+            // latency-bound members by 30-60 %, profiles/r03_insitu_*).  The plan cache records "g<cfg>" GEMM family, "p<cfg>" patch
+            // kernel, "pw", "c3" or "rgb"; a pinned race (u8_patch, u8_rgb3x3, u8_pw, u8_c3) never reads the file, it still writes it
+            char ckey[256];
+            snprintf(ckey, sizeof(ckey), "u8conv|%s|%dx%dx%dx%d>%d k%dx%d s%d d%d%s%s", n.name.c_str(), x.n, x.c, x.h, x.w, cout, p.kernel_h, p.kernel_w,
+                     p.stride_h, p.dilation_h, relu ? "+relu" : "", pool ? "+pool" : "");
+            const bool pinned = pk_env || rgb_env || pw_env || c3_env;
+            const std::function<bool()> unpinned = [pinned]() { return !pinned; };
+            std::vector<RaceCand> race, patches;
             std::vector<int> order{a.cfg};
             for (int c = 0; c < conv_u8_gemm_num_cfgs(); c++)
                 if (c != a.cfg) order.push_back(c);
             for (int c : order) {
                 U8ConvArgs ac = a; ac.cfg = c; ac.Kpad = rup(K, conv_u8_gemm_kc(c));
                 if (conv_u8_gemm_lds(ac) > 150 * 1024) continue;
-                if ((ac.wq = pack_for(c)) == nullptr) return -1;
-                float ms = 0;
-                if (time_of([&]() { return launch_conv_u8_gemm(ac, g->stream); }, &ms)) return -1;
-                if (best_ms > 1e29f || ms < best_ms * 0.96f) { best_ms = ms; best_cfg = c; }
+                race.push_back({"g" + std::to_string(c), [&, ac, c](hipStream_t s) {
+                                    U8ConvArgs ar = ac;
+                                    return (ar.wq = pack_for(c)) ? launch_conv_u8_gemm(ar, s) : hipErrorOutOfMemory;
+                                }, conv_u8_gemm_kernel_name(ac), unpinned});
             }
-            float pk_ms = 1e30f;
             const char* pcfg = tamd_pin("u8_patch_cfg");
             int named = -1;
             if (pk_force && pcfg) {
@@ -449,47 +393,43 @@ static int plan_conv_u8(tamd_graph* g, HNode& n, const HNode* relu = nullptr, co
                 if (conv_u8_patch_prepare(ac, c, p.kernel_h, p.kernel_w, p.dilation_h, p.dilation_w)) named = c;
             }
             for (int c = 0; c < conv_u8_patch_num_cfgs(); c++) {
-                // TAMD_U8_PATCH=1 pins the MFMA patch kernel (tests): the lanes configuration only competes there when it is named
                 // TAMD_U8_PATCH=1 + TAMD_U8_PATCH_CFG=<c>: that configuration alone competes where it applies (tests pin forms with it);
                 // without a name the lanes configuration stays out of the forced race (it pins the MFMA patch kernel)
                 if (pk_force && named >= 0 && c != named) continue;
                 if (pk_force && named < 0 && c == conv_u8_patch_lanes_cfg()) continue;
                 U8ConvArgs ac = a;
-                const int r = patch_for(ac, c);
-                if (r < 0) return -1;
-                if (!r) continue;
-                float ms = 0;
-                if (time_of([&]() { return launch_conv_u8_patch(ac, g->stream); }, &ms)) return -1;
-                if (getenv("TAMD_DEBUG")) fprintf(stderr, "[tamd] %s: %s %.2f us (gemm family best %.2f us)\n", n.name.c_str(), conv_u8_patch_kernel_name(ac), 1e3 * ms, 1e3 * best_ms);
-                if (pk_force ? ms < pk_ms : ms < best_ms * 0.96f) { pk_best = c; pk_ms = ms; if (!pk_force) best_ms = ms; }
+                if (!conv_u8_patch_prepare(ac, c, p.kernel_h, p.kernel_w, p.dilation_h, p.dilation_w)) continue;
+                patches.push_back({"p" + std::to_string(c), [&, c](hipStream_t s) {
+                                       U8ConvArgs ar = a;
+                                       return patch_for(ar, c) == 1 ? launch_conv_u8_patch(ar, s) : hipErrorOutOfMemory;
+                                   }, conv_u8_patch_kernel_name(ac), [&, pinned, c]() { U8ConvArgs ar = a; return !pinned && patch_for(ar, c) == 1; }});
             }
-            if (conv_u8_pw_applicable(a, p.kernel_h, p.kernel_w)) {
-                U8ConvArgs ac = a;
-                if (pw_ready(ac)) return -1;
-                {
-                    float ms = 1e30f;
-                    if (time_of([&]() { return launch_conv_u8_pw(ac, g->stream); }, &ms)) return -1;
-                    if (getenv("TAMD_DEBUG")) fprintf(stderr, "[tamd] %s: %s %.2f us (best so far %.2f us)\n", n.name.c_str(), conv_u8_pw_kernel_name(ac), 1e3 * ms, 1e3 * best_ms);
-                    if (ms < best_ms * 0.96f) { use_pw = true; best_ms = ms; }
+            if (pk_force) {
+                // TAMD_U8_PATCH=1 pins the patch kernel: its configurations race each other alone, the GEMM family only sets the bar
+                // conv_u8_pw / _c3 / _rgb3x3 have to beat and stands for the patch kernel in the file
+                if (!patches.empty()) {
+                    const int w = plan_race(g, n.name, patches, "", 1.0f, true);
+                    if (w < 0) return -1;
+                    pk_best = atoi(patches[w].tag.c_str() + 1);
+                    for (auto& r : race) r.tag = patches[w].tag;
                 }
-            }
-            if (c3_ok) {
-                U8ConvArgs ac = a;
-                if (c3_ready(ac)) return -1;
-                float ms = 1e30f;
-                if (time_of([&]() { return launch_conv_u8_c3(ac, g->stream); }, &ms)) return -1;
-                if (getenv("TAMD_DEBUG")) fprintf(stderr, "[tamd] %s: %s %.2f us (best so far %.2f us)\n", n.name.c_str(), conv_u8_c3_kernel_name(ac), 1e3 * ms, 1e3 * best_ms);
-                if (ms < best_ms * 0.96f) { use_c3 = true; use_pw = false; pk_best = -1; best_ms = ms; }
-            }
-            if (rgb_ok) {
-                if (rgb_ready()) return -1;
-                float ms = 1e30f;
-                if (time_of([&]() { return launch_conv_u8_rgb3x3(rgb, g->stream); }, &ms)) return -1;
-                use_rgb = ms < best_ms * 0.96f;
-            }
-            hipEventDestroy(e0); hipEventDestroy(e1);
-            a.cfg = best_cfg;
-            plan_cache_put(ckey, use_rgb ? std::string("rgb") : use_c3 ? std::string("c3") : use_pw ? std::string("pw") : pk_best >= 0 ? "p" + std::to_string(pk_best) : "g" + std::to_string(best_cfg));
+            } else
+                race.insert(race.end(), patches.begin(), patches.end());
+            if (conv_u8_pw_applicable(a, p.kernel_h, p.kernel_w))
+                race.push_back({"pw", [&](hipStream_t s) { U8ConvArgs ar = a; return pw_ready(ar) ? hipErrorOutOfMemory : launch_conv_u8_pw(ar, s); },
+                                conv_u8_pw_kernel_name(a), unpinned});
+            if (c3_ok)
+                race.push_back({"c3", [&](hipStream_t s) { U8ConvArgs ar = a; return c3_ready(ar) ? hipErrorOutOfMemory : launch_conv_u8_c3(ar, s); },
+                                conv_u8_c3_kernel_name(a), unpinned});
+            if (rgb_ok)
+                race.push_back({"rgb", [&](hipStream_t s) { return rgb_ready() ? hipErrorOutOfMemory : launch_conv_u8_rgb3x3(rgb, s); },
+                                conv_u8_rgb3x3_kernel_name(rgb), unpinned});
+            const int w = plan_race(g, n.name, race, ckey, 0.96f, true);
+            if (w < 0) return -1;
+            const std::string& t = race[w].tag;
+            use_rgb = t == "rgb"; use_c3 = t == "c3"; use_pw = t == "pw";
+            if (t[0] == 'g') a.cfg = atoi(t.c_str() + 1);
+            if (t[0] == 'p' && t != "pw") pk_best = atoi(t.c_str() + 1);
         }
         if (rgb_ok && rgb_env && atoi(rgb_env) == 1) use_rgb = true;
         if (pw_env && atoi(pw_env) == 1 && conv_u8_pw_applicable(a, p.kernel_h, p.kernel_w)) use_pw = true;

@@ -1,10 +1,13 @@
 """TAMD_PLAN_CACHE (plan_cache.hip; used by graph_plan*.hip / graph_u8.hip): the first prerun of a model measures its candidates and writes what it chose,
 later preruns take the recorded choices without launching anything -- same kernels, same bytes, a shorter prerun; a line that
 names nothing known is ignored (the site is measured again)."""
+import os
+import re
+
 import numpy as np
 import pytest
 
-from tengine_amd import capi, models, tm2
+from tengine_amd import capi, models, plans, tm2
 
 pytestmark = pytest.mark.gpu
 
@@ -86,3 +89,39 @@ def test_autotune_switch_is_read_at_every_prerun(tmp_path, monkeypatch):
     for o in outs[1:]:
         for a, b in zip(outs[0], o):
             assert np.array_equal(a, b)
+
+
+SHIPPED = sorted(f[:-4] for f in os.listdir(plans.PLAN_DIR) if f.endswith(".txt"))
+
+
+@pytest.mark.parametrize("plan_name", SHIPPED)
+def test_shipped_plan_answers_every_race(plan_name, tmp_path, monkeypatch):
+    """A prerun of a shipped configuration the way tools/make_plans.py runs it (direct dispatch, one launch list) takes every choice
+    from the seeded plan: the file is byte-identical afterwards (nothing was timed, so nothing was recorded), and the outputs equal
+    those of the heuristic plan (TAMD_AUTOTUNE=0) -- every candidate of a race computes the same bytes."""
+    name, dtype, integer, batch = re.match(r"(.+)_(int8|uint8)(_int)?_b(\d+)$", plan_name).groups()
+    batch = int(batch)
+    cache = tmp_path / "plan.txt"
+    assert plans.seed(str(cache), name, dtype + (integer or ""), batch)
+    seeded = cache.read_bytes()
+    if integer:
+        monkeypatch.setenv("TAMD_U8_INT", "1")
+    g = models.build(name, dtype, batch, device_only=(name != "mobilenet_v1"))
+    x = models.synth_input(g, 3, tm2.DT_UINT8 if dtype == "uint8" else tm2.DT_INT8)
+
+    def run():
+        gr = capi.Graph(tm2.write_tm2(g), batch=batch, direct_dispatch=True, split_batch=1)
+        gr.set_input(x)
+        out = [o.copy() for o in gr.run()]
+        gr.close()
+        return out
+
+    monkeypatch.setenv("TAMD_PLAN_CACHE", str(cache))
+    planned = run()
+    assert cache.read_bytes() == seeded
+    monkeypatch.delenv("TAMD_PLAN_CACHE")
+    monkeypatch.setenv("TAMD_AUTOTUNE", "0")
+    heuristic = run()
+    assert len(planned) == len(heuristic)
+    for a, b in zip(planned, heuristic):
+        assert np.array_equal(a, b)
