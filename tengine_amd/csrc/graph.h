@@ -227,6 +227,10 @@ int plan_cached(const std::string& key, const std::vector<RaceCand>& cands);
 bool autotune_enabled();           // TAMD_AUTOTUNE=0: no site races, every one keeps its incumbent
 void nhwc_geom(HTensor& t);
 int count_consumers(const tamd_graph* g, int tensor);
+// the front and the tail that the NCHW planners (graph_u8.hip, graph_f32.hip) share: dense buffers of `esz` bytes per element for
+// inputs and tensors, views for Dropout / Flatten / Reshape and for channel-concat inputs that `in_place` allows; graph outputs
+int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place);
+int plan_nchw_outputs(tamd_graph* g, size_t esz);
 int priorbox_count(const tamd_priorbox_param& p);
 void priorbox_eval(const tamd_priorbox_param& p, int feat_h, int feat_w, int data_h, int data_w, std::vector<float>* out);
 void priorbox_quant_u8(const std::vector<float>& f, float scale, int zp, std::vector<uint8_t>* q);

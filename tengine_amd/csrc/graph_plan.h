@@ -14,16 +14,24 @@ int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, Rq
 bool exp_plain_kernels();
 std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps);
 
-// the arguments of the last depthwise 3x3 / implicit-GEMM convolution planned on this thread (dwpw.hip: depthwise -> pointwise in one
-// launch reads them back)
-extern thread_local DwArgs g_last_dw;
-extern thread_local bool g_last_dw_valid;
-extern thread_local ConvArgs g_last_gemm;
-extern thread_local bool g_last_gemm_valid;
+std::vector<int8_t> pack_dw3x3(const int8_t* wd, int cin, int cw);
+std::vector<int32_t> padded_bias(const int32_t* bd, int n, int padded);
 
-// graph_plan_pairs.hip
+// One planned launch, as plan_conv / plan_pool hand it out: the step, which form it took, and that form's kernel arguments for a
+// fuser that folds this launch and its neighbour into one.  The caller pushes either the fused step or the planned ones.
+struct Planned {
+    enum Kind { FIRST, DW3X3, DIRECT, GEMM, POOL } kind = DIRECT;   // first-layer MFMA conv, depthwise 3x3, generic direct, GEMM family, pooling
+    bool elt_tail = false;      // GEMM: an eltwise (+ReLU) tail is folded into the launch
+    Step step;
+    FirstArgs first{};          // the member of `kind` is set; DIRECT has none
+    DwArgs dw{};
+    ConvArgs gemm{};
+    PoolArgs pool{};
+};
+
+// graph_plan_pairs.hip.  The fusers: 1 = *fused is the one launch for both, 0 = not fused, -1 = error
 int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod);
-int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s0);
-int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, size_t s0);
+int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Planned& a, const Planned& b, Step* fused);
+int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& d, const Planned& c, Step* fused);
 
 }  // namespace tamd

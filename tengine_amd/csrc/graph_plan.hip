@@ -1,22 +1,16 @@
 // The int8 planner: device buffers (arena), requantisation folds, plan-time timing, the convolution / pooling planners and plan_i8()
 // itself -- node list -> launch list (NHWC int8).  The pair fusions (pointwise + depthwise, depthwise + pointwise) are in
-// graph_plan_pairs.hip.  Split out of graph.hip in round 6.
+// graph_plan_pairs.hip.
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
 
-#include <stdarg.h>
-#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
-#include <mutex>
 
 #include "epilogue.h"
 #include "graph_plan.h"
@@ -64,6 +58,75 @@ void nhwc_geom(HTensor& t)
     if (t.dims.size() == 4) { t.n = t.dims[0]; t.c = t.dims[1]; t.h = t.dims[2]; t.w = t.dims[3]; }
     else if (t.dims.size() == 2) { t.n = t.dims[0]; t.c = t.dims[1]; t.h = t.w = 1; }
     else { t.n = 1; t.c = (int)t.elems(); t.h = t.w = 1; }
+}
+
+// The NCHW planners' front: every non-constant tensor is dense NCHW bytes (read_tensor / IO copy them as they are), `esz` bytes per
+// element.  Allocation order: the graph inputs in their order, then every remaining tensor that owns a buffer in index order.
+// concat-by-offset: a node whose only consumer is a channel concat writes its channels straight into the concat
+// output, and the concat launch disappears, where in_place(producer, input, concat output) says that it may.
+int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place)
+{
+    for (auto& t : g->tensors) {
+        if (t.ttype == TAMD_TT_CONST) continue;
+        nhwc_geom(t);
+        t.nchw_raw = true;
+        t.cs = 0; t.c_off = 0;
+    }
+    std::vector<int> alias_of(g->tensors.size(), -1);
+    for (auto& n : g->nodes)
+        if (n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) alias_of[n.out[0]] = n.in[0];   // dense NCHW: views
+    for (auto& io : g->inputs) {
+        HTensor& t = g->tensors[io.tensor];
+        io.bytes = t.elems() * esz;
+        if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
+        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
+        t.dptr = io.stage;
+    }
+    std::vector<int> view_of(g->tensors.size(), -1), view_off(g->tensors.size(), 0);
+    for (auto& n : g->nodes) {
+        if (n.op != TAMD_OP_CONCAT) continue;
+        HTensor& y = g->tensors[n.out[0]];
+        const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
+        int off = 0;
+        for (int i : n.in) {
+            HTensor& xi = g->tensors[i];
+            bool ok = ax == 1 && xi.ttype == TAMD_TT_VAR && count_consumers(g, i) == 1 && alias_of[i] < 0 && view_of[i] < 0;
+            if (ok) {
+                ok = false;
+                for (auto& pn : g->nodes)
+                    if (!pn.out.empty() && pn.out[0] == i) ok = in_place(pn, xi, y);
+            }
+            if (ok) { view_of[i] = n.out[0]; view_off[i] = off; }
+            off += xi.c;
+        }
+    }
+    for (size_t i = 0; i < g->tensors.size(); i++) {
+        HTensor& t = g->tensors[i];
+        if (t.ttype == TAMD_TT_CONST || t.dptr || alias_of[i] >= 0 || view_of[i] >= 0) continue;
+        if (dev_alloc(g, &t.dptr, t.elems() * esz, true)) return -1;
+    }
+    for (size_t i = 0; i < g->tensors.size(); i++)
+        if (view_of[i] >= 0) {
+            HTensor& t = g->tensors[i];
+            HTensor& o = g->tensors[view_of[i]];
+            if (!o.dptr) { set_error("concat of concat views is not supported"); return -1; }
+            t.dptr = o.dptr; t.is_view = true; t.c_off = view_off[i]; t.cs = o.c;      // cs: channels of the enclosing buffer
+        }
+    for (int pass = 0; pass < 4; pass++)
+        for (size_t i = 0; i < g->tensors.size(); i++)
+            if (alias_of[i] >= 0) g->tensors[i].dptr = g->tensors[alias_of[i]].dptr;
+    return 0;
+}
+
+int plan_nchw_outputs(tamd_graph* g, size_t esz)
+{
+    for (auto& io : g->outputs) {
+        HTensor& t = g->tensors[io.tensor];
+        io.bytes = t.elems() * esz;
+        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
+        io.stage = t.dptr;
+    }
+    return 0;
 }
 
 int count_consumers(const tamd_graph* g, int tensor)
@@ -182,18 +245,26 @@ struct FusedElt {            // an eltwise (+ReLU) node folded into the epilogue
     bool conv_is_first, relu;
 };
 
-// the arguments of the last first-layer convolution / pooling step planned on this thread: plan() reads them back when it turns
-// the pair into ONE launch (conv_first_pool.hip)
-static thread_local FirstArgs g_last_first;
-static thread_local bool g_last_first_valid = false;
-static thread_local PoolArgs g_last_pool;
-// ... of the last depthwise 3x3 / implicit-GEMM convolution planned on this thread (dwpw.hip: depthwise -> pointwise in one launch)
-thread_local DwArgs g_last_dw;
-thread_local bool g_last_dw_valid = false;
-thread_local ConvArgs g_last_gemm;
-thread_local bool g_last_gemm_valid = false;
+// depthwise 3x3 weights as [3 rows][cw] dwords {w[r][0], w[r][1], w[r][2], 0}: one v_dot4 operand per (row, channel)
+std::vector<int8_t> pack_dw3x3(const int8_t* wd, int cin, int cw)
+{
+    std::vector<int8_t> wp((size_t)3 * cw * 4, 0);
+    for (int c = 0; c < cin; c++)
+        for (int r = 0; r < 3; r++)
+            for (int kx = 0; kx < 3; kx++) wp[((size_t)r * cw + c) * 4 + kx] = wd[(size_t)c * 9 + r * 3 + kx];
+    return wp;
+}
 
-static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = nullptr)
+// a node's int32 bias, zeros where it has none, in a vector of `padded` entries
+std::vector<int32_t> padded_bias(const int32_t* bd, int n, int padded)
+{
+    std::vector<int32_t> bp(padded, 0);
+    for (int c = 0; c < n; c++) bp[c] = bd ? bd[c] : 0;
+    return bp;
+}
+
+// Plans one convolution / FC node as ONE launch and hands it out in *out; nothing is pushed onto g->steps here.
+static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& w = g->tensors[n.in[1]];
@@ -226,8 +297,9 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
     const double macs = (double)y.n * y.h * y.w * cout * cin_g * KH * KW;
     const double abytes = (double)x.n * x.h * x.w * cin + (double)y.n * y.h * y.w * cout + (double)cout * cin_g * KH * KW + 4.0 * cout;
 
-    Step st;
+    Step& st = out->step;
     st.node = n.name; st.macs = macs; st.bytes = abytes;
+    out->elt_tail = fz != nullptr;
     const bool is_dw = (group > 1 && group == cin && cout == cin);
     if (x.nchw_raw && group == 1 && cin <= 4 && cin * KH * KW <= 224 && cout <= 128
         && p.dilation_h * (KH - 1) < 256 && p.dilation_w * (KW - 1) < 256) {
@@ -241,8 +313,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
             for (int r = 0; r < cin * KH; r++)                              // kx padded to kwp: a patch row is kwp consecutive bytes
                 memcpy(&wp[(size_t)co * kp + (size_t)r * kwp], wd + (size_t)co * kreal + (size_t)r * KW, KW);
         }
-        std::vector<int32_t> bp(cpad, 0);
-        for (int c = 0; c < cout; c++) bp[c] = bd ? bd[c] : 0;
+        const std::vector<int32_t> bp = padded_bias(bd, cout, cpad);
         FirstArgs a{};
         int8_t* dw_; int32_t* db_;
         if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cpad, &a.wscale, &a.rq)) return -1;
@@ -253,19 +324,14 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
         a.DH = p.dilation_h; a.DW = p.dilation_w; a.kp = kp; a.kwp = kwp;
         st.kernel = "conv_first_i8";
         st.fn = [a](hipStream_t s) { return launch_conv_first(a, s); };
-        g_last_first = a; g_last_first_valid = true;
+        out->kind = Planned::FIRST; out->first = a;
     } else if (x.nchw_raw || group != 1) {
         if (!x.nchw_raw && is_dw && KH == 3 && KW == 3 && p.dilation_h == 1 && p.dilation_w == 1 && p.stride_h == p.stride_w
             && (p.stride_h == 1 || p.stride_h == 2)) {
             // ---- depthwise 3x3 ----
             const int cw = rup(cin, 16);
-            // [3 rows][cw] dwords {w[r][0], w[r][1], w[r][2], 0}: one v_dot4 operand per (row, channel)
-            std::vector<int8_t> wp((size_t)3 * cw * 4, 0);
-            for (int c = 0; c < cin; c++)
-                for (int r = 0; r < 3; r++)
-                    for (int kx = 0; kx < 3; kx++) wp[((size_t)r * cw + c) * 4 + kx] = wd[(size_t)c * 9 + r * 3 + kx];
-            std::vector<int32_t> bp(cw, 0);
-            for (int c = 0; c < cin; c++) bp[c] = bd ? bd[c] : 0;
+            const std::vector<int8_t> wp = pack_dw3x3(wd, cin, cw);
+            const std::vector<int32_t> bp = padded_bias(bd, cin, cw);
             DwArgs a{};
             int8_t* dw_; int32_t* db_;
             if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cw, &a.wscale, &a.rq)) return -1;
@@ -275,7 +341,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
             a.ldc = y.cs; a.c_off = y.c_off; a.S = p.stride_h; a.PH = p.pad_h0; a.PW = p.pad_w0;
             st.kernel = dwconv3x3_kernel_name(a);
             st.fn = [a](hipStream_t s) { return launch_dwconv3x3(a, s); };
-            g_last_dw = a; g_last_dw_valid = true;
+            out->kind = Planned::DW3X3; out->dw = a;
         } else {
             // ---- generic direct (first layer from NCHW, grouped, non-3x3 depthwise) ----
             std::vector<int8_t> wv(wd, wd + w.elems());
@@ -291,6 +357,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
             a.DH = p.dilation_h; a.DW = p.dilation_w; a.group = group;
             st.kernel = "conv_direct_i8";
             st.fn = [a](hipStream_t s) { return launch_conv_direct(a, s); };
+            out->kind = Planned::DIRECT;
         }
     } else {
         // ---- implicit GEMM on MFMA ----
@@ -305,8 +372,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
                 for (int ky = 0; ky < KH; ky++)
                     for (int kx = 0; kx < KW; kx++)
                         wp[(size_t)co * kpad + (size_t)(ky * KW + kx) * ckp + ci] = wd[(((size_t)co * cin + ci) * KH + ky) * KW + kx];
-        std::vector<int32_t> bp(cout_pad, 0);
-        for (int c = 0; c < cout; c++) bp[c] = bd ? bd[c] : 0;
+        const std::vector<int32_t> bp = padded_bias(bd, cout, cout_pad);
         ConvArgs a{};
         int8_t* dw_; int32_t* db_;
         if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cout_pad, &a.wscale, &a.rq)) return -1;
@@ -321,7 +387,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
         a.mg_ow = ((1ull << 40) + (unsigned)y.w - 1) / (unsigned)y.w;
         a.M = y.n * y.h * y.w;
         a.cfg = -1;
-        g_last_gemm = a; g_last_gemm_valid = !fz;
+        out->kind = Planned::GEMM; out->gemm = a;       // (as it is without the eltwise tail: what a fuser reads)
         if (fz) {      // conv -> eltwise (-> relu) in one launch: the conv's own int8 rounding is kept, see epilogue.h
             HTensor& r = g->tensors[fz->res_tensor];
             HTensor& o = g->tensors[fz->out_tensor];
@@ -390,8 +456,7 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
             const int steps = pwdw_steps((ckp + 63) / 64), nsteps = rup((ckp + 63) / 64, steps);
             std::vector<int8_t> w2(wd, wd + (size_t)cout * cin);
             const std::vector<int8_t> wf = pack_pw_panel(w2.data(), cout, cin, nsteps);
-            std::vector<int32_t> b2(cws, 0);
-            for (int c = 0; c < cout; c++) b2[c] = bd ? bd[c] : 0;
+            const std::vector<int32_t> b2 = padded_bias(bd, cout, cws);
             int8_t* d0; int32_t* d1;
             if (upload(g, wf, &d0) || upload(g, b2, &d1) || upload_rq(g, rqf, cws, &v.wscale, &v.rq)) return -1;
             v.wf = d0; v.bias = d1;
@@ -447,12 +512,11 @@ static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz = n
     if (!fz) {                           // reads its input, writes its output (constants aside), one launch: all a convolution / FC step touches
         st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
     }
-    g->steps.push_back(st);
     return 0;
 }
 
 
-static int plan_pool(tamd_graph* g, HNode& n)
+static int plan_pool(tamd_graph* g, HNode& n, Planned* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
@@ -463,116 +527,127 @@ static int plan_pool(tamd_graph* g, HNode& n)
     a.KH = pg.kh; a.KW = pg.kw; a.SH = pg.sh; a.SW = pg.sw; a.PH = pg.ph0; a.PW = pg.pw0;
     a.method = n.p.pool.pool_method; a.caffe_flavor = n.p.pool.caffe_flavor;
     a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-    const PoolArgs av = a;
-    g_last_pool = a;
-    Step st; st.node = n.name; st.kernel = "pool_i8";
+    out->kind = Planned::POOL; out->pool = a;
+    Step& st = out->step;
+    st.node = n.name; st.kernel = "pool_i8";
     st.bytes = (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c;
-    st.fn = [av](hipStream_t s) { return launch_pool(av, s); };
-    g->steps.push_back(st);
+    st.fn = [a](hipStream_t s) { return launch_pool(a, s); };
     return 0;
 }
 
 
-int plan_i8(tamd_graph* g)
+// What the passes of plan_i8 hand on to each other, per tensor (layout) and per node (fusion).
+struct I8Layout {
+    // view_of / view_off: a concat input that lives in its concat's buffer at a channel offset; alias_of: an identity op's output
+    // (Dropout, Flatten, Reshape of a dense tensor); dense / perm_src / flat_concat: see plan_dense
+    std::vector<int> view_of, view_off, alias_of, perm_src;
+    std::vector<char> dense, flat_concat;
+    // fused[node]: planned inside another node's launch (skipped at its own position); has_fuse / fuse_at[node]: the convolution
+    // that takes an eltwise (+ReLU) into its epilogue
+    std::vector<char> fused, has_fuse;
+    std::vector<FusedElt> fuse_at;
+    I8Layout(size_t nt, size_t nn)
+        : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn) {}
+};
+
+// ---- DENSE tensors (the SSD head plumbing of an int8 graph).  The convolution stack lives in NHWC buffers
+// with padded channels; what Permute(0,2,3,1) / PriorBox produce, and everything that is only a re-reading of it (Flatten, Reshape,
+// Concat on any axis, Softmax on any axis), lives in the reference's own dense element order (HTensor::nchw_raw, cs = 0): those ops
+// are byte copies / views there (permute_ref.c:305-343, flatten_ref.c:74-80, reshape_ref.c:76-90), and a graph output needs no
+// layout pass.  L.perm_src[t] >= 0: t is NHWC tensor L.perm_src[t] seen through Permute(0,2,3,1) (+ views) -- a Concat reads the NHWC
+// buffer itself (flatcat_i8, kind 1) and the permuted copy is never written unless something else reads it too.
+static int plan_dense(tamd_graph* g, I8Layout& L)
 {
-    // ---- 1. geometry + device buffers for every non-const tensor -------------------------------
-    for (auto& t : g->tensors) if (t.ttype != TAMD_TT_CONST) nhwc_geom(t);
-    // concat outputs own a buffer; their inputs become views when layouts allow (concat-by-offset:
-    // concat/concat_kernel_ref_int8.c with in_scale == out_scale is a pure copy)
-    // An input that cannot be written in place (its scale differs -> the reference rescales, concat_kernel_ref_int8.c:70-80;
-    // channel count / offset not a multiple of 16; produced or also consumed by a kernel that does not address channel
-    // slices; a graph input) keeps its own buffer and is copied by concat_copy_i8 at the concat's position.
-    std::vector<int> view_of(g->tensors.size(), -1), view_off(g->tensors.size(), 0);
-    std::vector<int> alias_of(g->tensors.size(), -1);
-    // ---- DENSE tensors (round 6: the SSD head plumbing of an int8 graph).  The convolution stack lives in NHWC buffers
-    // with padded channels; what Permute(0,2,3,1) / PriorBox produce, and everything that is only a re-reading of it (Flatten, Reshape,
-    // Concat on any axis, Softmax on any axis), lives in the reference's own dense element order (HTensor::nchw_raw, cs = 0): those ops
-    // are byte copies / views there (permute_ref.c:305-343, flatten_ref.c:74-80, reshape_ref.c:76-90), and a graph output needs no
-    // layout pass.  perm_src[t] >= 0: t is NHWC tensor perm_src[t] seen through Permute(0,2,3,1) (+ views) -- a Concat reads the NHWC
-    // buffer itself (flatcat_i8, kind 1) and the permuted copy is never written unless something else reads it too.
     const size_t NT = g->tensors.size();
-    std::vector<char> dense(NT, 0), flat_concat(g->nodes.size(), 0), need_buf(NT, 0);
-    std::vector<int> perm_src(NT, -1);
-    {
-        auto root = [&](int t) { for (int hop = 0; hop < 16 && alias_of[t] >= 0; hop++) t = alias_of[t]; return t; };
-        for (size_t ni = 0; ni < g->nodes.size(); ni++) {
-            HNode& n = g->nodes[ni];
-            if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.in.empty() || n.out.empty()) continue;
-            HTensor& x = g->tensors[n.in[0]];
-            const int yo = n.out[0];
-            switch (n.op) {
-            case TAMD_OP_PERMUTE: {
-                const int* o = n.p.perm.order;
-                if (x.dims.size() != 4 || dense[n.in[0]] || !(o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1)) {
-                    set_error("permute %s: only order (0, 2, 3, 1) of a 4-D convolution-stack tensor runs on the device", n.name.c_str());
+    std::vector<char> need_buf(NT, 0);
+    auto root = [&](int t) { for (int hop = 0; hop < 16 && L.alias_of[t] >= 0; hop++) t = L.alias_of[t]; return t; };
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        HNode& n = g->nodes[ni];
+        if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.in.empty() || n.out.empty()) continue;
+        HTensor& x = g->tensors[n.in[0]];
+        const int yo = n.out[0];
+        switch (n.op) {
+        case TAMD_OP_PERMUTE: {
+            const int* o = n.p.perm.order;
+            if (x.dims.size() != 4 || L.dense[n.in[0]] || !(o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1)) {
+                set_error("permute %s: only order (0, 2, 3, 1) of a 4-D convolution-stack tensor runs on the device", n.name.c_str());
+                return -1;
+            }
+            L.dense[yo] = 1; L.perm_src[yo] = n.in[0];
+            break;
+        }
+        case TAMD_OP_PRIORBOX: L.dense[yo] = 1; break;
+        case TAMD_OP_RESHAPE: L.dense[yo] = 1; if (L.dense[n.in[0]]) { L.alias_of[yo] = n.in[0]; L.perm_src[yo] = L.perm_src[n.in[0]]; } break;
+        case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
+            if (L.dense[n.in[0]]) { L.dense[yo] = 1; L.alias_of[yo] = n.in[0]; L.perm_src[yo] = L.perm_src[n.in[0]]; }
+            else {
+                // Flatten of an H x W map: the [N, C*H*W] result is the SAME NCHW element order; on the device it stays the NHWC
+                // buffer and keeps the 4-D geometry, so a following FC (== conv whose kernel covers the map), the NCHW output
+                // conversion and a flat Concat (kind 2) all see (c, h, w).  Set HERE, in node order: the Concat case below looks
+                // at the geometry of its inputs (a 2-D tensor that is a flattened MAP must not take the channel-concat path --
+                // it did until round 6 and wrote N*H*W rows into an N-row output)
+                L.alias_of[yo] = n.in[0];
+                HTensor& yy = g->tensors[yo];
+                yy.n = x.n; yy.c = x.c; yy.h = x.h; yy.w = x.w;
+            }
+            break;
+        case TAMD_OP_SOFTMAX: if (L.dense[n.in[0]]) L.dense[yo] = 1; break;
+        case TAMD_OP_CONCAT: {
+            HTensor& y = g->tensors[yo];
+            const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
+            bool any_dense = false, any_map = false;
+            for (int i : n.in) { any_dense |= L.dense[i] != 0; any_map |= g->tensors[i].h * g->tensors[i].w > 1; }
+            if (any_dense || ax != 1 || (y.dims.size() != 4 && any_map)) {
+                L.flat_concat[ni] = 1; L.dense[yo] = 1;
+            }
+            break;
+        }
+        default:
+            for (int i : n.in)
+                if (g->tensors[i].ttype != TAMD_TT_CONST && L.dense[i]) {
+                    set_error("%s reads %s, a tensor in dense (permuted / flattened) order: only Flatten, Reshape, Concat and Softmax do on the device", n.name.c_str(), g->tensors[i].name.c_str());
                     return -1;
                 }
-                dense[yo] = 1; perm_src[yo] = n.in[0];
-                break;
-            }
-            case TAMD_OP_PRIORBOX: dense[yo] = 1; break;
-            case TAMD_OP_RESHAPE: dense[yo] = 1; if (dense[n.in[0]]) { alias_of[yo] = n.in[0]; perm_src[yo] = perm_src[n.in[0]]; } break;
-            case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
-                if (dense[n.in[0]]) { dense[yo] = 1; alias_of[yo] = n.in[0]; perm_src[yo] = perm_src[n.in[0]]; }
-                else {
-                    // Flatten of an H x W map: the [N, C*H*W] result is the SAME NCHW element order; on the device it stays the NHWC
-                    // buffer and keeps the 4-D geometry, so a following FC (== conv whose kernel covers the map), the NCHW output
-                    // conversion and a flat Concat (kind 2) all see (c, h, w).  Set HERE, in node order: the Concat case below looks
-                    // at the geometry of its inputs (a 2-D tensor that is a flattened MAP must not take the channel-concat path --
-                    // it did until round 6 and wrote N*H*W rows into an N-row output)
-                    alias_of[yo] = n.in[0];
-                    HTensor& yy = g->tensors[yo];
-                    yy.n = x.n; yy.c = x.c; yy.h = x.h; yy.w = x.w;
-                }
-                break;
-            case TAMD_OP_SOFTMAX: if (dense[n.in[0]]) dense[yo] = 1; break;
-            case TAMD_OP_CONCAT: {
-                HTensor& y = g->tensors[yo];
-                const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
-                bool any_dense = false, any_map = false;
-                for (int i : n.in) { any_dense |= dense[i] != 0; any_map |= g->tensors[i].h * g->tensors[i].w > 1; }
-                if (any_dense || ax != 1 || (y.dims.size() != 4 && any_map)) {
-                    flat_concat[ni] = 1; dense[yo] = 1;
-                }
-                break;
-            }
-            default:
-                for (int i : n.in)
-                    if (g->tensors[i].ttype != TAMD_TT_CONST && dense[i]) {
-                        set_error("%s reads %s, a tensor in dense (permuted / flattened) order: only Flatten, Reshape, Concat and Softmax do on the device", n.name.c_str(), g->tensors[i].name.c_str());
-                        return -1;
-                    }
-            }
-        }
-        // who needs the bytes of a dense tensor in memory: everything but the flat Concat of a lazily permuted tensor (and its views)
-        for (size_t ni = 0; ni < g->nodes.size(); ni++) {
-            const HNode& n = g->nodes[ni];
-            for (int i : n.in) {
-                if (g->tensors[i].ttype == TAMD_TT_CONST || !dense[i]) continue;
-                const bool is_alias_op = !n.out.empty() && alias_of[n.out[0]] == i;
-                if (is_alias_op) continue;
-                if (!(flat_concat[ni] && perm_src[i] >= 0)) need_buf[root(i)] = 1;
-            }
-        }
-        for (auto& io : g->outputs) if (dense[io.tensor]) need_buf[root(io.tensor)] = 1;
-        for (size_t t = 0; t < NT; t++) {
-            if (!dense[t]) continue;
-            if (need_buf[root((int)t)]) perm_src[t] = -1;              // materialised: its readers take the dense bytes
-            HTensor& d = g->tensors[t];
-            d.nchw_raw = true; d.cs = 0; d.c_off = 0;
-        }
-        for (size_t t = 0; t < NT; t++) {
-            HTensor& d = g->tensors[t];
-            if (!dense[t] || alias_of[t] >= 0) continue;
-            if (d.dtype != TAMD_DT_INT8) { set_error("tensor %s: dtype %d not supported on the device yet", d.name.c_str(), d.dtype); return -1; }
-            if (perm_src[t] >= 0) continue;                             // never written: read through its NHWC source
-            if (dev_alloc(g, &d.dptr, d.elems(), true)) return -1;
         }
     }
+    // who needs the bytes of a dense tensor in memory: everything but the flat Concat of a lazily permuted tensor (and its views)
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        const HNode& n = g->nodes[ni];
+        for (int i : n.in) {
+            if (g->tensors[i].ttype == TAMD_TT_CONST || !L.dense[i]) continue;
+            const bool is_alias_op = !n.out.empty() && L.alias_of[n.out[0]] == i;
+            if (is_alias_op) continue;
+            if (!(L.flat_concat[ni] && L.perm_src[i] >= 0)) need_buf[root(i)] = 1;
+        }
+    }
+    for (auto& io : g->outputs) if (L.dense[io.tensor]) need_buf[root(io.tensor)] = 1;
+    for (size_t t = 0; t < NT; t++) {
+        if (!L.dense[t]) continue;
+        if (need_buf[root((int)t)]) L.perm_src[t] = -1;              // materialised: its readers take the dense bytes
+        HTensor& d = g->tensors[t];
+        d.nchw_raw = true; d.cs = 0; d.c_off = 0;
+    }
+    for (size_t t = 0; t < NT; t++) {
+        HTensor& d = g->tensors[t];
+        if (!L.dense[t] || L.alias_of[t] >= 0) continue;
+        if (d.dtype != TAMD_DT_INT8) { set_error("tensor %s: dtype %d not supported on the device yet", d.name.c_str(), d.dtype); return -1; }
+        if (L.perm_src[t] >= 0) continue;                             // never written: read through its NHWC source
+        if (dev_alloc(g, &d.dptr, d.elems(), true)) return -1;
+    }
+    return 0;
+}
+
+// concat outputs own a buffer; their inputs become views when layouts allow (concat-by-offset:
+// concat/concat_kernel_ref_int8.c with in_scale == out_scale is a pure copy)
+// An input that cannot be written in place (its scale differs -> the reference rescales, concat_kernel_ref_int8.c:70-80;
+// channel count / offset not a multiple of 16; produced or also consumed by a kernel that does not address channel
+// slices; a graph input) keeps its own buffer and is copied by concat_copy_i8 at the concat's position.
+static int plan_concat_views(tamd_graph* g, I8Layout& L)
+{
     auto producer_op = [&](int t) { for (auto& n : g->nodes) if (!n.out.empty() && n.out[0] == t) return n.op; return -1; };
     auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL; };
     for (auto& n : g->nodes) {
-        if (n.op != TAMD_OP_CONCAT || flat_concat[&n - g->nodes.data()]) continue;
+        if (n.op != TAMD_OP_CONCAT || L.flat_concat[&n - g->nodes.data()]) continue;
         HTensor& y = g->tensors[n.out[0]];
         int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
         if (ax != 1 || y.dims.size() < 2) { set_error("concat %s: only the channel axis is supported on the device", n.name.c_str()); return -1; }
@@ -582,19 +657,23 @@ int plan_i8(tamd_graph* g)
             HTensor& x = g->tensors[i];
             if (x.dtype != y.dtype || x.scales.empty()) { set_error("concat %s: input %s: dtype / quant params", n.name.c_str(), x.name.c_str()); return -1; }
             bool ok = (x.c % 16 == 0) && (off % 16 == 0) && (x.scales[0] == y.scales[0] || n.in.size() == 1) && x.ttype == TAMD_TT_VAR
-                      && view_of[i] < 0 && slice_capable(producer_op(i));
+                      && L.view_of[i] < 0 && slice_capable(producer_op(i));
             for (auto& c : g->nodes)            // every other reader must cope with a channel slice too
                 for (int ci : c.in)
                     if (ci == i && &c != &n && !(slice_capable(c.op) || c.op == TAMD_OP_CONCAT)) ok = false;
             int readers = 0;
             for (int ci : n.in) readers += (ci == i);
             if (readers > 1) ok = false;        // the same tensor twice: one copy per position
-            if (ok) { view_of[i] = n.out[0]; view_off[i] = off; }
+            if (ok) { L.view_of[i] = n.out[0]; L.view_off[i] = off; }
             off += x.c;
         }
     }
-    // (identity ops -- Dropout, Flatten -- alias their input: alias_of, set by the dense analysis above)
-    // graph inputs: NCHW staging; first conv with <=4 channels reads NCHW directly
+    return 0;
+}
+
+// graph inputs: NCHW staging; first conv with <=4 channels reads NCHW directly
+static int plan_input_staging(tamd_graph* g)
+{
     for (auto& io : g->inputs) {
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esize(t.dtype);
@@ -608,11 +687,25 @@ int plan_i8(tamd_graph* g)
         }
         if (direct) { t.nchw_raw = true; t.dptr = io.stage; t.cs = 0; }
     }
+    return 0;
+}
+
+// ---- activation buffers.  Tensors whose lifetimes cannot overlap share device memory (tamd_options.keep_tensors = 0, the
+// default): a pass then touches a fraction of the bytes -- ResNet-50 at batch 32 owns 345 MB of activations one by one, more
+// than the 256 MB last-level cache, but never has more than ~65 MB of them alive.  Lifetime of a buffer, in node positions
+// (the launch list follows the node order, except that a fused tail runs at ITS PRODUCER's position and a fused
+// eltwise / ReLU at the position of the convolution that absorbs it): written from `birth` = the earliest producer within two
+// hops above the node that produces it (covers both exceptions, conservatively), read until `death` = the last node that
+// names it (or a view / alias of it) as an input.  A launch reads and writes in one go, so buffers with birth == death of
+// another never share.  Graph inputs / outputs and tensors with padding channels (cs != c: their padding bytes are zero from
+// the allocation on and stay zero) keep their own buffers.
+static int plan_buffers(tamd_graph* g, I8Layout& L)
+{
     std::vector<size_t> own;                     // tensors that own a buffer (not a constant, a raw input, a view or an alias)
     for (size_t i = 0; i < g->tensors.size(); i++) {
         HTensor& t = g->tensors[i];
         if (t.ttype == TAMD_TT_CONST || t.nchw_raw) continue;
-        if (view_of[i] >= 0 || alias_of[i] >= 0) continue;
+        if (L.view_of[i] >= 0 || L.alias_of[i] >= 0) continue;
         if (t.dtype != TAMD_DT_INT8) { set_error("tensor %s: dtype %d not supported on the device yet", t.name.c_str(), t.dtype); return -1; }
         t.cs = rup(t.c, 16);
         // a 1x1-map graph output written by conv/fc/pool (dword stores) keeps its channels dense, so the
@@ -627,84 +720,78 @@ int plan_i8(tamd_graph* g)
         }
         own.push_back(i);
     }
-    // ---- activation buffers.  Tensors whose lifetimes cannot overlap share device memory (tamd_options.keep_tensors = 0, the
-    // default): a pass then touches a fraction of the bytes -- ResNet-50 at batch 32 owns 345 MB of activations one by one, more
-    // than the 256 MB last-level cache, but never has more than ~65 MB of them alive.  Lifetime of a buffer, in node positions
-    // (the launch list follows the node order, except that a fused tail runs at ITS PRODUCER's position and a fused
-    // eltwise / ReLU at the position of the convolution that absorbs it): written from `birth` = the earliest producer within two
-    // hops above the node that produces it (covers both exceptions, conservatively), read until `death` = the last node that
-    // names it (or a view / alias of it) as an input.  A launch reads and writes in one go, so buffers with birth == death of
-    // another never share.  Graph inputs / outputs and tensors with padding channels (cs != c: their padding bytes are zero from
-    // the allocation on and stay zero) keep their own buffers.
     g->pooled.assign(g->tensors.size(), 0);
-    {
-        const char* pe = getenv("TAMD_POOL");
-        const bool pool = pe ? atoi(pe) != 0 : !g->opt.keep_tensors;
-        const int NN = (int)g->nodes.size();
-        auto root_of = [&](int t) { for (int hop = 0; hop < 8; hop++) { if (view_of[t] >= 0) t = view_of[t]; else if (alias_of[t] >= 0) t = alias_of[t]; else break; } return t; };
-        std::vector<int> prod(g->tensors.size(), -1), birth(g->tensors.size(), NN), death(g->tensors.size(), -1);
-        for (int ni = 0; ni < NN; ni++)
-            for (int o : g->nodes[ni].out) prod[o] = ni;
-        auto up = [&](int ni) { int e = ni; for (int i : g->nodes[ni].in) if (g->tensors[i].ttype != TAMD_TT_CONST && prod[i] >= 0) e = std::min(e, prod[i]); return e; };
-        for (int ni = 0; ni < NN; ni++) {
-            const HNode& n = g->nodes[ni];
-            if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST) continue;
-            int e = ni;
-            for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST && prod[i] >= 0) e = std::min(e, up(prod[i]));
-            for (int o : n.out) { const int r = root_of(o); birth[r] = std::min(birth[r], e); death[r] = std::max(death[r], ni); }
-            for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST) { const int r = root_of(i); death[r] = std::max(death[r], ni); }
-        }
-        // an NHWC tensor that a flat Concat reads THROUGH its Permute (perm_src) is read at the Concat's position, not at the Permute's
-        for (int ni = 0; ni < NN; ni++)
-            if (flat_concat[ni])
-                for (int i : g->nodes[ni].in)
-                    if (perm_src[i] >= 0) { const int r = root_of(perm_src[i]); death[r] = std::max(death[r], ni); }
-        std::vector<char> pinned(g->tensors.size(), 0);
-        for (auto& io : g->inputs) pinned[root_of(io.tensor)] = 1;
-        for (auto& io : g->outputs) pinned[root_of(io.tensor)] = 1;
-        struct Blk { size_t t, bytes, off; int b, d; };
-        std::vector<Blk> blks;
-        auto bytes_of = [&](const HTensor& t) { return ((size_t)t.n * t.h * t.w * t.cs + 1024 + 255) & ~(size_t)255; };
-        for (size_t i : own) {
-            HTensor& t = g->tensors[i];
-            g->unpooled_bytes += bytes_of(t);
-            if (pool && !pinned[i] && t.cs == t.c && death[i] >= 0 && birth[i] <= death[i]) blks.push_back({i, bytes_of(t), 0, birth[i], death[i]});
-            else if (dev_alloc(g, &t.dptr, (size_t)t.n * t.h * t.w * t.cs, true)) return -1;
-        }
-        // greedy by size: the largest buffers first, each at the lowest offset that is free over its whole lifetime
-        std::sort(blks.begin(), blks.end(), [](const Blk& a, const Blk& b) { return a.bytes != b.bytes ? a.bytes > b.bytes : a.t < b.t; });
-        size_t total = 0;
-        for (size_t k = 0; k < blks.size(); k++) {
-            std::vector<std::pair<size_t, size_t>> busy;           // [offset, end) of placed buffers alive at the same time
-            for (size_t j = 0; j < k; j++)
-                if (blks[j].b <= blks[k].d && blks[k].b <= blks[j].d) busy.push_back({blks[j].off, blks[j].off + blks[j].bytes});
-            std::sort(busy.begin(), busy.end());
-            size_t off = 0;
-            for (auto& r : busy) { if (off + blks[k].bytes <= r.first) break; off = std::max(off, r.second); }
-            blks[k].off = off;
-            total = std::max(total, off + blks[k].bytes);
-        }
-        if (!blks.empty()) {
-            void* base = nullptr;
-            if (dev_alloc(g, &base, total, true)) return -1;
-            for (const Blk& b : blks) { g->tensors[b.t].dptr = (char*)base + b.off; g->pooled[b.t] = 1; }
-            g->pool_bytes = total;
-        }
-        for (size_t i = 0; i < g->tensors.size(); i++)                 // views / aliases of a shared buffer are shared too
-            if (g->tensors[i].ttype != TAMD_TT_CONST && (view_of[i] >= 0 || alias_of[i] >= 0) && g->pooled[root_of((int)i)]) g->pooled[i] = 1;
-        if (getenv("TAMD_DEBUG"))
-            fprintf(stderr, "[tamd] activations: %.1f MB one buffer per tensor, %zu of %zu buffers share %.1f MB\n", g->unpooled_bytes / 1048576.0, blks.size(),
-                    own.size(), g->pool_bytes / 1048576.0);
+    const char* pe = getenv("TAMD_POOL");
+    const bool pool = pe ? atoi(pe) != 0 : !g->opt.keep_tensors;
+    const int NN = (int)g->nodes.size();
+    auto root_of = [&](int t) { for (int hop = 0; hop < 8; hop++) { if (L.view_of[t] >= 0) t = L.view_of[t]; else if (L.alias_of[t] >= 0) t = L.alias_of[t]; else break; } return t; };
+    std::vector<int> prod(g->tensors.size(), -1), birth(g->tensors.size(), NN), death(g->tensors.size(), -1);
+    for (int ni = 0; ni < NN; ni++)
+        for (int o : g->nodes[ni].out) prod[o] = ni;
+    auto up = [&](int ni) { int e = ni; for (int i : g->nodes[ni].in) if (g->tensors[i].ttype != TAMD_TT_CONST && prod[i] >= 0) e = std::min(e, prod[i]); return e; };
+    for (int ni = 0; ni < NN; ni++) {
+        const HNode& n = g->nodes[ni];
+        if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST) continue;
+        int e = ni;
+        for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST && prod[i] >= 0) e = std::min(e, up(prod[i]));
+        for (int o : n.out) { const int r = root_of(o); birth[r] = std::min(birth[r], e); death[r] = std::max(death[r], ni); }
+        for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST) { const int r = root_of(i); death[r] = std::max(death[r], ni); }
     }
-    // resolve views / aliases (nodes are in topological order; resolve chains iteratively)
+    // an NHWC tensor that a flat Concat reads THROUGH its Permute (perm_src) is read at the Concat's position, not at the Permute's
+    for (int ni = 0; ni < NN; ni++)
+        if (L.flat_concat[ni])
+            for (int i : g->nodes[ni].in)
+                if (L.perm_src[i] >= 0) { const int r = root_of(L.perm_src[i]); death[r] = std::max(death[r], ni); }
+    std::vector<char> pinned(g->tensors.size(), 0);
+    for (auto& io : g->inputs) pinned[root_of(io.tensor)] = 1;
+    for (auto& io : g->outputs) pinned[root_of(io.tensor)] = 1;
+    struct Blk { size_t t, bytes, off; int b, d; };
+    std::vector<Blk> blks;
+    auto bytes_of = [&](const HTensor& t) { return ((size_t)t.n * t.h * t.w * t.cs + 1024 + 255) & ~(size_t)255; };
+    for (size_t i : own) {
+        HTensor& t = g->tensors[i];
+        g->unpooled_bytes += bytes_of(t);
+        if (pool && !pinned[i] && t.cs == t.c && death[i] >= 0 && birth[i] <= death[i]) blks.push_back({i, bytes_of(t), 0, birth[i], death[i]});
+        else if (dev_alloc(g, &t.dptr, (size_t)t.n * t.h * t.w * t.cs, true)) return -1;
+    }
+    // greedy by size: the largest buffers first, each at the lowest offset that is free over its whole lifetime
+    std::sort(blks.begin(), blks.end(), [](const Blk& a, const Blk& b) { return a.bytes != b.bytes ? a.bytes > b.bytes : a.t < b.t; });
+    size_t total = 0;
+    for (size_t k = 0; k < blks.size(); k++) {
+        std::vector<std::pair<size_t, size_t>> busy;           // [offset, end) of placed buffers alive at the same time
+        for (size_t j = 0; j < k; j++)
+            if (blks[j].b <= blks[k].d && blks[k].b <= blks[j].d) busy.push_back({blks[j].off, blks[j].off + blks[j].bytes});
+        std::sort(busy.begin(), busy.end());
+        size_t off = 0;
+        for (auto& r : busy) { if (off + blks[k].bytes <= r.first) break; off = std::max(off, r.second); }
+        blks[k].off = off;
+        total = std::max(total, off + blks[k].bytes);
+    }
+    if (!blks.empty()) {
+        void* base = nullptr;
+        if (dev_alloc(g, &base, total, true)) return -1;
+        for (const Blk& b : blks) { g->tensors[b.t].dptr = (char*)base + b.off; g->pooled[b.t] = 1; }
+        g->pool_bytes = total;
+    }
+    for (size_t i = 0; i < g->tensors.size(); i++)                 // views / aliases of a shared buffer are shared too
+        if (g->tensors[i].ttype != TAMD_TT_CONST && (L.view_of[i] >= 0 || L.alias_of[i] >= 0) && g->pooled[root_of((int)i)]) g->pooled[i] = 1;
+    if (getenv("TAMD_DEBUG"))
+        fprintf(stderr, "[tamd] activations: %.1f MB one buffer per tensor, %zu of %zu buffers share %.1f MB\n", g->unpooled_bytes / 1048576.0, blks.size(),
+                own.size(), g->pool_bytes / 1048576.0);
+    return 0;
+}
+
+// Resolve views / aliases (nodes are in topological order; resolve chains iteratively); then the input layout steps
+static int resolve_views(tamd_graph* g, I8Layout& L)
+{
     for (int pass = 0; pass < 4; pass++)
         for (size_t i = 0; i < g->tensors.size(); i++) {
             HTensor& t = g->tensors[i];
-            if (view_of[i] >= 0) {
-                HTensor& o = g->tensors[view_of[i]];
-                t.dptr = o.dptr; t.cs = o.cs; t.c_off = o.c_off + view_off[i]; t.is_view = true;
-            } else if (alias_of[i] >= 0) {
-                HTensor& o = g->tensors[alias_of[i]];
+            if (L.view_of[i] >= 0) {
+                HTensor& o = g->tensors[L.view_of[i]];
+                t.dptr = o.dptr; t.cs = o.cs; t.c_off = o.c_off + L.view_off[i]; t.is_view = true;
+            } else if (L.alias_of[i] >= 0) {
+                HTensor& o = g->tensors[L.alias_of[i]];
                 t.dptr = o.dptr; t.cs = o.cs; t.c_off = o.c_off; t.is_view = o.is_view;
             }
         }
@@ -717,13 +804,14 @@ int plan_i8(tamd_graph* g)
         st.fn = [a](hipStream_t s) { return launch_nchw_to_nhwc(a, s); };
         g->in_steps.push_back(st);
     }
-    // ---- 2. compile nodes ---------------------------------------------------------------------
+    return 0;
+}
+
+// conv -> eltwise (-> relu) fusion (ResNet: branch2c / branch1 + residual add + relu): the eltwise is
+// folded into the LATER of its two producers when that one is a group-1 GEMM conv whose output feeds nothing else
+static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
+{
     g->fused_away.assign(g->tensors.size(), 0);
-    std::vector<char> fused(g->nodes.size(), 0);
-    // conv -> eltwise (-> relu) fusion (ResNet: branch2c / branch1 + residual add + relu): the eltwise is
-    // folded into the LATER of its two producers when that one is a group-1 GEMM conv whose output feeds nothing else
-    std::vector<FusedElt> fuse_at(g->nodes.size());
-    std::vector<char> has_fuse(g->nodes.size(), 0);
     const char* fuse_env = getenv("TAMD_FUSE_ELTWISE");
     auto producer = [&](int t) { for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].out.empty() && g->nodes[i].out[0] == t) return (int)i; return -1; };
     for (size_t ei = 0; ei < g->nodes.size() && !(fuse_env && atoi(fuse_env) == 0); ei++) {
@@ -739,7 +827,7 @@ int plan_i8(tamd_graph* g)
         const int later = std::max(pa, pb), conv_in = later == pa ? 0 : 1;
         if (later < 0 || later >= (int)ei) continue;
         HNode& c = g->nodes[later];
-        if (c.op != TAMD_OP_CONV || c.p.conv.group != 1 || g->tensors[c.in[0]].nchw_raw || has_fuse[later]) continue;
+        if (c.op != TAMD_OP_CONV || c.p.conv.group != 1 || g->tensors[c.in[0]].nchw_raw || L.has_fuse[later]) continue;
         if (c.p.conv.kernel_h * c.p.conv.kernel_w > 128 || count_consumers(g, e.in[conv_in]) != 1) continue;
         FusedElt fz{};
         fz.res_tensor = e.in[1 - conv_in]; fz.elt_tensor = e.out[0]; fz.out_tensor = e.out[0]; fz.type = ty;
@@ -753,325 +841,339 @@ int plan_i8(tamd_graph* g)
                     break;
                 }
             }
-        fuse_at[later] = fz; has_fuse[later] = 1; fused[ei] = 1;
+        L.fuse_at[later] = fz; L.has_fuse[later] = 1; L.fused[ei] = 1;
         g->fused_away[e.in[conv_in]] = 1;        // the conv's own int8 result only exists in registers
-        if (fz.relu) { fused[relu_node] = 1; g->fused_away[e.out[0]] = 1; }
+        if (fz.relu) { L.fused[relu_node] = 1; g->fused_away[e.out[0]] = 1; }
     }
-    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
-        HNode& n = g->nodes[ni];
-        if (fused[ni]) continue;
-        switch (n.op) {
-        case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
-            break;
-        case TAMD_OP_PERMUTE: {            // permute_ref.c:305-343, order (0, 2, 3, 1): a byte permutation -- written only when somebody reads it
-            HTensor& x = g->tensors[n.in[0]];
-            HTensor& y = g->tensors[n.out[0]];
-            if (perm_src[n.out[0]] >= 0) { g->fused_away[n.out[0]] = 1; break; }       // its Concat reads the NHWC buffer itself
-            FlatCatI8Args a{};
-            a.nsrc = 1; a.y = (int8_t*)y.dptr; a.outer = x.n; a.out_row = x.c * x.h * x.w; a.row_begin = 0; a.row_len = a.out_row;
-            a.src[0] = FlatCatI8Src{(const int8_t*)x.dptr + x.c_off, 1, a.out_row, x.c, x.h * x.w, x.cs, 0, 1.f, 1};
-            Step st; st.node = n.name; st.kernel = "permute_i8"; st.bytes = 2.0 * x.elems();
-            st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
+}
+
+// Permute(0, 2, 3, 1) and Reshape of a convolution-stack tensor: one copy into the reference's dense element order, the source read
+// as flatcat_i8 kind 1 (permuted) | 2 (NCHW)
+static void push_dense_copy(tamd_graph* g, HNode& n, int kind, const char* kernel)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    FlatCatI8Args a{};
+    a.nsrc = 1; a.y = (int8_t*)y.dptr; a.outer = x.n; a.out_row = x.c * x.h * x.w; a.row_begin = 0; a.row_len = a.out_row;
+    a.src[0] = FlatCatI8Src{(const int8_t*)x.dptr + x.c_off, kind, a.out_row, x.c, x.h * x.w, x.cs, 0, 1.f, 1};
+    Step st; st.node = n.name; st.kernel = kernel; st.bytes = 2.0 * x.elems();
+    st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
+    g->steps.push_back(st);
+}
+
+// permute_ref.c:305-343, order (0, 2, 3, 1): a byte permutation -- written only when somebody reads it
+static int plan_permute(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    if (L.perm_src[n.out[0]] >= 0) g->fused_away[n.out[0]] = 1;         // its Concat reads the NHWC buffer itself
+    else push_dense_copy(g, n, 1, "permute_i8");
+    return 0;
+}
+
+// reshape_ref.c:76-90 (NCHW): the same bytes under another shape
+static int plan_reshape(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    if (L.alias_of[n.out[0]] >= 0) { if (L.perm_src[n.out[0]] >= 0) g->fused_away[n.out[0]] = 1; }     // dense input: a view
+    else push_dense_copy(g, n, 2, "reshape_i8");      // convolution-stack input: its NCHW element order, written once
+    return 0;
+}
+
+// shapes only: evaluated here, once (graph_infer.hip priorbox_eval), quantised as priorbox_ref.c:195-210
+static int plan_priorbox(tamd_graph* g, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const HTensor& img = g->tensors[n.in[1]];
+    if (y.scales.empty()) { set_error("priorbox %s: missing quant params", n.name.c_str()); return -1; }
+    std::vector<float> boxes;
+    std::vector<int8_t> q;
+    priorbox_eval(n.p.priorbox, x.dims[2], x.dims[3], img.dims[2], img.dims[3], &boxes);
+    if (boxes.size() != y.elems()) { set_error("priorbox %s: output shape mismatch", n.name.c_str()); return -1; }
+    priorbox_quant_i8(boxes, y.scales[0], &q);
+    HIPCHK(hipMemcpyAsync(y.dptr, q.data(), q.size(), hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    y.prerun_const = true;
+    return 0;
+}
+
+static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    HTensor& y = g->tensors[n.out[0]];
+    // dense output: for every index in front of the axis each input is one contiguous run of the output's run; up to
+    // kFlatCatMax inputs per launch (the six SSD heads of a Concat: one launch), each read in the reference's element order
+    const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
+    if (y.scales.empty()) { set_error("concat %s: missing quant params", n.name.c_str()); return -1; }
+    long outer = 1, inner = 1;
+    for (int d = 0; d < ax; d++) outer *= y.dims[d];
+    for (size_t d = ax + 1; d < y.dims.size(); d++) inner *= y.dims[d];
+    const int out_row = (int)(y.dims[ax] * inner);
+    bool all_const = true;
+    for (int i : n.in) all_const &= g->tensors[i].prerun_const;
+    int begin = 0;
+    for (size_t k0 = 0; k0 < n.in.size(); k0 += kFlatCatMax) {
+        FlatCatI8Args a{};
+        a.y = (int8_t*)y.dptr; a.outer = outer; a.out_row = out_row; a.row_begin = begin;
+        Step st; st.node = n.name; st.kernel = "flatcat_i8"; st.once = all_const;
+        for (size_t k = k0; k < std::min(n.in.size(), k0 + (size_t)kFlatCatMax); k++) {
+            HTensor& x = g->tensors[n.in[k]];
+            if (x.dtype != y.dtype || x.scales.empty()) { set_error("concat %s: input %s: dtype / quant params", n.name.c_str(), x.name.c_str()); return -1; }
+            FlatCatI8Src s{};
+            s.begin = begin; s.identity = n.in.size() == 1;            // concat_kernel_ref_int8.c:47-57: a single input is copied as it is
+            volatile float rs = x.scales[0] / y.scales[0];             // :70 rescale = in_scale / out_scale
+            s.rescale = rs;
+            if (L.perm_src[n.in[k]] >= 0) {                              // Permute(0,2,3,1) (-> Flatten) of an NHWC tensor, read in place
+                HTensor& p = g->tensors[L.perm_src[n.in[k]]];
+                s.x = (const int8_t*)p.dptr + p.c_off; s.kind = 1; s.C = p.c; s.HW = p.h * p.w; s.cs = p.cs; s.chunk = p.c * p.h * p.w;
+                if (p.n != outer) { set_error("concat %s: a permuted input on axis %d", n.name.c_str(), ax); return -1; }
+                st.kernel = "permute_concat_i8";
+            } else if (L.dense[n.in[k]]) {
+                s.x = (const int8_t*)x.dptr; s.kind = 0; s.chunk = (int)(x.dims[ax] * inner);
+            } else {                                                   // a convolution-stack tensor, read in NCHW element order
+                s.x = (const int8_t*)x.dptr + x.c_off; s.kind = 2; s.C = x.c; s.HW = x.h * x.w; s.cs = x.cs;
+                s.chunk = (int)((size_t)x.n * x.c * x.h * x.w / (size_t)outer);
+            }
+            a.src[a.nsrc++] = s;
+            begin += s.chunk;
+            st.bytes += 2.0 * outer * s.chunk;
+        }
+        a.row_len = begin - a.row_begin;
+        st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
+        g->steps.push_back(st);
+    }
+    if (begin != out_row) { set_error("concat %s: the inputs do not add up to the output", n.name.c_str()); return -1; }
+    y.prerun_const = all_const;
+    return 0;
+}
+
+static int plan_channel_concat(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    HTensor& y = g->tensors[n.out[0]];
+    int off = 0;
+    for (int i : n.in) {
+        HTensor& x = g->tensors[i];
+        if (!(L.view_of[i] == n.out[0] && L.view_off[i] == off && x.is_view)) {
+            CatCopyArgs a{};
+            a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+            a.pixels = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.ldc = y.cs; a.c_off = y.c_off + off;
+            volatile float rs = x.scales[0] / y.scales[0];      // concat_kernel_ref_int8.c:70: rescale = in_scale / out_scale
+            a.rescale = rs;
+            a.identity = n.in.size() == 1;                      // :47-57: a single input is copied as it is
+            Step st; st.node = n.name; st.kernel = "concat_copy_i8"; st.bytes = 2.0 * a.pixels * x.c;
+            st.fn = [a](hipStream_t s) { return launch_concat_copy_i8(a, s); };
             g->steps.push_back(st);
-            break;
         }
-        case TAMD_OP_RESHAPE: {            // reshape_ref.c:76-90 (NCHW): the same bytes under another shape
-            HTensor& x = g->tensors[n.in[0]];
-            HTensor& y = g->tensors[n.out[0]];
-            if (alias_of[n.out[0]] >= 0) { if (perm_src[n.out[0]] >= 0) g->fused_away[n.out[0]] = 1; break; }     // dense input: a view
-            FlatCatI8Args a{};              // convolution-stack input: its NCHW element order, written once
-            a.nsrc = 1; a.y = (int8_t*)y.dptr; a.outer = x.n; a.out_row = x.c * x.h * x.w; a.row_begin = 0; a.row_len = a.out_row;
-            a.src[0] = FlatCatI8Src{(const int8_t*)x.dptr + x.c_off, 2, a.out_row, x.c, x.h * x.w, x.cs, 0, 1.f, 1};
-            Step st; st.node = n.name; st.kernel = "reshape_i8"; st.bytes = 2.0 * x.elems();
-            st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
-            g->steps.push_back(st);
-            break;
+        off += x.c;
+    }
+    return 0;
+}
+
+// stem: first-layer convolution whose only consumer is a MAX pool 3x3 / 2 -> one launch, the conv map stays in LDS
+// (conv_first_pool.hip).  1: *fused is that launch, 0: the pair stays two launches
+static int fuse_stem(tamd_graph* g, HNode& conv, HNode& pool, const Planned& c, const Planned& p, Step* fused)
+{
+    if (c.kind != Planned::FIRST || !conv_first_pool_applicable(c.first, p.pool)) return 0;
+    const FirstPoolArgs fa = conv_first_pool_args(c.first, p.pool);
+    Step& st = *fused;
+    st.node = c.step.node + "+" + p.step.node;
+    st.kernel = "conv_first_pool_i8";
+    st.macs = c.step.macs;
+    st.bytes = c.step.bytes + p.step.bytes;      // SURVEY 8(d) accounting, per layer: the conv map still counts
+    st.fn = [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); };
+    st.rd.push_back(access_of(g->tensors[conv.in[0]])); st.wr.push_back(access_of(g->tensors[pool.out[0]])); st.deps = true;
+    g->fused_away[conv.out[0]] = 1;
+    return 1;
+}
+
+// depthwise 3x3 whose only consumer is a pointwise conv (large batches): one launch, the depthwise map stays in LDS (dwpw.hip).
+// The node dwi has just been planned as `pd`; where that is a depthwise 3x3 launch this plans its pointwise consumer as a trial and
+// lets plan_dwpw turn the two into one.  1: *fused is that launch (the consumer is marked), 0: the depthwise launch stands alone, the
+// trial is dropped and the consumer goes through the ordinary path at its own node (its weights are uploaded again there: known, and
+// kept, because keeping the trial would move every later buffer), -1: error
+static int try_dwpw(tamd_graph* g, I8Layout& L, size_t dwi, const Planned& pd, Step* fused)
+{
+    HNode& d = g->nodes[dwi];
+    const HTensor& dy = g->tensors[d.out[0]];
+    const char* dp_env = getenv("TAMD_FUSE_DWPW");
+    if ((dp_env && atoi(dp_env) == 0) || pd.kind != Planned::DW3X3 || d.p.conv.stride_h != 1 || count_consumers(g, d.out[0]) != 1 || dy.is_view) return 0;
+    if ((long)dy.n * dy.h * dy.w < 4096 && !(dp_env && atoi(dp_env) == 2)) return 0;
+    for (auto& o : g->outputs) if (o.tensor == d.out[0]) return 0;
+    int pw_node = -1;
+    for (size_t nj = dwi + 1; nj < g->nodes.size(); nj++)
+        if (g->nodes[nj].op == TAMD_OP_CONV && g->nodes[nj].in.size() >= 2 && g->nodes[nj].in[0] == d.out[0] && !L.fused[nj] && !L.has_fuse[nj]
+            && g->nodes[nj].p.conv.group == 1 && g->nodes[nj].p.conv.kernel_h == 1 && g->nodes[nj].p.conv.kernel_w == 1) { pw_node = (int)nj; break; }
+    if (pw_node < 0) return 0;
+    {   // what dwpw_applicable will ask of the shapes, before the consumer is planned (and its weights uploaded) for nothing
+        const HTensor& py = g->tensors[g->nodes[pw_node].out[0]];
+        const tamd_conv_param& q = g->nodes[pw_node].p.conv;
+        if (py.c % 64 != 0 || py.c > 512 || dy.w > 16 || q.stride_h != 1 || q.stride_w != 1 || q.pad_h0 || q.pad_w0 || q.pad_h1 || q.pad_w1) return 0;
+    }
+    Planned pc;
+    if (plan_conv(g, g->nodes[pw_node], false, nullptr, &pc)) return -1;
+    const int r = plan_dwpw(g, d, g->nodes[pw_node], pd, pc, fused);
+    if (r == 1) L.fused[pw_node] = 1;
+    return r;
+}
+
+// A convolution node and its three pairings: conv + pool (stem), pointwise + its tail (pwdw), depthwise + pointwise (dwpw).  Each
+// plans the launches involved as values and pushes either the fused launch or the planned ones.
+static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
+{
+    HNode& n = g->nodes[ni];
+    Step st;
+    // stem (TAMD_FIRST_POOL=0: two launches, for A/B runs and the fused == unfused tests)
+    if (!L.has_fuse[ni] && g->tensors[n.in[0]].nchw_raw && count_consumers(g, n.out[0]) == 1) {
+        int pool_node = -1;
+        for (size_t nj = ni + 1; nj < g->nodes.size(); nj++)
+            if (g->nodes[nj].op == TAMD_OP_POOL && g->nodes[nj].in[0] == n.out[0] && !L.fused[nj]) { pool_node = (int)nj; break; }
+        const char* fp_env = tamd_pin("first_pool");
+        bool is_out = false;
+        for (auto& o : g->outputs) is_out |= (o.tensor == n.out[0]);
+        if (pool_node >= 0 && !is_out && !(fp_env && atoi(fp_env) == 0)) {
+            Planned c, p;
+            if (plan_conv(g, n, false, nullptr, &c)) return -1;
+            if (plan_pool(g, g->nodes[pool_node], &p)) return -1;
+            L.fused[pool_node] = 1;
+            if (fuse_stem(g, n, g->nodes[pool_node], c, p, &st)) g->steps.push_back(st);
+            else { g->steps.push_back(c.step); g->steps.push_back(p.step); }
+            return 0;
         }
-        case TAMD_OP_PRIORBOX: {           // shapes only: evaluated here, once (graph_infer.hip priorbox_eval), quantised as priorbox_ref.c:195-210
-            HTensor& x = g->tensors[n.in[0]];
-            HTensor& y = g->tensors[n.out[0]];
-            const HTensor& img = g->tensors[n.in[1]];
-            if (y.scales.empty()) { set_error("priorbox %s: missing quant params", n.name.c_str()); return -1; }
-            std::vector<float> boxes;
-            std::vector<int8_t> q;
-            priorbox_eval(n.p.priorbox, x.dims[2], x.dims[3], img.dims[2], img.dims[3], &boxes);
-            if (boxes.size() != y.elems()) { set_error("priorbox %s: output shape mismatch", n.name.c_str()); return -1; }
-            priorbox_quant_i8(boxes, y.scales[0], &q);
-            HIPCHK(hipMemcpyAsync(y.dptr, q.data(), q.size(), hipMemcpyHostToDevice, g->stream));
-            HIPCHK(hipStreamSynchronize(g->stream));
-            y.prerun_const = true;
-            break;
-        }
-        case TAMD_OP_CONCAT: {
-            HTensor& y = g->tensors[n.out[0]];
-            if (flat_concat[ni]) {
-                // dense output: for every index in front of the axis each input is one contiguous run of the output's run; up to
-                // kFlatCatMax inputs per launch (the six SSD heads of a Concat: one launch), each read in the reference's element order
-                const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
-                if (y.scales.empty()) { set_error("concat %s: missing quant params", n.name.c_str()); return -1; }
-                long outer = 1, inner = 1;
-                for (int d = 0; d < ax; d++) outer *= y.dims[d];
-                for (size_t d = ax + 1; d < y.dims.size(); d++) inner *= y.dims[d];
-                const int out_row = (int)(y.dims[ax] * inner);
-                bool all_const = true;
-                for (int i : n.in) all_const &= g->tensors[i].prerun_const;
-                int begin = 0;
-                for (size_t k0 = 0; k0 < n.in.size(); k0 += kFlatCatMax) {
-                    FlatCatI8Args a{};
-                    a.y = (int8_t*)y.dptr; a.outer = outer; a.out_row = out_row; a.row_begin = begin;
-                    Step st; st.node = n.name; st.kernel = "flatcat_i8"; st.once = all_const;
-                    for (size_t k = k0; k < std::min(n.in.size(), k0 + (size_t)kFlatCatMax); k++) {
-                        HTensor& x = g->tensors[n.in[k]];
-                        if (x.dtype != y.dtype || x.scales.empty()) { set_error("concat %s: input %s: dtype / quant params", n.name.c_str(), x.name.c_str()); return -1; }
-                        FlatCatI8Src s{};
-                        s.begin = begin; s.identity = n.in.size() == 1;            // concat_kernel_ref_int8.c:47-57: a single input is copied as it is
-                        volatile float rs = x.scales[0] / y.scales[0];             // :70 rescale = in_scale / out_scale
-                        s.rescale = rs;
-                        if (perm_src[n.in[k]] >= 0) {                              // Permute(0,2,3,1) (-> Flatten) of an NHWC tensor, read in place
-                            HTensor& p = g->tensors[perm_src[n.in[k]]];
-                            s.x = (const int8_t*)p.dptr + p.c_off; s.kind = 1; s.C = p.c; s.HW = p.h * p.w; s.cs = p.cs; s.chunk = p.c * p.h * p.w;
-                            if (p.n != outer) { set_error("concat %s: a permuted input on axis %d", n.name.c_str(), ax); return -1; }
-                            st.kernel = "permute_concat_i8";
-                        } else if (dense[n.in[k]]) {
-                            s.x = (const int8_t*)x.dptr; s.kind = 0; s.chunk = (int)(x.dims[ax] * inner);
-                        } else {                                                   // a convolution-stack tensor, read in NCHW element order
-                            s.x = (const int8_t*)x.dptr + x.c_off; s.kind = 2; s.C = x.c; s.HW = x.h * x.w; s.cs = x.cs;
-                            s.chunk = (int)((size_t)x.n * x.c * x.h * x.w / (size_t)outer);
-                        }
-                        a.src[a.nsrc++] = s;
-                        begin += s.chunk;
-                        st.bytes += 2.0 * outer * s.chunk;
-                    }
-                    a.row_len = begin - a.row_begin;
-                    st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
-                    g->steps.push_back(st);
-                }
-                if (begin != out_row) { set_error("concat %s: the inputs do not add up to the output", n.name.c_str()); return -1; }
-                y.prerun_const = all_const;
-                break;
-            }
-            int off = 0;
-            for (int i : n.in) {
-                HTensor& x = g->tensors[i];
-                if (!(view_of[i] == n.out[0] && view_off[i] == off && x.is_view)) {
-                    CatCopyArgs a{};
-                    a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
-                    a.pixels = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.ldc = y.cs; a.c_off = y.c_off + off;
-                    volatile float rs = x.scales[0] / y.scales[0];      // concat_kernel_ref_int8.c:70: rescale = in_scale / out_scale
-                    a.rescale = rs;
-                    a.identity = n.in.size() == 1;                      // :47-57: a single input is copied as it is
-                    Step st; st.node = n.name; st.kernel = "concat_copy_i8"; st.bytes = 2.0 * a.pixels * x.c;
-                    st.fn = [a](hipStream_t s) { return launch_concat_copy_i8(a, s); };
-                    g->steps.push_back(st);
-                }
-                off += x.c;
-            }
-            break;
-        }
-        case TAMD_OP_CONV: {
-            int tmode = -1, prod = 0;
-            // depthwise 3x3 whose only consumer is a pointwise conv (large batches): one launch, the depthwise map stays in LDS (dwpw.hip).
-            // `try_dwpw(dwi)`: the depthwise node dwi has just been planned as the LAST step (g_last_dw describes it); plans its
-            // pointwise consumer behind it and lets plan_dwpw turn the two steps into one.  1: fused (the consumer is marked), 0: the
-            // depthwise step stands alone and the consumer goes through the ordinary path later, -1: error
-            auto try_dwpw = [&](size_t dwi) -> int {
-                HNode& d = g->nodes[dwi];
-                const HTensor& dy = g->tensors[d.out[0]];
-                const char* dp_env = getenv("TAMD_FUSE_DWPW");
-                if ((dp_env && atoi(dp_env) == 0) || !g_last_dw_valid || d.p.conv.stride_h != 1 || count_consumers(g, d.out[0]) != 1 || dy.is_view) return 0;
-                if ((long)dy.n * dy.h * dy.w < 4096 && !(dp_env && atoi(dp_env) == 2)) return 0;
-                for (auto& o : g->outputs) if (o.tensor == d.out[0]) return 0;
-                int pw_node = -1;
-                for (size_t nj = dwi + 1; nj < g->nodes.size(); nj++)
-                    if (g->nodes[nj].op == TAMD_OP_CONV && g->nodes[nj].in.size() >= 2 && g->nodes[nj].in[0] == d.out[0] && !fused[nj] && !has_fuse[nj]
-                        && g->nodes[nj].p.conv.group == 1 && g->nodes[nj].p.conv.kernel_h == 1 && g->nodes[nj].p.conv.kernel_w == 1) { pw_node = (int)nj; break; }
-                if (pw_node < 0) return 0;
-                {   // what dwpw_applicable will ask of the shapes, before the consumer is planned (and its weights uploaded) for nothing
-                    const HTensor& py = g->tensors[g->nodes[pw_node].out[0]];
-                    const tamd_conv_param& q = g->nodes[pw_node].p.conv;
-                    if (py.c % 64 != 0 || py.c > 512 || dy.w > 16 || q.stride_h != 1 || q.stride_w != 1 || q.pad_h0 || q.pad_w0 || q.pad_h1 || q.pad_w1) return 0;
-                }
-                const size_t sdw = g->steps.size() - 1;
-                g_last_gemm_valid = false;
-                if (plan_conv(g, g->nodes[pw_node], false)) return -1;
-                int r = 0;
-                if (g->steps.size() == sdw + 2) r = plan_dwpw(g, d, g->nodes[pw_node], sdw);
-                if (r < 0) return -1;
-                if (r == 1) { fused[pw_node] = 1; return 1; }
-                g->steps.resize(sdw + 1);                      // not fused: forget the trial plan of the consumer
-                return 0;
-            };
-            if (!has_fuse[ni] && n.p.conv.group > 1 && n.p.conv.group == g->tensors[n.in[0]].c && n.p.conv.kernel_h == 3 && n.p.conv.stride_h == 1
-                && !g->tensors[n.in[0]].nchw_raw) {
-                const size_t s0 = g->steps.size();
-                g_last_dw_valid = false;
-                if (plan_conv(g, n, false)) return -1;
-                if (g->steps.size() == s0 + 1 && try_dwpw(ni) < 0) return -1;
-                break;
-            }
-            // stem: first-layer convolution whose only consumer is a MAX pool 3x3 / 2 -> one launch, the conv map stays in LDS
-            // (TAMD_FIRST_POOL=0: two launches, for A/B runs and the fused == unfused tests)
-            if (!has_fuse[ni] && g->tensors[n.in[0]].nchw_raw && count_consumers(g, n.out[0]) == 1) {
-                int pool_node = -1;
-                for (size_t nj = ni + 1; nj < g->nodes.size(); nj++)
-                    if (g->nodes[nj].op == TAMD_OP_POOL && g->nodes[nj].in[0] == n.out[0] && !fused[nj]) { pool_node = (int)nj; break; }
-                const char* fp_env = tamd_pin("first_pool");
-                bool is_out = false;
-                for (auto& o : g->outputs) is_out |= (o.tensor == n.out[0]);
-                if (pool_node >= 0 && !is_out && !(fp_env && atoi(fp_env) == 0)) {
-                    const size_t s0 = g->steps.size();
-                    g_last_first_valid = false;
-                    if (plan_conv(g, n, false)) return -1;
-                    if (plan_pool(g, g->nodes[pool_node])) return -1;
-                    fused[pool_node] = 1;
-                    if (g->steps.size() == s0 + 2 && g_last_first_valid && conv_first_pool_applicable(g_last_first, g_last_pool)) {
-                        const FirstPoolArgs fa = conv_first_pool_args(g_last_first, g_last_pool);
-                        Step st;
-                        st.node = g->steps[s0].node + "+" + g->steps[s0 + 1].node;
-                        st.kernel = "conv_first_pool_i8";
-                        st.macs = g->steps[s0].macs;
-                        st.bytes = g->steps[s0].bytes + g->steps[s0 + 1].bytes;      // SURVEY 8(d) accounting, per layer: the conv map still counts
-                        st.fn = [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); };
-                        st.rd.push_back(access_of(g->tensors[n.in[0]])); st.wr.push_back(access_of(g->tensors[g->nodes[pool_node].out[0]])); st.deps = true;
-                        g->steps.resize(s0);
-                        g->steps.push_back(st);
-                        g->fused_away[n.out[0]] = 1;
-                    }
-                    break;
-                }
-            }
-            const int tail = has_fuse[ni] ? -1 : find_pwdw_tail(g, ni, &tmode, &prod);
-            if (tail >= 0 && !fused[tail]) {
-                // the pair is planned here, the tail ahead of its node order (its only input is this conv's output), then
-                // possibly replaced by ONE fused launch
-                const size_t s0 = g->steps.size();
-                g_last_dw_valid = false;
-                if (plan_conv(g, n, false)) return -1;
-                if (tmode == 0 ? plan_pool(g, g->nodes[tail]) : plan_conv(g, g->nodes[tail], false)) return -1;
-                fused[tail] = 1;
-                g_last_dw_valid = g_last_dw_valid && tmode == 1;
-                // Where the depthwise tail can go together with ITS consumer (dwpw.hip: batched 14x14-class maps, stride 1), that pairing is
-                // tried FIRST.  In a chain pw, dw, pw, dw, .. either pairing covers every layer once per period, and in a pass dwpw is the
-                // cheaper period (MobileNet-v1 b64: 16.4 us against 22.9 us for the pwdw pair with two slices per block) -- but the
-                // plan-time race, which times a launch back to back with itself, saw the pwdw pair at < 18.8 us and took it
-                // (profiles/r05_layers_mobilenet_v1_int8_b64.txt, the evidence plan: the 14x14 block 120 us; with this order 95 us)
-                int took = 0;
-                if (tmode == 1 && g->steps.size() == s0 + 2) { took = try_dwpw((size_t)tail); if (took < 0) return -1; }
-                if (!took && g->steps.size() == s0 + 2 && plan_pwdw(g, n, g->nodes[tail], tmode, prod, s0)) return -1;
-                break;
-            }
-            if (plan_conv(g, n, false, has_fuse[ni] ? &fuse_at[ni] : nullptr)) return -1;
-            break;
-        }
-        case TAMD_OP_FC:
-            if (plan_conv(g, n, true)) return -1;
-            break;
-        case TAMD_OP_POOL:
-            if (plan_pool(g, n)) return -1;
-            break;
-        case TAMD_OP_SOFTMAX: {            // ResNet-50's prob; softmax_kernel_ref_int8.c over the channel axis
-            HTensor& x = g->tensors[n.in[0]];
-            HTensor& y = g->tensors[n.out[0]];
-            int ax = n.p.softmax.axis < 0 ? n.p.softmax.axis + (int)x.dims.size() : n.p.softmax.axis;
-            if (x.scales.empty() || y.scales.empty()) { set_error("softmax %s: missing quant params", n.name.c_str()); return -1; }
-            const bool general = dense[n.in[0]] || (x.dims.size() == 4 && (ax == 2 || ax == 3));
-            if (general) {
-                // round 6: any axis of a dense tensor (the SSD tail: Reshape -> Softmax(axis 2) on [N, priors, classes]) and the spatial
-                // axes of an NHWC tensor -- the same kernel with strided addressing (kernels.h: SoftmaxI8Args)
-                if (ax < 0 || ax >= (int)x.dims.size() || x.dims[ax] < 1 || x.dims[ax] > kSoftmaxI8MaxC) {
-                    set_error("softmax %s: axis %d of at most %d values", n.name.c_str(), ax, kSoftmaxI8MaxC);
-                    return -1;
-                }
-                SoftmaxI8Args a{};
-                a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
-                a.C = x.dims[ax]; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-                if (dense[n.in[0]]) {
-                    long outer = 1, inner = 1;
-                    for (int d = 0; d < ax; d++) outer *= x.dims[d];
-                    for (size_t d = ax + 1; d < x.dims.size(); d++) inner *= x.dims[d];
-                    a.positions = outer * inner; a.d1 = a.d2 = inner; a.is1 = a.os1 = (long)a.C * inner; a.is2 = a.os2 = 0; a.istride = a.ostride = inner;
-                } else if (ax == 3) {
-                    a.positions = (long)x.n * x.h * x.c; a.d1 = a.d2 = x.c;
-                    a.is1 = (long)x.w * x.cs; a.os1 = (long)y.w * y.cs; a.is2 = a.os2 = 0; a.istride = x.cs; a.ostride = y.cs;
-                } else {
-                    a.positions = (long)x.n * x.w * x.c; a.d1 = (long)x.w * x.c; a.d2 = x.c;
-                    a.is1 = (long)x.h * x.w * x.cs; a.os1 = (long)y.h * y.w * y.cs; a.is2 = x.cs; a.os2 = y.cs;
-                    a.istride = (long)x.w * x.cs; a.ostride = (long)y.w * y.cs;
-                }
-                Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * (double)x.elems();
-                st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
-                g->steps.push_back(st);
-                break;
-            }
-            if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || x.c < 1 || x.c > kSoftmaxI8MaxC) {
-                set_error("softmax %s is not supported on the device: int8 softmax runs over the channel axis of a 2-D / 4-D tensor of at most %d channels",
-                          n.name.c_str(), kSoftmaxI8MaxC);
-                return -1;
-            }
-            if (x.dims.size() == 2 && x.h * x.w != 1) {
-                // a 2-D tensor that is the flattened view of an H x W > 1 map keeps the map's NHWC geometry on the device: its "channel
-                // axis" is C, the reference normalises over all C*H*W values in NCHW order.  The plugin leaves such a node to
-                // the CPU device (hip_device.cc: node_runs_on_device); through the C ABI it is refused here
-                set_error("softmax %s is not supported on the device: its 2-D input is the flattened view of a %d x %d map", n.name.c_str(), x.h, x.w);
-                return -1;
-            }
-            if (x.scales.empty() || y.scales.empty()) { set_error("softmax %s: missing quant params", n.name.c_str()); return -1; }
-            SoftmaxI8Args a{};
-            a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
-            a.positions = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.cs_out = y.cs;
-            a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-            Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * a.positions * x.c;
-            st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
-            g->steps.push_back(st);
-            break;
-        }
-        case TAMD_OP_RELU: {
-            HTensor& x = g->tensors[n.in[0]];
-            HTensor& y = g->tensors[n.out[0]];
-            if (x.is_view || y.is_view) { set_error("relu %s on a concat view is not supported", n.name.c_str()); return -1; }
-            ReluArgs a{(const int8_t*)x.dptr, (int8_t*)y.dptr, (size_t)x.n * x.h * x.w * x.cs, n.p.relu.negative_slope, x.scales[0], y.scales[0]};
-            Step st; st.node = n.name; st.kernel = "relu_i8"; st.bytes = 2.0 * x.n * x.h * x.w * x.c;
-            st.fn = [a](hipStream_t s) { return launch_relu(a, s); };
-            g->steps.push_back(st);
-            break;
-        }
-        case TAMD_OP_ELTWISE: {
-            HTensor& xa = g->tensors[n.in[0]];
-            HTensor& xb = g->tensors[n.in[1]];
-            HTensor* y = &g->tensors[n.out[0]];
-            if (xa.is_view || xb.is_view || y->is_view || xa.dims != xb.dims) { set_error("eltwise %s: views / broadcast not supported", n.name.c_str()); return -1; }
-            EltArgs a{};
-            a.a = (const int8_t*)xa.dptr; a.b = (const int8_t*)xb.dptr; a.count = (size_t)xa.n * xa.h * xa.w * xa.cs;
-            a.type = n.p.elt.type; a.sa = xa.scales[0]; a.sb = xb.scales[0]; a.out_scale = y->scales[0];
-            if (a.type != 0 && a.type != 2 && a.type != 4 && a.type != 6) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
-            std::string kname = "eltwise_i8";
-            double bytes = 3.0 * xa.n * xa.h * xa.w * xa.c;
-            // fuse the standalone ReLU that follows (ResNet: 16 x eltwise -> relu), SURVEY §8f-1
-            if (count_consumers(g, n.out[0]) == 1) {
-                for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
-                    HNode& r = g->nodes[nj];
-                    if (r.op == TAMD_OP_RELU && r.in[0] == n.out[0] && r.p.relu.negative_slope == 0.f) {
-                        HTensor& ry = g->tensors[r.out[0]];
-                        if (ry.is_view) break;
-                        a.fuse_relu = ry.scales[0] == a.out_scale ? 2 : 1; a.relu_out_scale = ry.scales[0];
-                        y = &ry; fused[nj] = 1; kname = "eltwise_relu_i8";
-                        g->fused_away[n.out[0]] = 1;
-                        break;
-                    }
-                }
-            }
-            a.y = (int8_t*)y->dptr;
-            Step st; st.node = n.name; st.kernel = kname; st.bytes = bytes;
-            st.fn = [a](hipStream_t s) { return launch_eltwise(a, s); };
-            g->steps.push_back(st);
-            break;
-        }
-        default:
-            set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
+    }
+    int tmode = -1, prod = 0;
+    const int tail = L.has_fuse[ni] ? -1 : find_pwdw_tail(g, ni, &tmode, &prod);
+    if (tail >= 0 && !L.fused[tail]) {
+        // the pair is planned here, the tail ahead of its node order (its only input is this conv's output), then
+        // possibly replaced by ONE fused launch
+        Planned a, b;
+        if (plan_conv(g, n, false, nullptr, &a)) return -1;
+        if (tmode == 0 ? plan_pool(g, g->nodes[tail], &b) : plan_conv(g, g->nodes[tail], false, nullptr, &b)) return -1;
+        L.fused[tail] = 1;
+        // Where the depthwise tail can go together with ITS consumer (dwpw.hip: batched 14x14-class maps, stride 1), that pairing is
+        // tried FIRST.  In a chain pw, dw, pw, dw, .. either pairing covers every layer once per period, and in a pass dwpw is the
+        // cheaper period (MobileNet-v1 b64: 16.4 us against 22.9 us for the pwdw pair with two slices per block) -- but the
+        // plan-time race, which times a launch back to back with itself, saw the pwdw pair at < 18.8 us and took it
+        // (profiles/r05_layers_mobilenet_v1_int8_b64.txt, the evidence plan: the 14x14 block 120 us; with this order 95 us)
+        int took = tmode == 1 ? try_dwpw(g, L, (size_t)tail, b, &st) : 0;
+        if (took < 0) return -1;
+        if (took) { g->steps.push_back(a.step); g->steps.push_back(st); return 0; }
+        took = plan_pwdw(g, n, g->nodes[tail], tmode, prod, a, b, &st);
+        if (took < 0) return -1;
+        if (took) g->steps.push_back(st);
+        else { g->steps.push_back(a.step); g->steps.push_back(b.step); }
+        return 0;
+    }
+    Planned c;
+    if (plan_conv(g, n, false, L.has_fuse[ni] ? &L.fuse_at[ni] : nullptr, &c)) return -1;
+    const int took = try_dwpw(g, L, ni, c, &st);        // (anything but a depthwise 3x3 launch: 0)
+    if (took < 0) return -1;
+    g->steps.push_back(took ? st : c.step);
+    return 0;
+}
+
+// ResNet-50's prob; softmax_kernel_ref_int8.c over the channel axis
+static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    int ax = n.p.softmax.axis < 0 ? n.p.softmax.axis + (int)x.dims.size() : n.p.softmax.axis;
+    if (x.scales.empty() || y.scales.empty()) { set_error("softmax %s: missing quant params", n.name.c_str()); return -1; }
+    const bool general = L.dense[n.in[0]] || (x.dims.size() == 4 && (ax == 2 || ax == 3));
+    if (general) {
+        // any axis of a dense tensor (the SSD tail: Reshape -> Softmax(axis 2) on [N, priors, classes]) and the spatial
+        // axes of an NHWC tensor -- the same kernel with strided addressing (kernels.h: SoftmaxI8Args)
+        if (ax < 0 || ax >= (int)x.dims.size() || x.dims[ax] < 1 || x.dims[ax] > kSoftmaxI8MaxC) {
+            set_error("softmax %s: axis %d of at most %d values", n.name.c_str(), ax, kSoftmaxI8MaxC);
             return -1;
         }
+        SoftmaxI8Args a{};
+        a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
+        a.C = x.dims[ax]; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
+        if (L.dense[n.in[0]]) {
+            long outer = 1, inner = 1;
+            for (int d = 0; d < ax; d++) outer *= x.dims[d];
+            for (size_t d = ax + 1; d < x.dims.size(); d++) inner *= x.dims[d];
+            a.positions = outer * inner; a.d1 = a.d2 = inner; a.is1 = a.os1 = (long)a.C * inner; a.is2 = a.os2 = 0; a.istride = a.ostride = inner;
+        } else if (ax == 3) {
+            a.positions = (long)x.n * x.h * x.c; a.d1 = a.d2 = x.c;
+            a.is1 = (long)x.w * x.cs; a.os1 = (long)y.w * y.cs; a.is2 = a.os2 = 0; a.istride = x.cs; a.ostride = y.cs;
+        } else {
+            a.positions = (long)x.n * x.w * x.c; a.d1 = (long)x.w * x.c; a.d2 = x.c;
+            a.is1 = (long)x.h * x.w * x.cs; a.os1 = (long)y.h * y.w * y.cs; a.is2 = x.cs; a.os2 = y.cs;
+            a.istride = (long)x.w * x.cs; a.ostride = (long)y.w * y.cs;
+        }
+        Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * (double)x.elems();
+        st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
+        g->steps.push_back(st);
+        return 0;
     }
-    // ---- 3. outputs: NHWC -> the reference's NCHW order ------------------------------------------
+    if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || x.c < 1 || x.c > kSoftmaxI8MaxC) {
+        set_error("softmax %s is not supported on the device: int8 softmax runs over the channel axis of a 2-D / 4-D tensor of at most %d channels",
+                  n.name.c_str(), kSoftmaxI8MaxC);
+        return -1;
+    }
+    if (x.dims.size() == 2 && x.h * x.w != 1) {
+        // a 2-D tensor that is the flattened view of an H x W > 1 map keeps the map's NHWC geometry on the device: its "channel
+        // axis" is C, the reference normalises over all C*H*W values in NCHW order.  The plugin leaves such a node to
+        // the CPU device (hip_device.cc: node_runs_on_device); through the C ABI it is refused here
+        set_error("softmax %s is not supported on the device: its 2-D input is the flattened view of a %d x %d map", n.name.c_str(), x.h, x.w);
+        return -1;
+    }
+    SoftmaxI8Args a{};
+    a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
+    a.positions = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.cs_out = y.cs;
+    a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
+    Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * a.positions * x.c;
+    st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
+    g->steps.push_back(st);
+    return 0;
+}
+
+static int plan_relu(tamd_graph* g, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (x.is_view || y.is_view) { set_error("relu %s on a concat view is not supported", n.name.c_str()); return -1; }
+    ReluArgs a{(const int8_t*)x.dptr, (int8_t*)y.dptr, (size_t)x.n * x.h * x.w * x.cs, n.p.relu.negative_slope, x.scales[0], y.scales[0]};
+    Step st; st.node = n.name; st.kernel = "relu_i8"; st.bytes = 2.0 * x.n * x.h * x.w * x.c;
+    st.fn = [a](hipStream_t s) { return launch_relu(a, s); };
+    g->steps.push_back(st);
+    return 0;
+}
+
+static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, size_t ni)
+{
+    HTensor& xa = g->tensors[n.in[0]];
+    HTensor& xb = g->tensors[n.in[1]];
+    HTensor* y = &g->tensors[n.out[0]];
+    if (xa.is_view || xb.is_view || y->is_view || xa.dims != xb.dims) { set_error("eltwise %s: views / broadcast not supported", n.name.c_str()); return -1; }
+    EltArgs a{};
+    a.a = (const int8_t*)xa.dptr; a.b = (const int8_t*)xb.dptr; a.count = (size_t)xa.n * xa.h * xa.w * xa.cs;
+    a.type = n.p.elt.type; a.sa = xa.scales[0]; a.sb = xb.scales[0]; a.out_scale = y->scales[0];
+    if (a.type != 0 && a.type != 2 && a.type != 4 && a.type != 6) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
+    std::string kname = "eltwise_i8";
+    double bytes = 3.0 * xa.n * xa.h * xa.w * xa.c;
+    // fuse the standalone ReLU that follows (ResNet: 16 x eltwise -> relu), SURVEY §8f-1
+    if (count_consumers(g, n.out[0]) == 1) {
+        for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
+            HNode& r = g->nodes[nj];
+            if (r.op == TAMD_OP_RELU && r.in[0] == n.out[0] && r.p.relu.negative_slope == 0.f) {
+                HTensor& ry = g->tensors[r.out[0]];
+                if (ry.is_view) break;
+                a.fuse_relu = ry.scales[0] == a.out_scale ? 2 : 1; a.relu_out_scale = ry.scales[0];
+                y = &ry; L.fused[nj] = 1; kname = "eltwise_relu_i8";
+                g->fused_away[n.out[0]] = 1;
+                break;
+            }
+        }
+    }
+    a.y = (int8_t*)y->dptr;
+    Step st; st.node = n.name; st.kernel = kname; st.bytes = bytes;
+    st.fn = [a](hipStream_t s) { return launch_eltwise(a, s); };
+    g->steps.push_back(st);
+    return 0;
+}
+
+// outputs: NHWC -> the reference's NCHW order
+static int plan_outputs(tamd_graph* g)
+{
     for (auto& io : g->outputs) {
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esize(t.dtype);
@@ -1087,6 +1189,37 @@ int plan_i8(tamd_graph* g)
     return 0;
 }
 
-// io_slot < 0: the device-resident launch list; 0 | 1: with the upload of every input from / the download of every output to
+// node list -> launch list: the layout passes in order, then one planner per node
+int plan_i8(tamd_graph* g)
+{
+    for (auto& t : g->tensors) if (t.ttype != TAMD_TT_CONST) nhwc_geom(t);
+    I8Layout L(g->tensors.size(), g->nodes.size());
+    if (plan_dense(g, L) || plan_concat_views(g, L) || plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
+    scan_eltwise_fusion(g, L);
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        HNode& n = g->nodes[ni];
+        if (L.fused[ni]) continue;
+        Planned one;
+        int r = 0;
+        switch (n.op) {
+        case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN: break;
+        case TAMD_OP_PERMUTE: r = plan_permute(g, L, n); break;
+        case TAMD_OP_RESHAPE: r = plan_reshape(g, L, n); break;
+        case TAMD_OP_PRIORBOX: r = plan_priorbox(g, n); break;
+        case TAMD_OP_CONCAT: r = L.flat_concat[ni] ? plan_flat_concat(g, L, n) : plan_channel_concat(g, L, n); break;
+        case TAMD_OP_CONV: r = plan_conv_node(g, L, ni); break;
+        case TAMD_OP_FC: if (!(r = plan_conv(g, n, true, nullptr, &one))) g->steps.push_back(one.step); break;
+        case TAMD_OP_POOL: if (!(r = plan_pool(g, n, &one))) g->steps.push_back(one.step); break;
+        case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n); break;
+        case TAMD_OP_RELU: r = plan_relu(g, n); break;
+        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, ni); break;
+        default:
+            set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
+            return -1;
+        }
+        if (r) return -1;
+    }
+    return plan_outputs(g);
+}
 
 }  // namespace tamd

@@ -1,21 +1,13 @@
 // int8 planner, the pair fusions: pointwise conv + its single consumer (depthwise 3x3 | global pooling) in one launch (pwdw.hip), and
-// depthwise 3x3 + the pointwise conv behind it (dwpw.hip).  Split out of graph.hip in round 6.
+// depthwise 3x3 + the pointwise conv behind it (dwpw.hip).
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
 
-#include <stdarg.h>
-#include <stddef.h>
 #include <stdio.h>
-#include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cfloat>
-#include <chrono>
 #include <cmath>
-#include <mutex>
 
 #include "epilogue.h"
 #include "graph_plan.h"
@@ -78,10 +70,10 @@ static RaceCand two_launches(const std::string& tag, const Step& sa, const Step&
 }
 
 
-// The two nodes were just planned as steps [s0, s0 + 2); build the fused launch, and keep whichever is faster
-// (plan-time measurement; without autotune: fuse the small-map cases where launches, not bytes, are the cost).
+// The two nodes were just planned as `pa` (the pointwise conv) and `pb` (its tail); build the fused launch, and keep whichever is
+// faster (plan-time measurement; without autotune: fuse the small-map cases where launches, not bytes, are the cost).
 // TAMD_FUSE_PWDW=0 never fuses, =2 always fuses; TAMD_PWDW_CFG="TH,TW,threads" pins the tile configuration (tests).
-int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s0)
+int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Planned& pa, const Planned& pb, Step* fused)
 {
     const char* fenv = getenv("TAMD_FUSE_PWDW");                 // read at every prerun
     const int fmode = fenv ? atoi(fenv) : 1;
@@ -110,8 +102,7 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
             wd = wrows.data();
         }
         const std::vector<int8_t> wf = pack_pw_panel(wd, C, K, nsteps);
-        std::vector<int32_t> bp(cw, 0);
-        for (int c = 0; c < C; c++) bp[c] = b ? ((const int32_t*)b->data.data())[c] : 0;
+        const std::vector<int32_t> bp = padded_bias(b ? (const int32_t*)b->data.data() : nullptr, C, cw);
         int8_t* d0; int32_t* d1;
         if (upload(g, wf, &d0) || upload(g, bp, &d1) || upload_rq(g, rq, cw, &a.wscale, &a.rq)) return -1;
         a.wf = d0; a.bias = d1;
@@ -144,13 +135,8 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
         HTensor* db = tl.in.size() > 2 ? &g->tensors[tl.in[2]] : nullptr;
         if (dwt.elems() != (size_t)C * 9 || (db && db->elems() < (size_t)C)) return 0;
         const RqFold rq = fold_requant(conv_mode(q, g->formula_batch ? g->formula_batch : mid.n, C, C), q.activation, mid.scales[0], y.scales[0], dwt, C);
-        const int8_t* wd = (const int8_t*)dwt.data.data();
-        std::vector<int8_t> wp((size_t)3 * cw * 4, 0);
-        for (int c = 0; c < C; c++)
-            for (int r = 0; r < 3; r++)
-                for (int kx = 0; kx < 3; kx++) wp[((size_t)r * cw + c) * 4 + kx] = wd[(size_t)c * 9 + r * 3 + kx];
-        std::vector<int32_t> bp(cw, 0);
-        for (int c = 0; c < C; c++) bp[c] = db ? ((const int32_t*)db->data.data())[c] : 0;
+        const std::vector<int8_t> wp = pack_dw3x3((const int8_t*)dwt.data.data(), C, cw);
+        const std::vector<int32_t> bp = padded_bias(db ? (const int32_t*)db->data.data() : nullptr, C, cw);
         int8_t* d0; int32_t* d1;
         if (upload(g, wp, &d0) || upload(g, bp, &d1) || upload_rq(g, rq, cw, &a.dw_wscale, &a.d_rq)) return -1;
         a.dw_w = d0; a.dw_bias = d1;
@@ -217,8 +203,8 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
         }
     }
     if (cfgs.empty()) return 0;
-    Step& sa = g->steps[s0];
-    Step& sb = g->steps[s0 + 1];
+    const Step& sa = pa.step;
+    const Step& sb = pb.step;
     const bool autotune = autotune_enabled() && sa.macs >= 4e6;
     // fused by construction (no race): a link of a LATENCY chain only -- batch 1.  Everything batched keeps the race against the two-launch
     // plan below (batch 8 at 56x56 or batch 16 at 19x19 are throughput launches; round 6's first evidence pass showed what the
@@ -266,7 +252,7 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
     if (!fuse) return 0;
     const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[best].th, cfgs[best].tw, cfgs[best].sl) : a;
     const int threads = cfgs[best].threads;
-    Step st;
+    Step& st = *fused;
     st.node = sa.node + "+" + sb.node;
     char nm[48];
     if (tmode == 1) snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d%s>", prod == 1 ? "firstdw" : "pwdw", a.S, v.TH, v.TW, threads, v.sl == 4 ? ",c64" : v.sl == 2 ? ",c32" : "");
@@ -278,23 +264,21 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, size_t s
     if (prod == 1 && tmode == 1) {       // the first layer pair: reads the graph input, writes the depthwise output, nothing else (run_steps: wrap)
         st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
     }
-    g->steps.resize(s0);
-    g->steps.push_back(st);
     g->fused_away[pw.out[0]] = 1;
-    return 0;
+    return 1;
 }
 
 // ---- depthwise 3x3 (stride 1) + the pointwise conv that consumes it in one launch: dwpw.hip ------------------------------------
-// Called with the pair planned as two steps at s0, s0 + 1 (the depthwise step, then whichever GEMM-family member the pointwise race
-// chose).  Large batches only: at batch 1 the pointwise conv pairs with the depthwise BEHIND it instead (pwdw.hip), which this
+// Called with the pair planned as `pd` (the depthwise launch) and `pc` (whichever GEMM-family member the pointwise race chose).
+// Large batches only: at batch 1 the pointwise conv pairs with the depthwise BEHIND it instead (pwdw.hip), which this
 // fusion would take away.  TAMD_FUSE_DWPW=0 never, =2 always (tests); default: the faster of the two by plan-time timing.
-int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, size_t s0)
+int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& pd, const Planned& pc, Step* fused)
 {
     const char* env = getenv("TAMD_FUSE_DWPW");
     const int fmode = env ? atoi(env) : 1;
-    if (!fmode || !g_last_dw_valid || !g_last_gemm_valid || !dwpw_applicable(g_last_dw, g_last_gemm)) return 0;
-    const DwArgs& d = g_last_dw;
-    const ConvArgs& c = g_last_gemm;
+    if (!fmode || pd.kind != Planned::DW3X3 || pc.kind != Planned::GEMM || pc.elt_tail || !dwpw_applicable(pd.dw, pc.gemm)) return 0;
+    const DwArgs& d = pd.dw;
+    const ConvArgs& c = pc.gemm;
     if (fmode != 2 && (long)d.N * d.OH * d.OW < 4096) return 0;
     const HTensor& w = g->tensors[pw.in[1]];
     std::vector<int8_t> wp(dwpw_packed_bytes(c.cout, c.cin));
@@ -307,27 +291,25 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, size_t s0)
     a.y = c.y;
     a.N = d.N; a.H = d.H; a.W = d.W; a.C = d.C; a.cs_in = d.cs_in; a.cw = d.cw; a.OH = d.OH; a.OW = d.OW; a.PH = d.PH; a.PW = d.PW;
     a.cout = c.cout; a.ldc = c.ldc; a.c_off = c.c_off; a.c_limit = c.c_limit;
-    Step& sa = g->steps[s0];
-    Step& sb = g->steps[s0 + 1];
+    const Step& sa = pd.step;
+    const Step& sb = pc.step;
     bool fuse = fmode == 2;
     if (fmode != 2) {
         char ckey[256];
         snprintf(ckey, sizeof(ckey), "dwpw|%s|n%d %dx%d c%d>%d", sa.node.c_str(), d.N, d.OH, d.OW, d.C, c.cout);
-        const RaceCand fused{"1", [a](hipStream_t s) { return launch_dwpw(a, s); }, "dwpw_i8"};
-        const int w = plan_race(g, sa.node, {two_launches("0", sa, sb), fused}, ckey, 0.97f, autotune_enabled());
+        const RaceCand one{"1", [a](hipStream_t s) { return launch_dwpw(a, s); }, "dwpw_i8"};
+        const int w = plan_race(g, sa.node, {two_launches("0", sa, sb), one}, ckey, 0.97f, autotune_enabled());
         if (w < 0) return -1;
         fuse = w == 1;
     }
     if (!fuse) return 0;
-    Step st;
+    Step& st = *fused;
     st.node = sa.node + "+" + sb.node;
     st.kernel = "dwpw_i8";
     st.macs = sa.macs + sb.macs;
     st.bytes = sa.bytes + sb.bytes;      // SURVEY 8(d) accounting, per layer: the intermediate tensor still counts as algorithmic bytes
     st.fn = [a](hipStream_t s) { return launch_dwpw(a, s); };
     st.rd.push_back(access_of(g->tensors[dw.in[0]])); st.wr.push_back(access_of(g->tensors[pw.out[0]])); st.deps = true;
-    g->steps.resize(s0);
-    g->steps.push_back(st);
     g->fused_away[dw.out[0]] = 1;
     return 1;
 }

@@ -546,60 +546,14 @@ static int plan_fc_u8(tamd_graph* g, HNode& n)
 
 int plan_u8(tamd_graph* g)
 {
-    for (auto& t : g->tensors) {
-        if (t.ttype == TAMD_TT_CONST) continue;
-        nhwc_geom(t);
-        t.nchw_raw = true;      // dense NCHW bytes: read_tensor / IO copy them as they are
-        t.cs = 0; t.c_off = 0;
-    }
-    std::vector<int> alias_of(g->tensors.size(), -1);
-    for (auto& n : g->nodes)
-        if (n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) alias_of[n.out[0]] = n.in[0];   // dense NCHW: views
-    for (auto& io : g->inputs) {
-        HTensor& t = g->tensors[io.tensor];
-        io.bytes = t.elems();
-        if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
-        t.dptr = io.stage;
-    }
-    // concat-by-offset: when an input carries the concat output's (scale, zero point) the reference's
-    // per-element rescale roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv /
-    // relu / upsample whose only consumer is that concat writes its channels straight into the concat output
-    std::vector<int> view_of(g->tensors.size(), -1), view_off(g->tensors.size(), 0);
-    for (auto& n : g->nodes) {
-        if (n.op != TAMD_OP_CONCAT) continue;
-        HTensor& y = g->tensors[n.out[0]];
-        const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
-        int off = 0;
-        for (int i : n.in) {
-            HTensor& xi = g->tensors[i];
-            bool ok = ax == 1 && xi.ttype == TAMD_TT_VAR && count_consumers(g, i) == 1 && alias_of[i] < 0 && view_of[i] < 0
-                      && !xi.scales.empty() && !y.scales.empty() && xi.scales[0] == y.scales[0]
-                      && (xi.zps.empty() ? 0 : xi.zps[0]) == (y.zps.empty() ? 0 : y.zps[0]);
-            if (ok) {
-                ok = false;
-                for (auto& pn : g->nodes)
-                    if (!pn.out.empty() && pn.out[0] == i) ok = pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE;
-            }
-            if (ok) { view_of[i] = n.out[0]; view_off[i] = off; }
-            off += xi.c;
-        }
-    }
-    for (size_t i = 0; i < g->tensors.size(); i++) {
-        HTensor& t = g->tensors[i];
-        if (t.ttype == TAMD_TT_CONST || t.dptr || alias_of[i] >= 0 || view_of[i] >= 0) continue;
-        if (dev_alloc(g, &t.dptr, t.elems(), true)) return -1;
-    }
-    for (size_t i = 0; i < g->tensors.size(); i++)
-        if (view_of[i] >= 0) {
-            HTensor& t = g->tensors[i];
-            HTensor& o = g->tensors[view_of[i]];
-            if (!o.dptr) { set_error("concat of concat views is not supported"); return -1; }
-            t.dptr = o.dptr; t.is_view = true; t.c_off = view_off[i]; t.cs = o.c;      // cs: channels of the enclosing buffer
-        }
-    for (int pass = 0; pass < 4; pass++)
-        for (size_t i = 0; i < g->tensors.size(); i++)
-            if (alias_of[i] >= 0) g->tensors[i].dptr = g->tensors[alias_of[i]].dptr;
+    // concat-by-offset: when an input carries the concat output's (scale, zero point) the reference's per-element rescale
+    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample whose only
+    // consumer is that concat writes in place
+    if (plan_nchw_buffers(g, 1, [](const HNode& pn, const HTensor& xi, const HTensor& y) {
+            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE) && !xi.scales.empty() && !y.scales.empty()
+                   && xi.scales[0] == y.scales[0] && (xi.zps.empty() ? 0 : xi.zps[0]) == (y.zps.empty() ? 0 : y.zps[0]);
+        }))
+        return -1;
 
     // conv -> ReLU / leaky ReLU fusion (YOLOv3-tiny: 11 of them): the ReLU node is applied to the conv's own uint8
     // result in the conv epilogue when nothing else reads that result
@@ -851,13 +805,7 @@ int plan_u8(tamd_graph* g)
             return -1;
         }
     }
-    for (auto& io : g->outputs) {
-        HTensor& t = g->tensors[io.tensor];
-        io.bytes = t.elems();
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
-        io.stage = t.dptr;
-    }
-    return 0;
+    return plan_nchw_outputs(g, 1);
 }
 
 }  // namespace tamd
