@@ -14,6 +14,7 @@
 namespace tamd {
 
 void set_error(const char* fmt, ...);
+static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 
 struct HTensor {               // host IR tensor == the parts of struct tensor the backend reads
     int dtype = 0, ttype = TAMD_TT_VAR;
@@ -82,6 +83,12 @@ inline bool step_conflict(const Step& a, const Step& b)          // RAW, WAR or 
     for (auto& w : a.wr) { for (auto& x : b.wr) if (access_overlap(w, x)) return true; for (auto& x : b.rd) if (access_overlap(w, x)) return true; }
     for (auto& r : a.rd) for (auto& x : b.wr) if (access_overlap(r, x)) return true;
     return false;
+}
+inline Step make_step(const std::string& node, const std::string& kernel, double macs, double bytes, std::function<hipError_t(hipStream_t)> fn)
+{
+    Step st;
+    st.node = node; st.kernel = kernel; st.macs = macs; st.bytes = bytes; st.fn = std::move(fn);
+    return st;
 }
 inline Access access_of(const HTensor& t)                         // dense tensor, or the channel slice of the concat buffer it lives in
 {
@@ -231,6 +238,14 @@ int count_consumers(const tamd_graph* g, int tensor);
 // inputs and tensors, views for Dropout / Flatten / Reshape and for channel-concat inputs that `in_place` allows; graph outputs
 int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place);
 int plan_nchw_outputs(tamd_graph* g, size_t esz);
+// output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
+inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
+// .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of
+// dense `dims`; -1 and the error "<what> <node>: bad axis" when it names no dimension
+struct AxisSplit { int axis = 0, outer = 1, on = 0, inner = 1; };
+int axis_split(const std::vector<int>& dims, int axis, const char* what, const std::string& node, AxisSplit* s);
+// [Kpad] packed tap table of a group-1 convolution, k = (c, ky, kx): (c*H*W + ky*DH*W + kx*DW) | kx*DW << 24 | ky*DH << 28; padding 0
+std::vector<unsigned> conv_tap_table(int K, int Kpad, int H, int W, int KH, int KW, int DH, int DW);
 int priorbox_count(const tamd_priorbox_param& p);
 void priorbox_eval(const tamd_priorbox_param& p, int feat_h, int feat_w, int data_h, int data_w, std::vector<float>* out);
 void priorbox_quant_u8(const std::vector<float>& f, float scale, int zp, std::vector<uint8_t>* q);
@@ -246,6 +261,38 @@ int upload(tamd_graph* g, const std::vector<T>& host, T** dev)
     HIPCHK(hipMemcpyAsync(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));   // own stream only
     HIPCHK(hipStreamSynchronize(g->stream));
     *dev = (T*)p;
+    return 0;
+}
+
+// the first n elements of a bias tensor on the device; no tensor: *dev stays null
+template <typename T>
+int upload_bias(tamd_graph* g, const HTensor* b, int n, const T** dev)
+{
+    if (!b) return 0;
+    std::vector<T> hb((const T*)b->data.data(), (const T*)b->data.data() + n);
+    T* d = nullptr;
+    if (upload(g, hb, &d)) return -1;
+    *dev = d;
+    return 0;
+}
+
+// the constant operands of conv_f32_mfma for the geometry in `a`: picks the tile configuration (a.cfg), uploads the weights in its
+// layout -- [cout tile of BM][stage of 32 k][group][ (k%G)*BM + c ], G = 64 / BM k rows per 64-float group, zero padded -- and
+// the tap table (a.w, a.klut).  wk(co, k): weight k of output channel co as float
+template <typename F>
+int conv_f32_mfma_operands(tamd_graph* g, F32ConvArgs& a, int KH, int KW, int DH, int DW, F wk)
+{
+    a.cfg = conv_f32_mfma_pick(a);
+    const int BM = conv_f32_mfma_bm(a.cfg), ntile = (a.cout + BM - 1) / BM, nstage = a.Kpad / 32, G = 64 / BM, NIg = 32 / G;
+    std::vector<float> wf((size_t)ntile * nstage * 32 * BM, 0.f);
+    for (int co = 0; co < a.cout; co++)
+        for (int k = 0; k < a.K; k++) {
+            const int r = k & 31;
+            wf[(((size_t)(co / BM) * nstage + (k >> 5)) * NIg + r / G) * 64 + (r % G) * BM + co % BM] = wk(co, k);
+        }
+    float* dwf = nullptr; unsigned* dlut = nullptr;
+    if (upload(g, wf, &dwf) || upload(g, conv_tap_table(a.K, a.Kpad, a.H, a.W, KH, KW, DH, DW), &dlut)) return -1;
+    a.w = dwf; a.klut = dlut;
     return 0;
 }
 

@@ -14,52 +14,29 @@
 
 namespace tamd {
 
-static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-
 // conv (group 1) or FC as [cout] x [pixels] x [K] GEMM on the matrix cores
 static int plan_gemm_f32(tamd_graph* g, HNode& n, const float* xdev, int N, int C, int H, int W, int OH, int OW, int cout,
                          int KH, int KW, int SH, int SW, int PH, int PW, int DH, int DW, int act, float* ydev, int oimg, int oc0)
 {
     HTensor& w = g->tensors[n.in[1]];
     HTensor* b = n.in.size() > 2 ? &g->tensors[n.in[2]] : nullptr;
-    const int K = C * KH * KW, Kpad = rup(K, 32), nstage = Kpad / 32;
+    const int K = C * KH * KW, Kpad = rup(K, 32);
     if (w.dtype != TAMD_DT_FP32 || (size_t)cout * K * 4 != w.data.size()) { set_error("%s: fp32 weight size mismatch", n.name.c_str()); return -1; }
     if ((KH - 1) * DH > 15 || (KW - 1) * DW > 15 || (size_t)C * H * W >= (1u << 24)) { set_error("%s: kernel extent / image size outside the packed tap table", n.name.c_str()); return -1; }
     F32ConvArgs a{};
     a.N = N; a.C = C; a.H = H; a.W = W; a.OH = OH; a.OW = OW; a.cout = cout; a.K = K; a.Kpad = Kpad;
     a.SH = SH; a.SW = SW; a.PH = PH; a.PW = PW;
     a.tail_split = 0;
-    a.cfg = conv_f32_mfma_pick(a);
-    const int BM = conv_f32_mfma_bm(a.cfg), ntile = (cout + BM - 1) / BM, G = 64 / BM, NIg = 32 / G;
     const float* wsrc = (const float*)w.data.data();
-    std::vector<float> wf((size_t)ntile * nstage * 32 * BM, 0.f);
-    for (int co = 0; co < cout; co++)
-        for (int k = 0; k < K; k++) {
-            const int r = k & 31;
-            wf[(((size_t)(co / BM) * nstage + (k >> 5)) * NIg + r / G) * 64 + (r % G) * BM + co % BM] = wsrc[(size_t)co * K + k];
-        }
-    std::vector<unsigned> lut(Kpad, 0u);
-    for (int k = 0; k < K; k++) {
-        const int kx = k % KW, ky = (k / KW) % KH, c = k / (KW * KH);
-        lut[k] = (unsigned)(c * H * W + ky * DH * W + kx * DW) | (unsigned)(kx * DW) << 24 | (unsigned)(ky * DH) << 28;
-    }
-    float* dwf = nullptr; unsigned* dlut = nullptr;
-    if (upload(g, wf, &dwf) || upload(g, lut, &dlut)) return -1;
-    if (b) {
-        if (b->dtype != TAMD_DT_FP32) { set_error("%s: fp32 bias expected", n.name.c_str()); return -1; }
-        std::vector<float> hb((const float*)b->data.data(), (const float*)b->data.data() + cout);
-        float* d = nullptr;
-        if (upload(g, hb, &d)) return -1;
-        a.bias_f32 = d;
-    }
+    if (conv_f32_mfma_operands(g, a, KH, KW, DH, DW, [&](int co, int k) { return wsrc[(size_t)co * K + k]; })) return -1;
+    if (b && b->dtype != TAMD_DT_FP32) { set_error("%s: fp32 bias expected", n.name.c_str()); return -1; }
+    if (upload_bias(g, b, cout, &a.bias_f32)) return -1;
     if (!g->zero_page) { if (dev_alloc(g, &g->zero_page, 256, true)) return -1; }
-    a.x = xdev; a.w = dwf; a.klut = dlut; a.zeros = (const float*)g->zero_page; a.out_f32 = ydev;
+    a.x = xdev; a.zeros = (const float*)g->zero_page; a.out_f32 = ydev;
     a.out_img = oimg; a.out_c0 = oc0; a.act = act; a.out_scale = 1.f;
-    Step st; st.node = n.name; st.kernel = conv_f32_mfma_kernel_name(a);
-    st.macs = (double)N * OH * OW * cout * K;
-    st.bytes = 4.0 * ((double)N * C * H * W + (double)N * cout * OH * OW + (double)cout * K);
-    st.fn = [a](hipStream_t s) { return launch_conv_f32_mfma(a, s); };
-    g->steps.push_back(st);
+    g->steps.push_back(make_step(n.name, conv_f32_mfma_kernel_name(a), (double)N * OH * OW * cout * K,
+                                 4.0 * ((double)N * C * H * W + (double)N * cout * OH * OW + (double)cout * K),
+                                 [a](hipStream_t s) { return launch_conv_f32_mfma(a, s); }));
     return 0;
 }
 
@@ -151,8 +128,6 @@ int plan_f32(tamd_graph* g)
             return pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_RELU6 || pn.op == TAMD_OP_UPSAMPLE;
         }))
         return -1;
-    // output placement of a tensor: elements per image of the buffer it lives in, first channel
-    auto out_img = [](const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; };
 
     for (auto& n : g->nodes) {
         if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) continue;
@@ -163,29 +138,22 @@ int plan_f32(tamd_graph* g)
             const tamd_conv_param& p = n.p.conv;
             if (p.group == 1) {
                 if (plan_gemm_f32(g, n, (const float*)x.dptr, x.n, x.c, x.h, x.w, y.h, y.w, y.c, p.kernel_h, p.kernel_w, p.stride_h,
-                                  p.stride_w, p.pad_h0, p.pad_w0, p.dilation_h, p.dilation_w, p.activation, (float*)y.dptr, out_img(y), y.c_off)) return -1;
-                if (plan_winograd_f32(g, n, x, y, out_img(y))) return -1;
+                                  p.stride_w, p.pad_h0, p.pad_w0, p.dilation_h, p.dilation_w, p.activation, (float*)y.dptr, nchw_out_img(y), y.c_off)) return -1;
+                if (plan_winograd_f32(g, n, x, y, nchw_out_img(y))) return -1;
             } else {
                 HTensor& w = g->tensors[n.in[1]];
                 HTensor* b = n.in.size() > 2 ? &g->tensors[n.in[2]] : nullptr;
                 std::vector<float> hw((const float*)w.data.data(), (const float*)w.data.data() + w.data.size() / 4);
-                float* dw = nullptr; float* db = nullptr;
-                if (upload(g, hw, &dw)) return -1;
-                if (b) {
-                    std::vector<float> hb((const float*)b->data.data(), (const float*)b->data.data() + y.c);
-                    if (upload(g, hb, &db)) return -1;
-                }
+                float* dw = nullptr; const float* db = nullptr;
+                if (upload(g, hw, &dw) || upload_bias(g, b, y.c, &db)) return -1;
                 F32DirectArgs a{};
                 a.x = (const float*)x.dptr; a.w = dw; a.bias = db; a.y = (float*)y.dptr;
                 a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w; a.cout = y.c;
                 a.KH = p.kernel_h; a.KW = p.kernel_w; a.SH = p.stride_h; a.SW = p.stride_w; a.PH = p.pad_h0; a.PW = p.pad_w0;
                 a.DH = p.dilation_h; a.DW = p.dilation_w; a.group = p.group;
-                a.out_img = out_img(y); a.out_c0 = y.c_off; a.act = p.activation;
-                Step st; st.node = n.name; st.kernel = "conv_f32_direct";
-                st.macs = (double)y.elems() * (x.c / p.group) * p.kernel_h * p.kernel_w;
-                st.bytes = 4.0 * ((double)x.elems() + (double)y.elems());
-                st.fn = [a](hipStream_t s) { return launch_conv_f32_direct(a, s); };
-                g->steps.push_back(st);
+                a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.act = p.activation;
+                g->steps.push_back(make_step(n.name, "conv_f32_direct", (double)y.elems() * (x.c / p.group) * p.kernel_h * p.kernel_w,
+                                             4.0 * ((double)x.elems() + (double)y.elems()), [a](hipStream_t s) { return launch_conv_f32_direct(a, s); }));
             }
             break;
         }
@@ -201,9 +169,8 @@ int plan_f32(tamd_graph* g)
             a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w;
             a.KH = pg.kh; a.KW = pg.kw; a.SH = pg.sh; a.SW = pg.sw; a.PH = pg.ph0; a.PW = pg.pw0;
             a.method = n.p.pool.pool_method; a.caffe_flavor = n.p.pool.caffe_flavor;
-            Step st; st.node = n.name; st.kernel = "pool_f32"; st.bytes = 4.0 * ((double)x.elems() + (double)y.elems());
-            st.fn = [a](hipStream_t s) { return launch_pool_f32(a, s); };
-            g->steps.push_back(st);
+            g->steps.push_back(make_step(n.name, "pool_f32", 0, 4.0 * ((double)x.elems() + (double)y.elems()),
+                                         [a](hipStream_t s) { return launch_pool_f32(a, s); }));
             break;
         }
         case TAMD_OP_RELU: case TAMD_OP_RELU6: case TAMD_OP_UPSAMPLE: {
@@ -211,12 +178,11 @@ int plan_f32(tamd_graph* g)
             a.x = (const float*)x.dptr; a.y = (float*)y.dptr;
             a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w;
             a.scale = n.op == TAMD_OP_UPSAMPLE ? (int)n.p.ups.scale : 1;
-            a.out_img = out_img(y); a.out_c0 = y.c_off;
+            a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
             a.slope = n.op == TAMD_OP_RELU ? n.p.relu.negative_slope : 0.f;
             const int mode = n.op == TAMD_OP_RELU ? 0 : (n.op == TAMD_OP_UPSAMPLE ? 2 : 3);
-            Step st; st.node = n.name; st.kernel = mode == 2 ? "upsample_f32" : "relu_f32"; st.bytes = 4.0 * ((double)x.elems() + (double)y.elems());
-            st.fn = [a, mode](hipStream_t s) { return launch_map_f32(a, mode, s); };
-            g->steps.push_back(st);
+            g->steps.push_back(make_step(n.name, mode == 2 ? "upsample_f32" : "relu_f32", 0, 4.0 * ((double)x.elems() + (double)y.elems()),
+                                         [a, mode](hipStream_t s) { return launch_map_f32(a, mode, s); }));
             break;
         }
         case TAMD_OP_PRIORBOX: {          // shapes-only node: evaluated here, once (graph_infer.hip priorbox_eval); no launch at run
@@ -230,12 +196,10 @@ int plan_f32(tamd_graph* g)
             break;
         }
         case TAMD_OP_CONCAT: {
-            int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
-            if (ax < 0 || ax >= (int)y.dims.size()) { set_error("concat %s: bad axis", n.name.c_str()); return -1; }
             // dense tensors: any axis is a channel concat of the [outer][dims[ax]][1][inner] view
-            int outer = 1, inner = 1;
-            for (int d = 0; d < ax; d++) outer *= y.dims[d];
-            for (size_t d = ax + 1; d < y.dims.size(); d++) inner *= y.dims[d];
+            AxisSplit sp;
+            if (axis_split(y.dims, n.p.concat.axis, "concat", n.name, &sp)) return -1;
+            const int ax = sp.axis, outer = sp.outer, inner = sp.inner;
             bool all_const = true;
             for (int i : n.in) all_const &= g->tensors[i].prerun_const;
             int off = 0;
@@ -246,9 +210,8 @@ int plan_f32(tamd_graph* g)
                 a.x = (const float*)xi.dptr; a.y = (float*)y.dptr;
                 a.N = outer; a.C = xi.dims[ax]; a.H = 1; a.W = inner; a.scale = 1;
                 a.out_img = y.dims[ax] * inner; a.out_c0 = off;
-                Step st; st.node = n.name; st.kernel = "concat_f32"; st.bytes = 8.0 * xi.elems();
+                Step st = make_step(n.name, "concat_f32", 0, 8.0 * xi.elems(), [a](hipStream_t s) { return launch_map_f32(a, 1, s); });
                 st.once = all_const;
-                st.fn = [a](hipStream_t s) { return launch_map_f32(a, 1, s); };
                 g->steps.push_back(st);
                 off += xi.dims[ax];
             }
@@ -261,22 +224,17 @@ int plan_f32(tamd_graph* g)
             if (x.dims != xb.dims || (type != 0 && type != 2 && type != 4 && type != 6)) { set_error("eltwise %s: broadcast / type %d unsupported", n.name.c_str(), type); return -1; }
             const float* pa = (const float*)x.dptr; const float* pb = (const float*)xb.dptr; float* py = (float*)y.dptr;
             const size_t cnt = x.elems();
-            Step st; st.node = n.name; st.kernel = "eltwise_f32"; st.bytes = 12.0 * cnt;
-            st.fn = [pa, pb, py, cnt, type](hipStream_t s) { return launch_eltwise_f32(pa, pb, py, cnt, type, s); };
-            g->steps.push_back(st);
+            g->steps.push_back(make_step(n.name, "eltwise_f32", 0, 12.0 * cnt,
+                                         [pa, pb, py, cnt, type](hipStream_t s) { return launch_eltwise_f32(pa, pb, py, cnt, type, s); }));
             break;
         }
         case TAMD_OP_SOFTMAX: {
             const float* px = (const float*)x.dptr; float* py = (float*)y.dptr;
-            int ax = n.p.softmax.axis < 0 ? n.p.softmax.axis + (int)x.dims.size() : n.p.softmax.axis;
-            if (ax < 0 || ax >= (int)x.dims.size()) { set_error("softmax %s: bad axis", n.name.c_str()); return -1; }
-            int N = 1, inner = 1;
-            const int C = x.dims[ax];
-            for (int i = 0; i < ax; i++) N *= x.dims[i];
-            for (size_t i = ax + 1; i < x.dims.size(); i++) inner *= x.dims[i];
-            Step st; st.node = n.name; st.kernel = "softmax_f32"; st.bytes = 8.0 * x.elems();
-            st.fn = [px, py, N, C, inner](hipStream_t s) { return launch_softmax_f32(px, py, N, C, inner, s); };
-            g->steps.push_back(st);
+            AxisSplit sp;
+            if (axis_split(x.dims, n.p.softmax.axis, "softmax", n.name, &sp)) return -1;
+            const int N = sp.outer, C = sp.on, inner = sp.inner;
+            g->steps.push_back(make_step(n.name, "softmax_f32", 0, 8.0 * x.elems(),
+                                         [px, py, N, C, inner](hipStream_t s) { return launch_softmax_f32(px, py, N, C, inner, s); }));
             break;
         }
         default:

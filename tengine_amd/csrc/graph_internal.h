@@ -19,7 +19,6 @@ namespace tamd {
 extern std::mutex g_capture_mutex;
 const char* last_error();                    // the calling thread's error string (set_error)
 
-static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 static inline int esize(int dt) { return (dt == TAMD_DT_FP32 || dt == TAMD_DT_INT32) ? 4 : (dt == TAMD_DT_FP16 ? 2 : 1); }
 static inline int cdiv_c(int a, int b) { return a / b; }  // C semantics (truncation), as the reference
 

@@ -138,6 +138,27 @@ int count_consumers(const tamd_graph* g, int tensor)
     return c;
 }
 
+int axis_split(const std::vector<int>& dims, int axis, const char* what, const std::string& node, AxisSplit* s)
+{
+    const int ax = axis < 0 ? axis + (int)dims.size() : axis;
+    if (ax < 0 || ax >= (int)dims.size()) { set_error("%s %s: bad axis", what, node.c_str()); return -1; }
+    *s = AxisSplit{};
+    s->axis = ax; s->on = dims[ax];
+    for (int d = 0; d < ax; d++) s->outer *= dims[d];
+    for (size_t d = ax + 1; d < dims.size(); d++) s->inner *= dims[d];
+    return 0;
+}
+
+std::vector<unsigned> conv_tap_table(int K, int Kpad, int H, int W, int KH, int KW, int DH, int DW)
+{
+    std::vector<unsigned> lut(Kpad, 0u);
+    for (int k = 0; k < K; k++) {
+        const int kx = k % KW, ky = (k / KW) % KH, c = k / (KW * KH);
+        lut[k] = (unsigned)(c * H * W + ky * DH * W + kx * DW) | (unsigned)(kx * DW) << 24 | (unsigned)(ky * DH) << 28;
+    }
+    return lut;
+}
+
 
 // which formula the reference's score() selection lands on (conv_hcl_x86.c:351-371,
 // conv_dw_hcl_x86.c:508-543, conv_ref.c:197-200)
