@@ -291,11 +291,17 @@ __global__ __launch_bounds__(512) void dwpw_i8_kernel(DwPwArgs a)
 // depthwise 3x3 stride 1 (any padding the map allows) feeding a pointwise 1x1 stride-1 convolution with no padding; output channels
 // in whole 64-channel wave slices up to 512, destination on 16-channel granularity (16-byte stores); OW <= 16 (one tile row spans the map);
 // at most 2048 (padded) channels: their constants live in LDS (dwpw_lds_bytes <= 64 KB)
+// the pointwise consumer's shape alone (64-channel tiles, at most 512 channels; map rows of at most 16 pixels; 1x1, stride 1, no pads):
+// the planner asks before it plans the consumer, dwpw_applicable once both launches are planned
+bool dwpw_pw_shape_ok(int cout, int map_w, int KH, int KW, int SH, int SW, bool pads)
+{
+    return cout % 64 == 0 && cout <= 512 && map_w <= 16 && KH == 1 && KW == 1 && SH == 1 && SW == 1 && !pads;
+}
+
 bool dwpw_applicable(const DwArgs& d, const ConvArgs& p)
 {
-    if (d.S != 1 || d.OW > 16 || d.C % 4 != 0 || d.cw < 16 || d.cw % 16 != 0 || d.cw > 2048) return false;
-    if (p.KH != 1 || p.KW != 1 || p.SH != 1 || p.SW != 1 || p.PH != 0 || p.PW != 0 || p.elt.res) return false;
-    if (p.cout % 64 != 0 || p.cout > 512 || p.cin != d.C) return false;
+    if (d.S != 1 || d.C % 4 != 0 || d.cw < 16 || d.cw % 16 != 0 || d.cw > 2048) return false;
+    if (!dwpw_pw_shape_ok(p.cout, d.OW, p.KH, p.KW, p.SH, p.SW, p.PH != 0 || p.PW != 0) || p.elt.res || p.cin != d.C) return false;
     if (((p.c_limit | p.c_off | p.ldc) & 15) != 0 || p.c_limit < p.cout) return false;
     return p.N == d.N && p.H == d.OH && p.W == d.OW;
 }

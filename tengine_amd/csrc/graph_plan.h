@@ -1,4 +1,4 @@
-// What the two units of the int8 planner share (graph_plan.hip, graph_plan_pairs.hip); private.
+// What the three units of the int8 planner share (graph_plan.hip, graph_plan_conv.hip, graph_plan_pairs.hip); private.
 #pragma once
 #include "graph_internal.h"
 #include "epilogue.h"
@@ -16,6 +16,18 @@ std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps);
 
 std::vector<int8_t> pack_dw3x3(const int8_t* wd, int cin, int cw);
 std::vector<int32_t> padded_bias(const int32_t* bd, int n, int padded);
+// a depthwise 3x3, stride 1 or 2, no dilation: what the depthwise kernels take (dwconv.hip; pwdw.hip asks for more on top)
+bool is_dw3x3(const tamd_conv_param& p, int cin, int cout);
+// channels [0, limit) a launch of `cout` channels may store into y: the padding channels of its own buffer, nothing of a neighbour's slice
+inline int store_limit(const HTensor& y, int cout) { return y.is_view ? cout : std::min(rup(cout, 16), y.cs - y.c_off); }
+
+struct FusedElt {            // an eltwise (+ReLU) node folded into the epilogue of the conv that produces its later operand
+    int res_tensor;          // the other eltwise operand
+    int elt_tensor;          // the eltwise node's own output (its scale)
+    int out_tensor;          // where the result is stored: elt_tensor, or the ReLU's output when one follows
+    int type;
+    bool conv_is_first, relu;
+};
 
 // One planned launch, as plan_conv / plan_pool hand it out: the step, which form it took, and that form's kernel arguments for a
 // fuser that folds this launch and its neighbour into one.  The caller pushes either the fused step or the planned ones.
@@ -28,6 +40,10 @@ struct Planned {
     ConvArgs gemm{};
     PoolArgs pool{};
 };
+
+// graph_plan_conv.hip.  One convolution / FC (as_fc) / pooling node as ONE launch, handed out in *out; fz: the eltwise tail it takes
+int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* out);
+int plan_pool(tamd_graph* g, HNode& n, Planned* out);
 
 // graph_plan_pairs.hip.  The fusers: 1 = *fused is the one launch for both, 0 = not fused, -1 = error
 int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod);

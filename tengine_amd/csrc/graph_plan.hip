@@ -1,18 +1,14 @@
-// The int8 planner: device buffers (arena), requantisation folds, plan-time timing, the convolution / pooling planners and plan_i8()
-// itself -- node list -> launch list (NHWC int8).  The pair fusions (pointwise + depthwise, depthwise + pointwise) are in
-// graph_plan_pairs.hip.
+// The int8 planner: device buffers (arena), the layout passes, one function per node kind and plan_i8() itself -- node list ->
+// launch list (NHWC int8).  The convolution / FC / pooling launches are planned in graph_plan_conv.hip, the pair fusions
+// (pointwise + depthwise, depthwise + pointwise) in graph_plan_pairs.hip.
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
 
 #include <stdio.h>
-#include <string.h>
 
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
 
-#include "epilogue.h"
 #include "graph_plan.h"
 
 namespace tamd {
@@ -157,403 +153,6 @@ std::vector<unsigned> conv_tap_table(int K, int Kpad, int H, int W, int KH, int 
         lut[k] = (unsigned)(c * H * W + ky * DH * W + kx * DW) | (unsigned)(kx * DW) << 24 | (unsigned)(ky * DH) << 28;
     }
     return lut;
-}
-
-
-// which formula the reference's score() selection lands on (conv_hcl_x86.c:351-371,
-// conv_dw_hcl_x86.c:508-543, conv_ref.c:197-200)
-int conv_mode(const tamd_conv_param& p, int batch, int cin, int cout)
-{
-    if (p.group == 1) return RQ_CONV_HCL;
-    int cin_g = cin / p.group, cout_g = cout / p.group;
-    if (p.kernel_h == p.kernel_w && batch == 1 && p.group > 1 && cin_g == 1 && cout_g == 1 && p.pad_h0 == p.pad_h1
-        && p.pad_w0 == p.pad_w1 && p.dilation_h == 1 && p.dilation_w == 1 && p.kernel_h == 3
-        && ((p.stride_h == 1 && p.stride_w == 1) || (p.stride_h == 2 && p.stride_w == 2)))
-        return RQ_CONV_HCL;
-    return RQ_CONV_REF;
-}
-
-
-// the reference's three requantisation formulas folded into (m1, m2[c], lo, hi, out_scale) -- epilogue.h.
-// Host float arithmetic here is binary32, unfused (-ffp-contract=off), exactly the reference's expressions.
-RqFold fold_requant(int mode, int act, float in_s, float out_s, const HTensor& w, int cout)
-{
-    RqFold r;
-    r.m2.resize(cout);
-    for (int i = 0; i < cout; i++) r.m2[i] = w.scales.size() == (size_t)cout ? w.scales[i] : w.scales[0];
-    r.m1 = in_s; r.out_scale = out_s; r.lo = -FLT_MAX; r.hi = FLT_MAX;
-    if (mode == RQ_CONV_HCL) {
-        if (act == 0) r.lo = 0.f;
-        if (act > 0) { r.lo = 0.f; r.hi = 6.f; }
-    } else if (mode == RQ_CONV_REF) {
-        r.m1 = 1.0f;
-        for (int i = 0; i < cout; i++) { volatile float d = in_s * r.m2[i]; r.m2[i] = d; }
-        if (act == 1) { r.lo = -1.f; r.hi = 1.f; }
-        else if (act >= 0) { r.lo = 0.f; if (act == 6) r.hi = 6.f; }
-    } else {   // RQ_FC
-        r.m1 = 1.0f;
-        for (int i = 0; i < cout; i++) { volatile float d = in_s * r.m2[i]; volatile float q = d / out_s; r.m2[i] = q; }
-        r.out_scale = 1.0f;
-    }
-    return r;
-}
-
-// RqArgs of epilogue.h for one node: the reference chain's constants (the +-127.49 * out_scale saturation folded into lo / hi)
-// and the fast path's window / multipliers.  Host float arithmetic here is binary32, unfused: q(lo) / q(hi) are the
-// reference's own sat127(round(x / out_scale)) on the clamp bounds.  The fold is used only when every factor is an ordinary
-// normal number (the error bound of epilogue.h assumes no underflow in the chain); otherwise thr = 2 hands every value to the chain.
-static int host_q(float x, float s)
-{
-    volatile float d = x / s;
-    const float r = roundf(d);
-    return r > 127.f ? 127 : (r < -127.f ? -127 : (int)r);
-}
-static RqArgs host_rq(const RqFold& r, int cpad, std::vector<float>* mf, std::vector<float>* m2)
-{
-    RqArgs q{};
-    volatile float lim = 127.49f * r.out_scale;
-    q.m1 = r.m1; q.out_scale = r.out_scale;
-    q.lo = std::max(r.lo, -(float)lim);
-    q.hi = std::min(r.hi, (float)lim);
-    auto ordinary = [](double v) { return std::isfinite(v) && std::fabs(v) >= 1e-30 && std::fabs(v) <= 1e30; };
-    bool ok = ordinary(r.m1) && ordinary(r.out_scale) && r.out_scale > 0.f && r.m1 > 0.f && q.lo <= q.hi;
-    for (float v : r.m2) ok = ok && (v == 0.f || (ordinary(v) && ordinary((double)r.m1 * v) && ordinary((double)r.m1 * v / r.out_scale)));
-    mf->assign(cpad, 0.f);
-    m2->assign(cpad, 1.f);
-    for (size_t c = 0; c < r.m2.size() && c < (size_t)cpad; c++) {
-        (*m2)[c] = r.m2[c];
-        if (ok) (*mf)[c] = (float)((double)r.m1 * (double)r.m2[c] / (double)r.out_scale);
-    }
-    q.thr = ok ? 0x1p-13f : 2.0f;
-    q.ylo = ok ? 128.f + (float)host_q(q.lo, r.out_scale) + 0.25f : 1.25f;
-    q.yhi = ok ? 128.f + (float)host_q(q.hi, r.out_scale) + 0.75f : 255.75f;
-    return q;
-}
-// timing experiments only (tools/exp/xcd_local.sh): TAMD_EXP_PLAIN_KERNELS=1 plans the ordinary (non-coherent) kernel
-// instances under direct dispatch; TAMD_EXP_NOFENCE=1 strips the fences of ordinary launches AND skips the self-check -- the bytes
-// of such a graph are NOT trustworthy (stale L1 lines), only its clock is looked at
-bool exp_plain_kernels() { const char* e = exp_env("TAMD_EXP_PLAIN_KERNELS"); return e && atoi(e) == 1; }
-
-// uploads both per-channel vectors; *wscale = the fast-path multipliers, rq->m2 = the chain's factors
-int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, RqArgs* rq)
-{
-    std::vector<float> mf, m2;
-    *rq = host_rq(r, cpad, &mf, &m2);
-    float *d0, *d1;
-    if (upload(g, mf, &d0) || upload(g, m2, &d1)) return -1;
-    *wscale = d0; rq->m2 = d1;
-    return 0;
-}
-
-// pointwise weight panel in MFMA fragment order: [16-channel slice][64-deep K step][lane = (k block of 16) * 16 + channel][16 B];
-// `wd` = [C][K] int8 rows (1x1 conv: K = cin; first conv: K = cin*KH*KW in OIHW order), zero padded to nsteps * 64
-std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps)
-{
-    const int slices = (C + 15) / 16;
-    std::vector<int8_t> wf((size_t)slices * nsteps * 1024, 0);
-    for (int c = 0; c < C; c++)
-        for (int k = 0; k < K; k++)
-            wf[((size_t)((c >> 4) * nsteps + (k >> 6)) * 64 + ((k >> 4) & 3) * 16 + (c & 15)) * 16 + (k & 15)] = wd[(size_t)c * K + k];
-    return wf;
-}
-
-
-struct FusedElt {            // an eltwise (+ReLU) node folded into the epilogue of the conv that produces its later operand
-    int res_tensor;          // the other eltwise operand
-    int elt_tensor;          // the eltwise node's own output (its scale)
-    int out_tensor;          // where the result is stored: elt_tensor, or the ReLU's output when one follows
-    int type;
-    bool conv_is_first, relu;
-};
-
-// depthwise 3x3 weights as [3 rows][cw] dwords {w[r][0], w[r][1], w[r][2], 0}: one v_dot4 operand per (row, channel)
-std::vector<int8_t> pack_dw3x3(const int8_t* wd, int cin, int cw)
-{
-    std::vector<int8_t> wp((size_t)3 * cw * 4, 0);
-    for (int c = 0; c < cin; c++)
-        for (int r = 0; r < 3; r++)
-            for (int kx = 0; kx < 3; kx++) wp[((size_t)r * cw + c) * 4 + kx] = wd[(size_t)c * 9 + r * 3 + kx];
-    return wp;
-}
-
-// a node's int32 bias, zeros where it has none, in a vector of `padded` entries
-std::vector<int32_t> padded_bias(const int32_t* bd, int n, int padded)
-{
-    std::vector<int32_t> bp(padded, 0);
-    for (int c = 0; c < n; c++) bp[c] = bd ? bd[c] : 0;
-    return bp;
-}
-
-// Plans one convolution / FC node as ONE launch and hands it out in *out; nothing is pushed onto g->steps here.
-static int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& w = g->tensors[n.in[1]];
-    HTensor* b = n.in.size() > 2 ? &g->tensors[n.in[2]] : nullptr;
-    HTensor& y = g->tensors[n.out[0]];
-    if (x.dtype != TAMD_DT_INT8 || w.dtype != TAMD_DT_INT8 || y.dtype != TAMD_DT_INT8) {
-        set_error("conv/fc %s: only int8 is implemented on the device in this round (dtype %d)", n.name.c_str(), x.dtype);
-        return -1;
-    }
-    if (x.scales.empty() || y.scales.empty() || w.scales.empty()) { set_error("%s: missing quant params", n.name.c_str()); return -1; }
-    tamd_conv_param p{};
-    int mode;
-    if (as_fc) {   // FC == "valid" convolution whose kernel covers the whole input map; weight [out][c*h*w]
-        p.kernel_h = x.h; p.kernel_w = x.w; p.stride_h = p.stride_w = 1; p.dilation_h = p.dilation_w = 1;
-        p.group = 1; p.activation = -1; p.input_channel = x.c; p.output_channel = y.c;
-        mode = RQ_FC;
-        if ((size_t)w.elems() != (size_t)y.c * x.c * x.h * x.w) { set_error("fc %s: weight size mismatch", n.name.c_str()); return -1; }
-    } else {
-        p = n.p.conv;
-        mode = conv_mode(p, g->formula_batch ? g->formula_batch : x.n, x.c, y.c);      // (a half of a pair: the whole graph's batch decides, graph.h)
-    }
-    const int cout = y.c, cin = x.c, group = p.group;
-    const int cin_g = cin / group;
-    const RqFold rqf = fold_requant(mode, p.activation, x.scales[0], y.scales[0], w, cout);
-    const std::vector<float>& ws = rqf.m2;     // m2[c]
-    const float in_scale = rqf.m1, out_scale = rqf.out_scale, rq_lo = rqf.lo, rq_hi = rqf.hi;
-    const int8_t* wd = (const int8_t*)w.data.data();
-    const int32_t* bd = b ? (const int32_t*)b->data.data() : nullptr;
-    const int KH = p.kernel_h, KW = p.kernel_w;
-    const double macs = (double)y.n * y.h * y.w * cout * cin_g * KH * KW;
-    const double abytes = (double)x.n * x.h * x.w * cin + (double)y.n * y.h * y.w * cout + (double)cout * cin_g * KH * KW + 4.0 * cout;
-
-    Step& st = out->step;
-    st.node = n.name; st.macs = macs; st.bytes = abytes;
-    out->elt_tail = fz != nullptr;
-    const bool is_dw = (group > 1 && group == cin && cout == cin);
-    if (x.nchw_raw && group == 1 && cin <= 4 && cin * KH * KW <= 224 && cout <= 128
-        && p.dilation_h * (KH - 1) < 256 && p.dilation_w * (KW - 1) < 256) {
-        // ---- first layer from the NCHW graph input on MFMA ----
-        const char* rows_env = tamd_pin("first_rows");                   // 0: always the generic gather kernel (tests; read at every prerun)
-        const int kwp = (rows_env && atoi(rows_env) == 0) ? 0 : conv_first_kwp(cin, KH, KW, p.dilation_w);
-        const int kreal = cin * KH * KW, kp = kwp ? rup(cin * KH * kwp, 32) : rup(kreal, 32), cpad = rup(cout, 32);
-        std::vector<int8_t> wp((size_t)cpad * kp, 0);
-        for (int co = 0; co < cout; co++) {
-            if (!kwp) { memcpy(&wp[(size_t)co * kp], wd + (size_t)co * kreal, kreal); continue; }   // OIHW row as stored
-            for (int r = 0; r < cin * KH; r++)                              // kx padded to kwp: a patch row is kwp consecutive bytes
-                memcpy(&wp[(size_t)co * kp + (size_t)r * kwp], wd + (size_t)co * kreal + (size_t)r * KW, KW);
-        }
-        const std::vector<int32_t> bp = padded_bias(bd, cout, cpad);
-        FirstArgs a{};
-        int8_t* dw_; int32_t* db_;
-        if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cpad, &a.wscale, &a.rq)) return -1;
-        a.x = (const int8_t*)x.dptr; a.w = dw_; a.bias = db_; a.y = (int8_t*)y.dptr;
-        a.N = x.n; a.C = cin; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w; a.cout = cout; a.ldc = y.cs; a.c_off = y.c_off;
-        a.c_limit = y.is_view ? cout : std::min(rup(cout, 16), y.cs - y.c_off);
-        a.KH = KH; a.KW = KW; a.SH = p.stride_h; a.SW = p.stride_w; a.PH = p.pad_h0; a.PW = p.pad_w0;
-        a.DH = p.dilation_h; a.DW = p.dilation_w; a.kp = kp; a.kwp = kwp;
-        st.kernel = "conv_first_i8";
-        st.fn = [a](hipStream_t s) { return launch_conv_first(a, s); };
-        out->kind = Planned::FIRST; out->first = a;
-    } else if (x.nchw_raw || group != 1) {
-        if (!x.nchw_raw && is_dw && KH == 3 && KW == 3 && p.dilation_h == 1 && p.dilation_w == 1 && p.stride_h == p.stride_w
-            && (p.stride_h == 1 || p.stride_h == 2)) {
-            // ---- depthwise 3x3 ----
-            const int cw = rup(cin, 16);
-            const std::vector<int8_t> wp = pack_dw3x3(wd, cin, cw);
-            const std::vector<int32_t> bp = padded_bias(bd, cin, cw);
-            DwArgs a{};
-            int8_t* dw_; int32_t* db_;
-            if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cw, &a.wscale, &a.rq)) return -1;
-            a.x = (const int8_t*)x.dptr + x.c_off; a.w = dw_; a.bias = db_;
-            a.y = (int8_t*)y.dptr;
-            a.N = x.n; a.H = x.h; a.W = x.w; a.C = cin; a.cs_in = x.cs; a.cw = cw; a.OH = y.h; a.OW = y.w;
-            a.ldc = y.cs; a.c_off = y.c_off; a.S = p.stride_h; a.PH = p.pad_h0; a.PW = p.pad_w0;
-            st.kernel = dwconv3x3_kernel_name(a);
-            st.fn = [a](hipStream_t s) { return launch_dwconv3x3(a, s); };
-            out->kind = Planned::DW3X3; out->dw = a;
-        } else {
-            // ---- generic direct (first layer from NCHW, grouped, non-3x3 depthwise) ----
-            std::vector<int8_t> wv(wd, wd + w.elems());
-            DirectArgs a{};
-            int8_t* dw_; int32_t* db_ = nullptr;
-            if (upload(g, wv, &dw_) || upload_rq(g, rqf, rup(cout, 4), &a.wscale, &a.rq)) return -1;
-            if (bd) { std::vector<int32_t> bv(bd, bd + cout); if (upload(g, bv, &db_)) return -1; }
-            a.x = (const int8_t*)x.dptr + (x.nchw_raw ? 0 : x.c_off); a.w = dw_; a.bias = db_;
-            a.y = (int8_t*)y.dptr;
-            a.N = x.n; a.C = cin; a.H = x.h; a.W = x.w; a.cs_in = x.nchw_raw ? 0 : x.cs;
-            a.OH = y.h; a.OW = y.w; a.cout = cout; a.ldc = y.cs; a.c_off = y.c_off;
-            a.KH = KH; a.KW = KW; a.SH = p.stride_h; a.SW = p.stride_w; a.PH = p.pad_h0; a.PW = p.pad_w0;
-            a.DH = p.dilation_h; a.DW = p.dilation_w; a.group = group;
-            st.kernel = "conv_direct_i8";
-            st.fn = [a](hipStream_t s) { return launch_conv_direct(a, s); };
-            out->kind = Planned::DIRECT;
-        }
-    } else {
-        // ---- implicit GEMM on MFMA ----
-        const int ckp = rup(cin, 16);
-        const int ktot = KH * KW * ckp;
-        const int kpad = rup(ktot, 64);
-        const int cout_pad = rup(cout, 128);
-        if (KH * KW > 128) { set_error("conv %s: kernel %dx%d too large", n.name.c_str(), KH, KW); return -1; }
-        std::vector<int8_t> wp((size_t)cout_pad * kpad + 256, 0);      // + tail: deep-K stages may read past the last row
-        for (int co = 0; co < cout; co++)
-            for (int ci = 0; ci < cin; ci++)
-                for (int ky = 0; ky < KH; ky++)
-                    for (int kx = 0; kx < KW; kx++)
-                        wp[(size_t)co * kpad + (size_t)(ky * KW + kx) * ckp + ci] = wd[(((size_t)co * cin + ci) * KH + ky) * KW + kx];
-        const std::vector<int32_t> bp = padded_bias(bd, cout, cout_pad);
-        ConvArgs a{};
-        int8_t* dw_; int32_t* db_;
-        if (upload(g, wp, &dw_) || upload(g, bp, &db_) || upload_rq(g, rqf, cout_pad, &a.wscale, &a.rq)) return -1;
-        a.x = (const int8_t*)x.dptr + x.c_off; a.w = dw_; a.bias = db_; a.y = (int8_t*)y.dptr;
-        a.N = x.n; a.H = x.h; a.W = x.w; a.cs_in = x.cs; a.ckp = ckp; a.OH = y.h; a.OW = y.w; a.cout = cout;
-        a.ldc = y.cs; a.c_off = y.c_off; a.c_limit = y.is_view ? cout : std::min(rup(cout, 16), y.cs - y.c_off);
-        a.KH = KH; a.KW = KW; a.SH = p.stride_h; a.SW = p.stride_w; a.PH = p.pad_h0; a.PW = p.pad_w0;
-        a.DH = p.dilation_h; a.DW = p.dilation_w; a.cin = cin; a.ktot = ktot; a.kpad = kpad;
-        if (!g->zero_page) { if (dev_alloc(g, &g->zero_page, 256, true)) return -1; }
-        a.zeros = (const int8_t*)g->zero_page;
-        a.mg_ohw = ((1ull << 40) + (unsigned)(y.h * y.w) - 1) / (unsigned)(y.h * y.w);
-        a.mg_ow = ((1ull << 40) + (unsigned)y.w - 1) / (unsigned)y.w;
-        a.M = y.n * y.h * y.w;
-        a.cfg = -1;
-        out->kind = Planned::GEMM; out->gemm = a;       // (as it is without the eltwise tail: what a fuser reads)
-        if (fz) {      // conv -> eltwise (-> relu) in one launch: the conv's own int8 rounding is kept, see epilogue.h
-            HTensor& r = g->tensors[fz->res_tensor];
-            HTensor& o = g->tensors[fz->out_tensor];
-            a.elt.res = (const int8_t*)r.dptr; a.elt.res_ldc = r.cs; a.elt.res_c_off = r.c_off;
-            a.elt.type = fz->type; a.elt.conv_is_first = fz->conv_is_first ? 1 : 0;
-            a.elt.s_conv = y.scales[0]; a.elt.s_res = r.scales[0];
-            a.elt.out_scale = g->tensors[fz->elt_tensor].scales[0];
-            a.elt.relu = fz->relu ? (o.scales[0] == a.elt.out_scale ? 2 : 1) : 0; a.elt.relu_out_scale = o.scales[0];
-            {   // SUM (+ scale-keeping ReLU): the two-fma tail of epilogue.h when its error bound holds (S = mc + mr <= 2)
-                const double sc = a.elt.s_conv, sr = a.elt.s_res, so = a.elt.out_scale;
-                auto ordinary = [](double v) { return std::isfinite(v) && v >= 1e-30 && v <= 1e30; };
-                const bool ok = fz->type == 2 && a.elt.relu != 1 && ordinary(sc) && ordinary(sr) && ordinary(so) && (sc + sr) / so <= 2.0;
-                a.elt.thr = 0.f;
-                if (ok && !(tamd_pin("elt_fold") && atoi(tamd_pin("elt_fold")) == 0)) {
-                    const float e = 0x1p-13f;
-                    a.elt.mc = (float)(sc / so); a.elt.mr = (float)(sr / so);
-                    a.elt.k0 = (float)(128.5 + (double)e - 128.0 * ((double)a.elt.mc + (double)a.elt.mr));
-                    a.elt.ylo = a.elt.relu ? 128.25f : 1.25f; a.elt.yhi = 255.75f; a.elt.thr = 2.f * e;
-                }
-            }
-            a.y = (int8_t*)o.dptr; a.ldc = o.cs; a.c_off = o.c_off;
-            a.c_limit = o.is_view ? cout : std::min(rup(cout, 16), o.cs - o.c_off);
-            st.bytes += (double)r.n * r.h * r.w * r.c;
-        }
-        // candidates: every kernel of the family computes the same bytes (exact integer GEMM + the same epilogue), so
-        // the choice is purely a matter of speed
-        std::vector<RaceCand> cands;        // tag = kernel name
-        // (the fused eltwise tail lives in the conv_igemm / conv_igemm2 / pw_stream epilogues)
-        if (!fz && gemm_direct_applicable(a)) cands.push_back({"gemm_direct_i8", [a](hipStream_t s) { return launch_gemm_direct(a, s); }});
-        if (pw_stream_applicable(a)) cands.push_back({"pw_stream_i8", [a](hipStream_t s) { return launch_pw_stream(a, s); }});
-        if (pw_rows_applicable(a)) cands.push_back({"pw_rows_i8", [a](hipStream_t s) { return launch_pw_rows(a, s); }});
-        if (conv_igemm2_applicable(a)) cands.push_back({conv_igemm2_kernel_name(a), [a](hipStream_t s) { return launch_conv_igemm2(a, s); }});
-        // lean-loop kernels (conv_pgemm.hip): fragment-ordered weights, k x k activations as an LDS-resident patch
-        {
-            int8_t* packed[2] = {nullptr, nullptr};       // per cout-tile width (64 / 128), packed on first use
-            int* geom[2] = {nullptr, nullptr};            // conv_pgemm_w.hip: the per-tile geometry table, per pixel-tile height (128 / 64)
-            for (int v = 0; v < conv_pgemm_num_variants(); v++) {
-                if (!conv_pgemm_applicable(a, v)) continue;
-                if ((v & 2) && a.M >= 65536) continue;    // 64-pixel tiles: only where 128-pixel tiles leave CUs idle
-                ConvArgs ap = a;
-                conv_pgemm_prepare(ap, v);
-                const int bn = conv_pgemm_bn(v), slot = bn == 128;
-                if (!packed[slot]) {
-                    std::vector<int8_t> wf(conv_pgemm_packed_bytes(ap, bn), 0);
-                    conv_pgemm_pack(ap, wp.data(), cout_pad, bn, wf.data());
-                    if (upload(g, wf, &packed[slot])) return -1;
-                }
-                ap.wfrag = packed[slot];
-                if (v & 16) {
-                    const int gs = (v & 2) ? 1 : 0;
-                    if (!geom[gs]) {
-                        std::vector<int> tab;
-                        conv_pgemm_w_table(ap, tab);
-                        if (upload(g, tab, &geom[gs])) return -1;
-                    }
-                    ap.pg_tab = geom[gs];
-                }
-                cands.push_back({conv_pgemm_kernel_name(ap), [ap](hipStream_t s) { return launch_conv_pgemm(ap, s); }});
-            }
-        }
-        // small maps (batch-1 tails, 1x1-map FC): the lean 16-channel-slice kernel of pwdw.hip without a tail
-        const bool is1x1 = KH == 1 && KW == 1 && p.stride_h == 1 && p.stride_w == 1 && !p.pad_h0 && !p.pad_h1 && !p.pad_w0 && !p.pad_w1;
-        if (!fz && is1x1 && a.M <= 4096 && !(exp_env("TAMD_PW_SMALL") && atoi(exp_env("TAMD_PW_SMALL")) == 0)) {
-            PwDwArgs v{};
-            const int slices = (cout + 15) / 16, cws = slices * 16;
-            const int steps = pwdw_steps((ckp + 63) / 64), nsteps = rup((ckp + 63) / 64, steps);
-            std::vector<int8_t> w2(wd, wd + (size_t)cout * cin);
-            const std::vector<int8_t> wf = pack_pw_panel(w2.data(), cout, cin, nsteps);
-            const std::vector<int32_t> b2 = padded_bias(bd, cout, cws);
-            int8_t* d0; int32_t* d1;
-            if (upload(g, wf, &d0) || upload(g, b2, &d1) || upload_rq(g, rqf, cws, &v.wscale, &v.rq)) return -1;
-            v.wf = d0; v.bias = d1;
-            v.x = a.x; v.N = x.n; v.H = x.h; v.W = x.w; v.cs_in = x.cs; v.ktot = ckp; v.nsteps = nsteps; v.steps = steps;
-            v.mode = 2; v.prod = 0; v.slices = slices; v.cw = cws;
-            v.coherent = (g->opt.direct_dispatch && !exp_plain_kernels()) ? 1 : 0;
-            v.tile_major = (double)x.h * x.w * x.cs > (double)cout * ckp && slices <= 65535 ? 1 : 0;
-            v.y = a.y; v.ldc = a.ldc; v.c_off = a.c_off; v.c_limit = a.c_limit;
-            v.S = 1; v.OH = x.h; v.OW = x.w; v.TW = x.w; v.tiles_x = 1; v.RH = 1; v.RW = x.w;
-            for (int px : {64, 128, 256}) {          // pixels per block: 1, 2, 4 tiles of 16 per wave at 256 threads
-                int th = std::max(1, std::min(x.h, px / std::max(1, x.w)));
-                v.TH = th; v.tiles_y = (x.h + th - 1) / th;
-                bool dup = false;
-                for (auto& c : cands) dup |= c.tag == "pw_small_i8<" + std::to_string(th) + ">";
-                if (dup || !pwdw_config_ok(v, 256)) continue;
-                const PwDwArgs vc = v;
-                cands.push_back({"pw_small_i8<" + std::to_string(th) + ">", [vc](hipStream_t s) { return launch_pwdw(vc, 256, s); }});
-            }
-        }
-        const bool heuristic_done = !cands.empty();
-        const bool autotune = autotune_enabled() && st.macs >= 5e5;
-        if (!heuristic_done || autotune) {
-            if (autotune) {
-                for (int c = 0; c < conv_igemm_num_cfgs(); c++) {
-                    if ((c == 1 || c == 3) && cout > 256 && a.M > 4096) continue;       // slivers: never competitive there
-                    if (!conv_igemm_cfg_ok(a, c)) continue;
-                    ConvArgs ac = a; ac.cfg = c;
-                    cands.push_back({conv_igemm_kernel_name(ac), [ac](hipStream_t s) { return launch_conv_igemm(ac, s); }});
-                }
-            } else
-                cands.push_back({conv_igemm_kernel_name(a), [a](hipStream_t s) { return launch_conv_igemm(a, s); }});
-        }
-        if (const char* force = getenv("TAMD_FORCE_GEMM")) {     // tests: pin one member of the family (read at every prerun)
-            const std::string want = force;
-            std::vector<RaceCand> only;
-            for (int c = 0; c < conv_igemm_num_cfgs(); c++) {
-                ConvArgs ac = a; ac.cfg = c;
-                if (want == "igemm" + std::to_string(c) && conv_igemm_cfg_ok(a, c)) only.push_back({conv_igemm_kernel_name(ac), [ac](hipStream_t s) { return launch_conv_igemm(ac, s); }});
-            }
-            for (auto& c : cands)
-                if (c.tag.find(want) == 0) only.push_back(c);
-            if (!only.empty()) cands = only;
-        }
-        char ckey[256];
-        snprintf(ckey, sizeof(ckey), "gemm|%s|%dx%dx%dx%d>%d k%dx%d s%d%s", n.name.c_str(), x.n, x.c, x.h, x.w, cout, KH, KW, p.stride_h, fz ? "+elt" : "");
-        // the heuristic candidates come first: a later one has to win by more than the timing noise; the heuristics remain the
-        // fallback (TAMD_AUTOTUNE=0)
-        const int best = plan_race(g, n.name, cands, ckey, 0.96f, autotune && cands.size() > 1);
-        if (best < 0) return -1;
-        st.kernel = cands[best].tag + (fz ? (fz->relu ? "+eltwise+relu" : "+eltwise") : "");
-        st.fn = cands[best].fn;
-    }
-    if (!fz) {                           // reads its input, writes its output (constants aside), one launch: all a convolution / FC step touches
-        st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
-    }
-    return 0;
-}
-
-
-static int plan_pool(tamd_graph* g, HNode& n, Planned* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    PoolGeom pg = pool_geom(n.p.pool, x.h, x.w);
-    PoolArgs a{};
-    a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
-    a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs; a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
-    a.KH = pg.kh; a.KW = pg.kw; a.SH = pg.sh; a.SW = pg.sw; a.PH = pg.ph0; a.PW = pg.pw0;
-    a.method = n.p.pool.pool_method; a.caffe_flavor = n.p.pool.caffe_flavor;
-    a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-    out->kind = Planned::POOL; out->pool = a;
-    Step& st = out->step;
-    st.node = n.name; st.kernel = "pool_i8";
-    st.bytes = (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c;
-    st.fn = [a](hipStream_t s) { return launch_pool(a, s); };
-    return 0;
 }
 
 
@@ -1022,11 +621,9 @@ static int try_dwpw(tamd_graph* g, I8Layout& L, size_t dwi, const Planned& pd, S
         if (g->nodes[nj].op == TAMD_OP_CONV && g->nodes[nj].in.size() >= 2 && g->nodes[nj].in[0] == d.out[0] && !L.fused[nj] && !L.has_fuse[nj]
             && g->nodes[nj].p.conv.group == 1 && g->nodes[nj].p.conv.kernel_h == 1 && g->nodes[nj].p.conv.kernel_w == 1) { pw_node = (int)nj; break; }
     if (pw_node < 0) return 0;
-    {   // what dwpw_applicable will ask of the shapes, before the consumer is planned (and its weights uploaded) for nothing
-        const HTensor& py = g->tensors[g->nodes[pw_node].out[0]];
-        const tamd_conv_param& q = g->nodes[pw_node].p.conv;
-        if (py.c % 64 != 0 || py.c > 512 || dy.w > 16 || q.stride_h != 1 || q.stride_w != 1 || q.pad_h0 || q.pad_w0 || q.pad_h1 || q.pad_w1) return 0;
-    }
+    // what dwpw_applicable will ask of the shapes, before the consumer is planned (and its weights uploaded) for nothing
+    const tamd_conv_param& q = g->nodes[pw_node].p.conv;
+    if (!dwpw_pw_shape_ok(g->tensors[g->nodes[pw_node].out[0]].c, dy.w, q.kernel_h, q.kernel_w, q.stride_h, q.stride_w, q.pad_h0 || q.pad_w0 || q.pad_h1 || q.pad_w1)) return 0;
     Planned pc;
     if (plan_conv(g, g->nodes[pw_node], false, nullptr, &pc)) return -1;
     const int r = plan_dwpw(g, d, g->nodes[pw_node], pd, pc, fused);

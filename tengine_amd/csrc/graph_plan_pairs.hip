@@ -42,9 +42,7 @@ int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod)
         const HTensor& o = g->tensors[c.out[0]];
         if (c.op == TAMD_OP_CONV && c.in.size() >= 2) {
             const tamd_conv_param& q = c.p.conv;
-            const bool dw3 = q.group > 1 && q.group == y.c && o.c == y.c && q.kernel_h == 3 && q.kernel_w == 3 && q.dilation_h == 1
-                             && q.dilation_w == 1 && q.stride_h == q.stride_w && (q.stride_h == 1 || q.stride_h == 2) && q.pad_h0 >= 0
-                             && q.pad_w0 >= 0 && q.pad_h0 <= 2 && q.pad_w0 <= 2;
+            const bool dw3 = is_dw3x3(q, y.c, o.c) && q.pad_h0 >= 0 && q.pad_w0 >= 0 && q.pad_h0 <= 2 && q.pad_w0 <= 2;
             if (!dw3 || o.scales.empty() || g->tensors[c.in[1]].scales.empty()) return -1;
             *tmode = 1;
             return (int)nj;
@@ -127,7 +125,7 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     a.N = x.n; a.H = mid.h; a.W = mid.w; a.cs_in = x.cs; a.ktot = ktot; a.nsteps = nsteps; a.steps = steps;
     a.mode = tmode; a.cw = cw; a.slices = slices;
     a.y = (int8_t*)y.dptr; a.ldc = y.cs; a.c_off = y.c_off;
-    a.c_limit = y.is_view ? C : std::min(rup(C, 16), y.cs - y.c_off);
+    a.c_limit = store_limit(y, C);
     a.S = 1; a.OH = a.OW = 1; a.TH = a.TW = 1; a.tiles_x = a.tiles_y = 1; a.RH = mid.h; a.RW = mid.w;
     if (tmode == 1) {
         const tamd_conv_param& q = tl.p.conv;

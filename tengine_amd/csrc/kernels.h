@@ -25,7 +25,7 @@ struct EltFuse {              // eltwise (+ReLU) node applied in the conv epilog
     float mc, mr, k0, ylo, yhi, thr;
 };
 
-// Requantisation constants of one conv / FC node, folded by the planner (graph_plan.hip: fold_requant + host_rq; the arithmetic and
+// Requantisation constants of one conv / FC node, folded by the planner (graph_plan_conv.hip: fold_requant + host_rq; the arithmetic and
 // its exactness argument are in epilogue.h).  The kernels' per-channel vector `wscale[]` holds the FAST-path multiplier
 // M[c] = RN32(m1 * m2[c] / out_scale); the reference chain's own factors stay here for the values the fast path hands over.
 struct RqArgs {
@@ -294,6 +294,7 @@ bool pw_stream_applicable(const ConvArgs& a);
 hipError_t launch_pw_rows(const ConvArgs& a, hipStream_t s);       // 1x1, shallow K, many pixels: row-major epilogue, persistent pipelined waves
 bool pw_rows_applicable(const ConvArgs& a);
 hipError_t launch_conv_first(const FirstArgs& a, hipStream_t s);
+bool dwpw_pw_shape_ok(int cout, int map_w, int KH, int KW, int SH, int SW, bool pads);   // the pointwise consumer's shape alone: what the planner can ask before it plans it
 bool dwpw_applicable(const DwArgs& d, const ConvArgs& p);
 size_t dwpw_packed_bytes(int cout, int cin);
 void dwpw_pack(const int8_t* w, int cout, int cin, int8_t* out);        // w: [cout][cin] (OIHW, 1x1)

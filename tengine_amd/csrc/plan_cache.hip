@@ -1,5 +1,5 @@
 // The plan-time races and the plan cache (TAMD_PLAN_CACHE=<file>) that remembers what they decided, shared by the planners
-// (graph_plan.hip, graph_plan_pairs.hip, graph_u8.hip, graph_f32.hip).  Split out of graph.hip in round 6.
+// (graph_plan_conv.hip, graph_plan_pairs.hip, graph_u8.hip, graph_f32.hip).  Split out of graph.hip in round 6.
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
