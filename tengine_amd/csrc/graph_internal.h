@@ -3,7 +3,7 @@
 //   graph_infer.hip       shape inference, validation, the PriorBox evaluator, the error string
 //   graph_plan.hip        the int8 planner (arena, layout passes, one function per node kind, plan_i8)
 //   graph_plan_conv.hip   .. its convolution / FC / pooling launches (requantisation folds, packers, one function per conv form)
-//   graph_plan_pairs.hip  .. its pair fusions (pwdw, dwpw); graph_plan.h is what those three share
+//   graph_plan_pairs.hip  .. its pair fusions (pwdw, dwpw) and the bottleneck-block fusion; graph_plan.h is what those three share
 //   plan_cache.hip        TAMD_PLAN_CACHE
 //   graph_pair.hip        a batched graph as two half-batch graphs side by side behind one handle (tamd_options.split_batch)
 //   graph_exec.hip        run_steps, the direct path's self-checks, zero-copy lists, the run-side entry points

@@ -38,6 +38,8 @@ struct Planned {
     FirstArgs first{};          // the member of `kind` is set; DIRECT has none
     DwArgs dw{};
     ConvArgs gemm{};
+    ConvArgs gemm_tail{};       // GEMM with elt_tail: the arguments as launched, tail included (`gemm` stays the bare convolution).  A second
+                                // ConvArgs in every Planned for ONE reader, plan_block, which needs the tail's folded constants
     PoolArgs pool{};
 };
 
@@ -49,5 +51,8 @@ int plan_pool(tamd_graph* g, HNode& n, Planned* out);
 int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod);
 int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Planned& a, const Planned& b, Step* fused);
 int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& d, const Planned& c, Step* fused);
+// an identity bottleneck block (1x1 -> 3x3 -> 1x1 + residual [+ ReLU]) in one launch: block_i8.hip.  c carries the eltwise tail fz
+bool fuse_block_enabled();
+int plan_block(tamd_graph* g, HNode& na, HNode& nb, HNode& nc, const FusedElt& fz, const Planned& a, const Planned& b, const Planned& c, Step* fused);
 
 }  // namespace tamd

@@ -631,12 +631,58 @@ static int try_dwpw(tamd_graph* g, I8Layout& L, size_t dwi, const Planned& pd, S
     return r;
 }
 
-// A convolution node and its three pairings: conv + pool (stem), pointwise + its tail (pwdw), depthwise + pointwise (dwpw).  Each
-// plans the launches involved as values and pushes either the fused launch or the planned ones.
+// identity bottleneck block (opt-in, TAMD_FUSE_BLOCK=1): node ni is a convolution whose output feeds exactly one convolution, whose
+// output feeds exactly one convolution that carries an eltwise SUM tail (scan_eltwise_fusion) with ni's INPUT as the other operand;
+// neither intermediate is a view or a graph output (count_consumers counts those).  The three are planned here, the later two ahead
+// of their node order (each reads only what is written by then), and either become one launch (plan_block) or are pushed as
+// planned.  1: pushed, 0: not such a block (nothing planned), -1: error.
+// Where the block fuses, plan_conv has uploaded each convolution's GEMM-family weight panel and run its plan-time race although only
+// its bias and requantisation vectors are read by the fused launch: dead device memory (res2: 3 x 68 KB), prerun time, and possibly
+// plan-cache entries for launches that never run -- try_dwpw's known waste, kept for the same reason (one plan_conv, no second path
+// that folds a requantisation).  The switch and the match on the eltwise tail are tested here only; plan_block takes what it is given.
+static int try_block(tamd_graph* g, I8Layout& L, size_t ni)
+{
+    if (!fuse_block_enabled()) return 0;
+    HNode& na = g->nodes[ni];
+    if (L.has_fuse[ni] || na.in.size() < 2 || g->tensors[na.in[0]].nchw_raw) return 0;
+    auto sole_conv_behind = [&](size_t from, int tensor) {
+        if (count_consumers(g, tensor) != 1 || g->tensors[tensor].is_view) return -1;
+        for (size_t nj = from + 1; nj < g->nodes.size(); nj++) {
+            const HNode& c = g->nodes[nj];
+            if (c.op == TAMD_OP_CONV && c.in.size() >= 2 && c.in[0] == tensor && !L.fused[nj]) return (int)nj;
+        }
+        return -1;
+    };
+    const int ib = sole_conv_behind(ni, na.out[0]);
+    if (ib < 0 || L.has_fuse[ib]) return 0;
+    const int ic = sole_conv_behind((size_t)ib, g->nodes[ib].out[0]);
+    if (ic < 0 || !L.has_fuse[ic] || L.fuse_at[ic].res_tensor != na.in[0] || L.fuse_at[ic].type != 2) return 0;
+    // what block_applicable will ask of the nodes' own shapes, before three convolutions are planned ahead of their order for nothing
+    auto shape_ok = [](const tamd_conv_param& q, int k) {
+        return q.group == 1 && block_conv_shape_ok(k, q.kernel_h, q.kernel_w, q.stride_h, q.stride_w, q.dilation_h, q.dilation_w, q.pad_h0, q.pad_h1, q.pad_w0, q.pad_w1);
+    };
+    if (!shape_ok(na.p.conv, 1) || !shape_ok(g->nodes[ib].p.conv, 3) || !shape_ok(g->nodes[ic].p.conv, 1)) return 0;      // (the pairings below keep the rest)
+    if (!block_channels_ok(g->tensors[na.in[0]].c, g->tensors[na.out[0]].c, g->tensors[g->nodes[ic].out[0]].c)) return 0;
+    Planned a, b, c;
+    if (plan_conv(g, na, false, nullptr, &a) || plan_conv(g, g->nodes[ib], false, nullptr, &b) || plan_conv(g, g->nodes[ic], false, &L.fuse_at[ic], &c)) return -1;
+    L.fused[ib] = 1; L.fused[ic] = 1;
+    Step st;
+    const int took = plan_block(g, na, g->nodes[ib], g->nodes[ic], L.fuse_at[ic], a, b, c, &st);
+    if (took < 0) return -1;
+    if (took) g->steps.push_back(st);
+    else { g->steps.push_back(a.step); g->steps.push_back(b.step); g->steps.push_back(c.step); }
+    return 1;
+}
+
+// A convolution node and its fusions: the bottleneck block (opt-in), then the three pairings conv + pool (stem), pointwise + its tail
+// (pwdw), depthwise + pointwise (dwpw).  Each plans the launches involved as values and pushes either the fused launch or the
+// planned ones.
 static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
 {
     HNode& n = g->nodes[ni];
     Step st;
+    const int blk = try_block(g, L, ni);
+    if (blk) return blk < 0 ? -1 : 0;
     // stem (TAMD_FIRST_POOL=0: two launches, for A/B runs and the fused == unfused tests)
     if (!L.has_fuse[ni] && g->tensors[n.in[0]].nchw_raw && count_consumers(g, n.out[0]) == 1) {
         int pool_node = -1;

@@ -446,7 +446,7 @@ static int conv_i8_gemm(ConvI8& c, const FusedElt* fz, Planned* out)
     std::vector<int8_t> wp;
     if (conv_i8_gemm_args(c, &a, &wp)) return -1;
     out->kind = Planned::GEMM; out->gemm = a;       // (as it is without the eltwise tail: what a fuser reads)
-    if (fz) conv_i8_elt_tail(c, *fz, a, st);
+    if (fz) { conv_i8_elt_tail(c, *fz, a, st); out->gemm_tail = a; }
     std::vector<RaceCand> cands;        // tag = kernel name
     gemm_fixed_cands(a, fz != nullptr, cands);
     if (gemm_pgemm_cands(c, a, wp, cands)) return -1;

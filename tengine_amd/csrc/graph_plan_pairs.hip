@@ -1,5 +1,5 @@
 // int8 planner, the pair fusions: pointwise conv + its single consumer (depthwise 3x3 | global pooling) in one launch (pwdw.hip), and
-// depthwise 3x3 + the pointwise conv behind it (dwpw.hip).
+// depthwise 3x3 + the pointwise conv behind it (dwpw.hip); and the one triple: an identity bottleneck block (block_i8.hip).
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_pack.h"
 #include "epilogue.h"
 #include "graph_plan.h"
 
@@ -309,6 +310,42 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& pd, const Plan
     st.fn = [a](hipStream_t s) { return launch_dwpw(a, s); };
     st.rd.push_back(access_of(g->tensors[dw.in[0]])); st.wr.push_back(access_of(g->tensors[pw.out[0]])); st.deps = true;
     g->fused_away[dw.out[0]] = 1;
+    return 1;
+}
+
+// ---- an identity bottleneck block -- 1x1 -> 3x3 -> 1x1 + residual (+ ReLU) -- in one launch: block_i8.hip --------------------------
+// TAMD_FUSE_BLOCK=1 fuses wherever block_applicable holds; unset or 0: never (opt-in: no plan-time race, no plan-cache entry).
+bool fuse_block_enabled()
+{
+    const char* env = getenv("TAMD_FUSE_BLOCK");                 // read at every prerun
+    return env && atoi(env) == 1;
+}
+
+// Called with the three convolutions planned as `pa`, `pb` (as they stand) and `pc` (with the eltwise tail fz that scan_eltwise_fusion
+// gave it); every one keeps the requantisation plan_conv folded for it (conv_mode at the graph's batch), the fused launch reads the
+// same device vectors.  The caller (try_block) has read the switch and matched the graph shape.
+int plan_block(tamd_graph* g, HNode& na, HNode& nb, HNode& nc, const FusedElt& fz, const Planned& pa, const Planned& pb, const Planned& pc, Step* fused)
+{
+    if (pa.kind != Planned::GEMM || pb.kind != Planned::GEMM || pc.kind != Planned::GEMM) return 0;
+    if (pa.elt_tail || pb.elt_tail || !pc.elt_tail || !block_applicable(pa.gemm, pb.gemm, pc.gemm_tail)) return 0;      // (the residual IS na's input: block_applicable compares the pointers)
+    const ConvArgs& a = pa.gemm;
+    const HTensor &wa = g->tensors[na.in[1]], &wb = g->tensors[nb.in[1]], &wc = g->tensors[nc.in[1]];
+    const int C = a.cin, mid = a.cout;
+    if (wa.elems() != (size_t)mid * C || wb.elems() != (size_t)mid * mid * 9 || wc.elems() != (size_t)C * mid) return 0;
+    std::vector<int8_t> wp(block_packed_bytes(C, block_mid_pad(mid)));
+    block_pack((const int8_t*)wa.data.data(), (const int8_t*)wb.data.data(), (const int8_t*)wc.data.data(), C, mid, wp.data());
+    int8_t* dwp = nullptr;
+    if (upload(g, wp, &dwp)) return -1;
+    const BlockArgs v = block_args(a, pb.gemm, pc.gemm_tail, dwp);
+    Step& st = *fused;
+    st.node = pa.step.node + "+" + pb.step.node + "+" + pc.step.node;
+    st.kernel = "block_i8";
+    st.macs = pa.step.macs + pb.step.macs + pc.step.macs;
+    st.bytes = pa.step.bytes + pb.step.bytes + pc.step.bytes;      // SURVEY 8(d) accounting, per layer: both intermediate maps still count
+    st.fn = [v](hipStream_t s) { return launch_block(v, s); };
+    st.rd.push_back(access_of(g->tensors[na.in[0]])); st.wr.push_back(access_of(g->tensors[fz.out_tensor])); st.deps = true;
+    g->fused_away[na.out[0]] = 1;
+    g->fused_away[nb.out[0]] = 1;
     return 1;
 }
 

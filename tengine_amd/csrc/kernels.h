@@ -104,6 +104,23 @@ struct DwPwArgs {          // depthwise 3x3 (stride 1) -> pointwise 1x1 in one l
 #endif
 };
 
+struct BlockArgs {         // identity bottleneck block in one launch (block_i8.hip): 1x1 -> 3x3 -> 1x1 + residual [+ ReLU]; both intermediate
+                           // maps only exist in LDS
+    const int8_t* x;       // NHWC input of branch2a == the residual (channel offset applied)
+    const int8_t* wpk;     // the three weight sets in A-fragment order (block_pack.h)
+    const int32_t* bias_a; const float* wscale_a; RqArgs rq_a;     // branch2a (1x1, C -> mid), padded to >= roundup(mid, 32) channels
+    const int32_t* bias_b; const float* wscale_b; RqArgs rq_b;     // branch2b (3x3 stride 1 pad 1, mid -> mid)
+    const int32_t* bias_c; const float* wscale_c; RqArgs rq_c;     // branch2c (1x1, mid -> C)
+    EltFuse elt;           // the eltwise (+ReLU) tail of branch2c; elt.res is not read: the residual comes from the staged input tile
+    int8_t* y;             // NHWC output of the tail
+    int N, H, W, C, mid, cs_in, ldc, c_off, c_limit;
+    int tiles_x, tiles_y, tiles;           // 8 x 8 output tiles per image row / column, in all (N * tiles_y * tiles_x)
+    int grid;              // blocks; each loops over tiles blockIdx.x, blockIdx.x + grid, ..
+#ifdef TAMD_BLOCK_STAMPS
+    unsigned long long* stamps;            // tools/exp/block_anatomy.hip only: 8 per block (100 MHz wall clock)
+#endif
+};
+
 struct PwDwArgs {          // pointwise conv + its consumer in one launch (pwdw.hip)
     const int8_t* x;       // NHWC input of the pointwise conv (channel offset applied)
     const int8_t* wf;      // pointwise weights in MFMA fragment order: [16-channel slice][64-deep K step][64 lanes][16 B]
@@ -299,6 +316,12 @@ bool dwpw_applicable(const DwArgs& d, const ConvArgs& p);
 size_t dwpw_packed_bytes(int cout, int cin);
 void dwpw_pack(const int8_t* w, int cout, int cin, int8_t* out);        // w: [cout][cin] (OIHW, 1x1)
 hipError_t launch_dwpw(const DwPwArgs& a, hipStream_t s);
+// identity bottleneck block in one launch (block_i8.hip).  a / b: branch2a / branch2b as planned; c: branch2c WITH its eltwise tail
+bool block_applicable(const ConvArgs& a, const ConvArgs& b, const ConvArgs& c);
+bool block_conv_shape_ok(int k, int KH, int KW, int SH, int SW, int DH, int DW, int p_h0, int p_h1, int p_w0, int p_w1);   // k = 1 (branch2a / 2c) or 3 (branch2b): a node's shape alone ..
+bool block_channels_ok(int C, int mid, int cout);                                                                        // .. and the channel counts: what the planner can ask before it plans the three
+BlockArgs block_args(const ConvArgs& a, const ConvArgs& b, const ConvArgs& c, const int8_t* wpk);     // (after block_applicable)
+hipError_t launch_block(const BlockArgs& a, hipStream_t s);
 bool conv_first_pool_applicable(const FirstArgs& c, const PoolArgs& p);
 FirstPoolArgs conv_first_pool_args(const FirstArgs& c, const PoolArgs& p);
 hipError_t launch_conv_first_pool(const FirstPoolArgs& a, hipStream_t s);
