@@ -55,7 +55,8 @@ enum {
     TAMD_OP_ELTWISE = 6, /* param: tamd_eltwise_param */
     TAMD_OP_CONCAT = 7,  /* param: tamd_concat_param */
     TAMD_OP_DROPOUT = 8, /* identity */
-    TAMD_OP_UPSAMPLE = 9,/* param: tamd_upsample_param */
+    TAMD_OP_UPSAMPLE = 9,/* param: tamd_upsample_param; nearest, an integer factor >= 1; fp32 / uint8 graphs, and int8 graphs for a 4-D
+                          * tensor: upsample_ref.c:162-165 runs its uint8 routine on the int8 BYTES (0 .. 255), and so does the device */
     TAMD_OP_RELU6 = 10,
     TAMD_OP_FLATTEN = 11,
     TAMD_OP_SOFTMAX = 12, /* param: tamd_softmax_param (NULL: axis 1); fp32 / uint8 graphs: any axis; int8 graphs: any axis >= 1 of a

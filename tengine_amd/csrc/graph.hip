@@ -73,7 +73,7 @@ const char* tamd_version(void) { return "tengine_amd 0.4 (gfx950)"; }
 int tamd_op_supported(int op, int dtype)
 {
     if (dtype != TAMD_DT_INT8 && dtype != TAMD_DT_UINT8 && dtype != TAMD_DT_FP32) return 0;
-    if (op == TAMD_OP_UPSAMPLE) return dtype != TAMD_DT_INT8;      // nearest upsample: uint8 / fp32 graphs
+    if (op == TAMD_OP_UPSAMPLE) return 1;                          // nearest upsample (which factors and ranks: tamd_node_supported)
     if (op == TAMD_OP_RELU6) return dtype == TAMD_DT_FP32;
     if (op == TAMD_OP_SOFTMAX) return 1;                           // (which axes: tamd_node_supported)
     if (op == TAMD_OP_RESHAPE || op == TAMD_OP_PRIORBOX) return 1; // dense device tensors: uint8 / fp32 graphs; int8 since round 6 (graph_plan.hip)
@@ -167,6 +167,7 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
     }
     case TAMD_OP_UPSAMPLE: {
         const float sc = n->param ? ((const tamd_upsample_param*)n->param)->scale : 0.f;
+        if (dt == TAMD_DT_INT8 && (n_in < 1 || in[0].dim_num != 4 || in[0].ttype == TAMD_TT_CONST)) return 0;   // NHWC device tensors (upsample_i8)
         return sc >= 1.f && sc == (float)(int)sc;
     }
     case TAMD_OP_POOL: {

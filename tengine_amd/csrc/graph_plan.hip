@@ -265,7 +265,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 static int plan_concat_views(tamd_graph* g, I8Layout& L)
 {
     auto producer_op = [&](int t) { for (auto& n : g->nodes) if (!n.out.empty() && n.out[0] == t) return n.op; return -1; };
-    auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL; };
+    auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE; };
     for (auto& n : g->nodes) {
         if (n.op != TAMD_OP_CONCAT || L.flat_concat[&n - g->nodes.data()]) continue;
         HTensor& y = g->tensors[n.out[0]];
@@ -790,14 +790,77 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
     return 0;
 }
 
-static int plan_relu(tamd_graph* g, HNode& n)
+// ReLU (slope >= 0) whose only consumer is a MAX pool (YOLOv3-tiny: five of its eleven leaky ReLUs; leaky4 has a second reader): one launch, relu_pool_i8
+// (misc_kernels.hip: the ReLU's byte map is non-decreasing, so it commutes with the max).  The pool is planned here, ahead of its
+// node, and its launch reads the ReLU's input; the ReLU's own output is never written.  A negative slope is not monotone, an average
+// pool does not commute, the global form has its own kernel: those stay two launches.  TAMD_PIN=relu_pool=0: two launches (A/B runs
+// and the fused == unfused tests).  1: pushed, 0: not such a pair, -1: error
+// The pool may sit anywhere behind the ReLU in node order: its output is then written at the RELU's position, while the ReLU's input is
+// still being read.  That is safe only because plan_buffers starts a buffer's lifetime at the earliest producer within TWO hops above the
+// node that produces it (pool <- relu <- the ReLU's producer), so the pool's output can never share memory with the ReLU's input; a change
+// to that rule or to this look-ahead has to keep the two apart.  The ReLU's never-written output still owns its (shared) buffer.
+static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni)
 {
+    HNode& n = g->nodes[ni];
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
+    if (!tamd_pin_int("relu_pool", 1) || !(n.p.relu.negative_slope >= 0.f) || x.is_view || y.is_view || x.nchw_raw) return 0;
+    if (count_consumers(g, n.out[0]) != 1) return 0;             // (a graph output counts as a consumer)
+    int pool_node = -1;
+    for (size_t nj = ni + 1; nj < g->nodes.size(); nj++)
+        if (g->nodes[nj].op == TAMD_OP_POOL && g->nodes[nj].in[0] == n.out[0] && !L.fused[nj]) { pool_node = (int)nj; break; }
+    if (pool_node < 0 || g->nodes[pool_node].p.pool.pool_method != 0) return 0;
+    Planned p;
+    if (plan_pool(g, g->nodes[pool_node], &p)) return -1;
+    if (pool_is_global(p.pool)) return 0;                        // (plan_pool uploads nothing: the trial costs nothing)
+    ReluPoolArgs a{};
+    a.p = p.pool;
+    a.p.x = (const int8_t*)x.dptr; a.p.cs_in = x.cs;
+    a.slope = n.p.relu.negative_slope; a.relu_in_scale = x.scales[0];
+    Step st = make_step(n.name + "+" + g->nodes[pool_node].name, "relu_pool_i8", 0, p.step.bytes, [a](hipStream_t s) { return launch_relu_pool(a, s); });
+    g->steps.push_back(st);
+    L.fused[pool_node] = 1;
+    g->fused_away[n.out[0]] = 1;
+    return 1;
+}
+
+static int plan_relu(tamd_graph* g, I8Layout& L, size_t ni)
+{
+    HNode& n = g->nodes[ni];
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const int took = try_relu_pool(g, L, ni);
+    if (took) return took < 0 ? -1 : 0;
     if (x.is_view || y.is_view) { set_error("relu %s on a concat view is not supported", n.name.c_str()); return -1; }
     ReluArgs a{(const int8_t*)x.dptr, (int8_t*)y.dptr, (size_t)x.n * x.h * x.w * x.cs, n.p.relu.negative_slope, x.scales[0], y.scales[0]};
     Step st; st.node = n.name; st.kernel = "relu_i8"; st.bytes = 2.0 * x.n * x.h * x.w * x.c;
     st.fn = [a](hipStream_t s) { return launch_relu(a, s); };
+    g->steps.push_back(st);
+    return 0;
+}
+
+// upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
+static int plan_upsample(tamd_graph* g, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const int sc = (int)n.p.ups.scale;
+    if (x.dims.size() != 4 || sc < 1 || (float)sc != n.p.ups.scale) { set_error("upsample %s: only an integer factor of a 4-D tensor runs on the device", n.name.c_str()); return -1; }
+    if (x.scales.empty() || y.scales.empty()) { set_error("upsample %s: missing quant params", n.name.c_str()); return -1; }
+    if (y.n != x.n || y.c != x.c || y.h != x.h * sc || y.w != x.w * sc) { set_error("upsample %s: output shape mismatch", n.name.c_str()); return -1; }
+    // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
+    const int cv = rup(x.c, 16);
+    if (x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + cv > x.cs || y.c_off + cv > y.cs) {
+        set_error("upsample %s: channel slice not 16-byte aligned", n.name.c_str());
+        return -1;
+    }
+    UpsampleI8Args a{};
+    a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+    a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs; a.scale = sc; a.ldc = y.cs; a.c_off = y.c_off;
+    a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
+    a.in_zp = x.zps.empty() ? 0 : x.zps[0]; a.out_zp = y.zps.empty() ? 0 : y.zps[0];
+    a.copy = a.in_scale == a.out_scale && a.in_zp == a.out_zp;
+    Step st = make_step(n.name, "upsample_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_upsample_i8(a, s); });
     g->steps.push_back(st);
     return 0;
 }
@@ -875,7 +938,8 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_FC: if (!(r = plan_conv(g, n, true, nullptr, &one))) g->steps.push_back(one.step); break;
         case TAMD_OP_POOL: if (!(r = plan_pool(g, n, &one))) g->steps.push_back(one.step); break;
         case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n); break;
-        case TAMD_OP_RELU: r = plan_relu(g, n); break;
+        case TAMD_OP_RELU: r = plan_relu(g, L, ni); break;
+        case TAMD_OP_UPSAMPLE: r = plan_upsample(g, n); break;
         case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, ni); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());

@@ -204,6 +204,24 @@ struct PoolArgs {
     float in_scale, out_scale;
 };
 
+// the global form (window == whole map, no padding): launch_pool takes its own kernel for it
+inline bool pool_is_global(const PoolArgs& a) { return a.OH == 1 && a.OW == 1 && a.KH == a.H && a.KW == a.W && a.PH == 0 && a.PW == 0; }
+
+struct ReluPoolArgs {      // ReLU (slope >= 0) -> MAX pool in one launch: max of the raw bytes, the ReLU's byte map once, the pool's requant
+    PoolArgs p;            // the pool as planned, except x / cs_in: the ReLU's INPUT; in_scale is the ReLU's output scale
+    float slope, relu_in_scale;
+};
+
+struct UpsampleI8Args {    // nearest upsample by an integer factor, NHWC int8: upsample_ref.c:74-130 run on the int8 BYTES (0 .. 255)
+    const int8_t* x;       // first channel of the input (a view's channel offset applied)
+    int8_t* y;             // base of the output buffer
+    int N, H, W, C, cs_in; // input map; the output map is H * scale x W * scale
+    int scale, ldc, c_off; // output pixel stride and channel offset (a concat view)
+    float in_scale, out_scale;
+    int in_zp, out_zp;
+    int copy;              // equal scales and zero points: the byte map is the identity
+};
+
 struct FirstPoolArgs {     // the stem in one launch: FirstArgs' convolution (7 x KW, stride 2, C = 3) + MAX pool 3x3 / 2 / pad 0 (conv_first_pool.hip)
     const int8_t* x;       // NCHW graph input
     const int8_t* w;       // FirstArgs::w with kwp == 8
@@ -338,6 +356,8 @@ hipError_t launch_pwdw_chain(const PwChainArgs& c, int threads, size_t lds, hipS
 bool pwdw_config_ok(const PwDwArgs& a, int threads);
 int pwdw_steps(int nsteps);
 hipError_t launch_pool(const PoolArgs& a, hipStream_t s);
+hipError_t launch_relu_pool(const ReluPoolArgs& a, hipStream_t s);   // (never the global form)
+hipError_t launch_upsample_i8(const UpsampleI8Args& a, hipStream_t s);
 hipError_t launch_eltwise(const EltArgs& a, hipStream_t s);
 hipError_t launch_relu(const ReluArgs& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);

@@ -117,13 +117,119 @@ __global__ __launch_bounds__(256) void global_pool_i8_kernel(PoolArgs a)
 
 hipError_t launch_pool(const PoolArgs& a, hipStream_t s)
 {
-    if (a.OH == 1 && a.OW == 1 && a.KH == a.H && a.KW == a.W && a.PH == 0 && a.PW == 0) {
+    if (pool_is_global(a)) {
         const int cg = (a.C + 3) / 4;
         hipLaunchKernelGGL(global_pool_i8_kernel, dim3((cg + 15) / 16, a.N), dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const long total = (long)a.N * a.OH * a.OW * ((a.C + 3) / 4);
     hipLaunchKernelGGL(pool_i8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- ReLU (slope >= 0) -> MAX pool in one launch.  relu_kernel_ref_int8.c:41-94 is a per-byte map T -- f = (float)x * in_scale;
+// f < 0 -> f * slope (0 when the slope is 0); round(f / out_scale), clamp +-127 -- and T is non-decreasing for a slope >= 0, so
+// max(T(x)) == T(max(x)) over any window: the max of the RAW bytes over the in-image taps (the window logic of pool_i8_kernel),
+// T once per output, then the pool's own round((float)m * (in_scale / out_scale)).  The ReLU's map is never stored.
+__global__ __launch_bounds__(256) void relu_pool_i8_kernel(ReluPoolArgs ra)
+{
+    const PoolArgs& a = ra.p;
+    const int cg = (a.C + 3) / 4;
+    const long total = (long)a.N * a.OH * a.OW * cg;
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int c4 = (int)(idx % cg); idx /= cg;
+    const int px = (int)(idx % a.OW); idx /= a.OW;
+    const int py = (int)(idx % a.OH);
+    const int n = (int)(idx / a.OH);
+
+    int hs = py * a.SH - a.PH, he = hs + a.KH;
+    int ws = px * a.SW - a.PW, we = ws + a.KW;
+    hs = hs > 0 ? hs : 0;
+    ws = ws > 0 ? ws : 0;
+    he = he < a.H ? he : a.H;
+    we = we < a.W ? we : a.W;
+
+    const int8_t* xn = a.x + (size_t)n * a.H * a.W * a.cs_in + c4 * 4;
+    const unsigned f0 = *reinterpret_cast<const unsigned*>(xn + ((size_t)hs * a.W + ws) * a.cs_in);
+    int m[4] = {sxb(f0, 0), sxb(f0, 1), sxb(f0, 2), sxb(f0, 3)};
+    for (int iy = hs; iy < he; iy++)
+        for (int ix = ws; ix < we; ix++) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(xn + ((size_t)iy * a.W + ix) * a.cs_in);
+#pragma unroll
+            for (int b = 0; b < 4; b++) { int t = sxb(v, b); m[b] = m[b] > t ? m[b] : t; }
+        }
+    const float inv_relu = __fdiv_rn(1.0f, a.in_scale);
+    const float rq = __fdiv_rn(a.in_scale, a.out_scale);
+    int q[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        float f = __fmul_rn((float)m[b], ra.relu_in_scale);
+        if (f < 0.f) f = (ra.slope == 0.f) ? 0.f : __fmul_rn(f, ra.slope);
+        const int t = round_div_sat(f, a.in_scale, inv_relu);
+        q[b] = round_sat(__fmul_rn((float)t, rq));
+    }
+    *reinterpret_cast<unsigned*>(a.y + (((size_t)n * a.OH + py) * a.OW + px) * a.ldc + a.c_off + c4 * 4) =
+        pack4(q[0], q[1], q[2], q[3]);
+}
+
+hipError_t launch_relu_pool(const ReluPoolArgs& a, hipStream_t s)
+{
+    if (a.p.method != 0 || pool_is_global(a.p) || !(a.slope >= 0.f)) return hipErrorInvalidValue;
+    const long total = (long)a.p.N * a.p.OH * a.p.OW * ((a.p.C + 3) / 4);
+    hipLaunchKernelGGL(relu_pool_i8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- nearest upsample by an integer factor: upsample_ref.c:162-165 sends every non-fp32 tensor through ref_upsample_uint8 (:74-130),
+// so an int8 tensor is read as BYTES u = 0 .. 255: f = ((float)u - (float)zp_in) * in_scale; round(f / out_scale + (float)zp_out),
+// clamp 0 .. 255, stored into the int8 tensor (zero points are 0 for int8; a negative input does NOT come out as a signed rescale
+// would give it).  Source pixel = (int)(out / scale).  Byte 0 -> 0: zero channel padding stays zero.  One lane per input pixel and
+// 16-byte channel vector: read once, mapped once, stored to its scale x scale output pixels.  COPY: equal scales and zero points.
+template <bool COPY>
+__global__ __launch_bounds__(256) void upsample_i8_kernel(UpsampleI8Args a)
+{
+    const int nv = (a.C + 15) / 16;
+    const long total = (long)a.N * a.H * a.W * nv;
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int v = (int)(idx % nv); idx /= nv;
+    const int ix = (int)(idx % a.W); idx /= a.W;
+    const int iy = (int)(idx % a.H);
+    const int n = (int)(idx / a.H);
+    uint4 d = *reinterpret_cast<const uint4*>(a.x + (((size_t)n * a.H + iy) * a.W + ix) * a.cs_in + v * 16);
+    if (!COPY) {
+        unsigned p[4] = {d.x, d.y, d.z, d.w};
+        const float zi = (float)a.in_zp, zo = (float)a.out_zp;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            unsigned o = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const float f = __fmul_rn(__fsub_rn((float)((p[k] >> (8 * b)) & 0xffu), zi), a.in_scale);
+                int q = (int)roundf(__fadd_rn(__fdiv_rn(f, a.out_scale), zo));
+                q = q > 255 ? 255 : (q < 0 ? 0 : q);
+                o |= (unsigned)q << (8 * b);
+            }
+            p[k] = o;
+        }
+        d = make_uint4(p[0], p[1], p[2], p[3]);
+    }
+    const int OW = a.W * a.scale;
+    int8_t* y0 = a.y + (((size_t)n * a.H * a.scale + (size_t)iy * a.scale) * OW + (size_t)ix * a.scale) * a.ldc + a.c_off + v * 16;
+    for (int dy = 0; dy < a.scale; dy++)
+        for (int dx = 0; dx < a.scale; dx++)
+            *reinterpret_cast<uint4*>(y0 + ((size_t)dy * OW + dx) * a.ldc) = d;
+}
+
+hipError_t launch_upsample_i8(const UpsampleI8Args& a, hipStream_t s)
+{
+    if (a.scale < 1 || a.C < 1) return hipErrorInvalidValue;
+    const long total = (long)a.N * a.H * a.W * ((a.C + 15) / 16);
+    if (total <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (a.copy) hipLaunchKernelGGL(upsample_i8_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(upsample_i8_kernel<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 
     python tools/tm_benchmark.py -r 50 -s 1 -p int8            # MobileNet-v1 int8, batch 1
     python tools/tm_benchmark.py -r 20 -s 8 -p uint8 -b 8      # YOLOv3-tiny uint8, 8 images
+    python tools/tm_benchmark.py -r 20 -s 8 -p int8 -b 8       # YOLOv3-tiny int8 (one launch list on the device: upsample_i8, relu_pool_i8)
 
 Times are what tm_benchmark times: H2D of the input, the graph, D2H of the outputs (`tamd_graph_run`).  Needs a GPU:
 the product has no CPU path."""
