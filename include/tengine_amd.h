@@ -171,6 +171,9 @@ typedef struct tamd_options {
                            * TAMD_SPLIT_BATCH=0|1|2 overrides 0 and 2 (0: never, 1: default rule, 2: wherever possible -- the values the
                            * plugin's switch of the same name takes).  tamd_graph_halves() tells which form a graph took. */
 } tamd_options;
+/* does a blob that carries `size` hold `field` whole?  Every reader of a caller's blob asks this field by field; a field the blob
+ * does not reach keeps the reader's default */
+#define TAMD_OPTIONS_HAS(size, field) ((size) >= (int)(offsetof(tamd_options, field) + sizeof(((const tamd_options*)0)->field)))
 
 typedef struct tamd_graph tamd_graph;
 

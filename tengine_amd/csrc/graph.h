@@ -10,6 +10,7 @@
 
 #include "../../include/tengine_amd.h"
 #include "kernels.h"
+#include "node_rules.h"
 
 namespace tamd {
 

@@ -88,8 +88,9 @@ int tamd_op_supported(int op, int dtype)
 }
 
 // What allocator.describe cannot say with an operator list alone: is THIS node, with these parameters and tensors, one the
-// planners compile?  The Tengine plugin asks before it claims a subgraph (hip_device.cc: subgraph_runs_on_device), so
-// anything else lands on the CPU device instead of failing pre_run.  Mirrors the planners' own conditions.
+// planners compile?  The Tengine plugin asks before it claims a subgraph (hip_device.cc: node_runs_on_device), so
+// anything else lands on the CPU device instead of failing pre_run.  The rules it shares with the planners are the predicates of
+// node_rules.h; elsewhere it is deliberately the stricter of the two (int8 Concat on a spatial axis, say).
 int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int n_in, const tamd_tensor_desc* out, int n_out)
 {
     if (!n || n_out < 1 || !out) return 0;
@@ -111,7 +112,7 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         if (in[1].quant_num != 0 && in[1].quant_num != 1 && in[1].quant_num != cout) return 0;
         if (dt != TAMD_DT_FP32 && in[1].quant_num == 0) return 0;
         if (dt == TAMD_DT_UINT8 && in[1].quant_num != 1) return 0;                 // per-tensor weights (conv_kernel_x86.c:76-79)
-        if (dt == TAMD_DT_INT8 && p.group == 1 && kh * kw > 128 && cin > 4) return 0;  // tap table of the implicit GEMM
+        if (dt == TAMD_DT_INT8 && p.group == 1 && cin > 4 && !conv_i8_gemm_taps_fit(kh, kw)) return 0;
         if (n_in > 2 && (in[2].ttype != TAMD_TT_CONST || elems(in[2]) < (size_t)cout)) return 0;
         return 1;
     }
@@ -121,12 +122,12 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         const int nout = out[0].dim_num > 1 ? out[0].dims[1] : 0;
         if (nout < 1 || in[1].dim_num != 2 || in[1].dims[0] != nout || (size_t)in[1].dims[1] != hidden) return 0;   // [num_output][hidden] only (fc.c:43-97)
         if (n->param && ((const tamd_fc_param*)n->param)->num_output && ((const tamd_fc_param*)n->param)->num_output != nout) return 0;
-        if (dt == TAMD_DT_UINT8 && hidden * 4 > 60000) return 0;                    // fc_u8 keeps the input row in LDS
+        if (dt == TAMD_DT_UINT8 && !fc_u8_row_fits_lds(hidden)) return 0;
         return 1;
     }
     case TAMD_OP_ELTWISE: {
         const int ty = n->param ? ((const tamd_eltwise_param*)n->param)->type : -1;
-        if (n_in != 2 || (ty != 0 && ty != 2 && ty != 4 && ty != 6)) return 0;
+        if (n_in != 2 || !eltwise_type_on_device(ty)) return 0;
         if (in[0].dim_num != in[1].dim_num) return 0;
         for (int i = 0; i < in[0].dim_num; i++) if (in[0].dims[i] != in[1].dims[i]) return 0;
         return in[0].ttype != TAMD_TT_CONST && in[1].ttype != TAMD_TT_CONST;
@@ -152,7 +153,7 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         if (ax < 0) ax += in[0].dim_num;
         if (ax < 1 || ax >= in[0].dim_num) return 0;
         if (in[0].dim_num == 2 && ax != 1) return 0;
-        return in[0].dims[ax] >= 1 && in[0].dims[ax] <= kSoftmaxI8MaxC;
+        return softmax_i8_axis_fits(in[0].dims[ax]);
     }
     case TAMD_OP_PRIORBOX: {
         if (!n->param || n_in < 2 || in[0].dim_num != 4 || in[1].dim_num != 4 || out[0].dim_num < 1 || out[0].dims[0] != 1) return 0;
@@ -162,13 +163,12 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
     }
     case TAMD_OP_PERMUTE: {
         if (!n->param || out[0].dim_num != 4) return 0;
-        const int* o = ((const tamd_permute_param*)n->param)->order;
-        return o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1;
+        return permute_order_on_device(((const tamd_permute_param*)n->param)->order);
     }
     case TAMD_OP_UPSAMPLE: {
         const float sc = n->param ? ((const tamd_upsample_param*)n->param)->scale : 0.f;
         if (dt == TAMD_DT_INT8 && (n_in < 1 || in[0].dim_num != 4 || in[0].ttype == TAMD_TT_CONST)) return 0;   // NHWC device tensors (upsample_i8)
-        return sc >= 1.f && sc == (float)(int)sc;
+        return upsample_factor_on_device(sc);
     }
     case TAMD_OP_POOL: {
         if (!n->param || in[0].dim_num != 4) return 0;
@@ -273,12 +273,12 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
     o.dev_name = "HIP"; o.size = (int)sizeof(tamd_options); o.gpu_index = 0; o.use_hip_graph = 1; o.profile = 0;
     if (opt) {             // options may be NULL (scheduler.c:49-59); only the fields the caller's blob really holds are read
         const int have = opt->size;
-        if (have >= (int)(offsetof(tamd_options, gpu_index) + sizeof(int))) o.gpu_index = opt->gpu_index;
-        if (have >= (int)(offsetof(tamd_options, use_hip_graph) + sizeof(int))) o.use_hip_graph = opt->use_hip_graph;
-        if (have >= (int)(offsetof(tamd_options, profile) + sizeof(int))) o.profile = opt->profile;
-        if (have >= (int)(offsetof(tamd_options, direct_dispatch) + sizeof(int))) o.direct_dispatch = opt->direct_dispatch;
-        if (have >= (int)(offsetof(tamd_options, keep_tensors) + sizeof(int))) o.keep_tensors = opt->keep_tensors;
-        if (have >= (int)(offsetof(tamd_options, u8_integer) + sizeof(int))) o.u8_integer = opt->u8_integer;
+        if (TAMD_OPTIONS_HAS(have, gpu_index)) o.gpu_index = opt->gpu_index;
+        if (TAMD_OPTIONS_HAS(have, use_hip_graph)) o.use_hip_graph = opt->use_hip_graph;
+        if (TAMD_OPTIONS_HAS(have, profile)) o.profile = opt->profile;
+        if (TAMD_OPTIONS_HAS(have, direct_dispatch)) o.direct_dispatch = opt->direct_dispatch;
+        if (TAMD_OPTIONS_HAS(have, keep_tensors)) o.keep_tensors = opt->keep_tensors;
+        if (TAMD_OPTIONS_HAS(have, u8_integer)) o.u8_integer = opt->u8_integer;
     }
     if (const char* ui = getenv("TAMD_U8_INT")) o.u8_integer = atoi(ui) != 0;
     if (const char* dd = getenv("TAMD_DIRECT_DISPATCH")) o.direct_dispatch = atoi(dd) != 0;

@@ -221,7 +221,7 @@ int plan_f32(tamd_graph* g)
         case TAMD_OP_ELTWISE: {
             HTensor& xb = g->tensors[n.in[1]];
             const int type = n.p.elt.type;
-            if (x.dims != xb.dims || (type != 0 && type != 2 && type != 4 && type != 6)) { set_error("eltwise %s: broadcast / type %d unsupported", n.name.c_str(), type); return -1; }
+            if (x.dims != xb.dims || !eltwise_type_on_device(type)) { set_error("eltwise %s: broadcast / type %d unsupported", n.name.c_str(), type); return -1; }
             const float* pa = (const float*)x.dptr; const float* pb = (const float*)xb.dptr; float* py = (float*)y.dptr;
             const size_t cnt = x.elems();
             g->steps.push_back(make_step(n.name, "eltwise_f32", 0, 12.0 * cnt,

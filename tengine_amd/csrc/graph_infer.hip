@@ -276,6 +276,8 @@ int validate_graph(tamd_graph* g)
     for (auto& n : g->nodes) {
         // priorbox_ref.c fills image 0 of its output only (:99-175); what a batch > 1 tensor holds behind it is undefined there
         if (n.op == TAMD_OP_PRIORBOX && g->tensors[n.out[0]].dims[0] != 1) return bad(n, "PriorBox is defined for batch 1 only");
+        // the uint8 / fp32 planners and infer_shapes take the factor as an int: 1.5 would run as 1, 0.5 would give an empty tensor
+        if (n.op == TAMD_OP_UPSAMPLE && !upsample_factor_on_device(n.p.ups.scale)) return bad(n, "Upsample takes an integer factor >= 1");
         if (n.op != TAMD_OP_CONV && n.op != TAMD_OP_FC) continue;
         const HTensor& x = g->tensors[n.in[0]];
         HTensor& w = g->tensors[n.in[1]];

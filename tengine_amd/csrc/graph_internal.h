@@ -8,6 +8,7 @@
 //   graph_pair.hip        a batched graph as two half-batch graphs side by side behind one handle (tamd_options.split_batch)
 //   graph_exec.hip        run_steps, the direct path's self-checks, zero-copy lists, the run-side entry points
 // (graph_u8.hip and graph_f32.hip are the uint8 / fp32 planners, as before.)
+// node_rules.h (through graph.h) states once the node-local rules that the support query, validate_graph and the planners share.
 #pragma once
 #include <mutex>
 

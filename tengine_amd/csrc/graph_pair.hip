@@ -34,7 +34,8 @@ static tamd_graph* clone_ir(const tamd_graph* g)
     return c;
 }
 
-// operators that treat the images of a batch independently (the plugin's list, hip_device.cc: split_wanted)
+// operators that treat the images of a batch independently: the one list (the plugin asks for a split by batch size alone and
+// leaves this test to pair_try_prerun)
 static bool ops_allow_split(const tamd_graph* g)
 {
     for (auto& n : g->nodes)
@@ -75,8 +76,8 @@ int pair_try_prerun(tamd_graph* g, const tamd_options* opt)
     if (g->is_half || g->inputs.empty() || g->outputs.empty()) return 0;
     // tamd_options.split_batch: 0 default rule, 1 never, 2 wherever possible; TAMD_SPLIT_BATCH: 0 never, 1 default rule, 2 wherever possible
     int mode = 0, direct = 0;
-    if (opt && opt->size >= (int)(offsetof(tamd_options, split_batch) + sizeof(int))) mode = opt->split_batch;
-    if (opt && opt->size >= (int)(offsetof(tamd_options, direct_dispatch) + sizeof(int))) direct = opt->direct_dispatch;
+    if (opt && TAMD_OPTIONS_HAS(opt->size, split_batch)) mode = opt->split_batch;
+    if (opt && TAMD_OPTIONS_HAS(opt->size, direct_dispatch)) direct = opt->direct_dispatch;
     if (mode != 1 && mode != 2) mode = 0;      // (a caller compiled against round 5's struct of the same padded size passes padding here)
     if (mode == 1) return 0;                   // a caller that splits batches by itself (the plugin): final, the switch below is then ITS switch
     if (const char* e = getenv("TAMD_SPLIT_BATCH")) { const int v = atoi(e); mode = v == 0 ? 1 : v == 2 ? 2 : 0; }

@@ -188,8 +188,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
         const int yo = n.out[0];
         switch (n.op) {
         case TAMD_OP_PERMUTE: {
-            const int* o = n.p.perm.order;
-            if (x.dims.size() != 4 || L.dense[n.in[0]] || !(o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1)) {
+            if (x.dims.size() != 4 || L.dense[n.in[0]] || !permute_order_on_device(n.p.perm.order)) {
                 set_error("permute %s: only order (0, 2, 3, 1) of a 4-D convolution-stack tensor runs on the device", n.name.c_str());
                 return -1;
             }
@@ -438,7 +437,7 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
         HNode& e = g->nodes[ei];
         if (e.op != TAMD_OP_ELTWISE || e.in.size() != 2) continue;
         const int ty = e.p.elt.type;
-        if (ty != 0 && ty != 2 && ty != 4 && ty != 6) continue;
+        if (!eltwise_type_on_device(ty)) continue;
         HTensor& ta = g->tensors[e.in[0]];
         HTensor& tb = g->tensors[e.in[1]];
         HTensor& te = g->tensors[e.out[0]];
@@ -448,7 +447,7 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
         if (later < 0 || later >= (int)ei) continue;
         HNode& c = g->nodes[later];
         if (c.op != TAMD_OP_CONV || c.p.conv.group != 1 || g->tensors[c.in[0]].nchw_raw || L.has_fuse[later]) continue;
-        if (c.p.conv.kernel_h * c.p.conv.kernel_w > 128 || count_consumers(g, e.in[conv_in]) != 1) continue;
+        if (!conv_i8_gemm_taps_fit(c.p.conv.kernel_h, c.p.conv.kernel_w) || count_consumers(g, e.in[conv_in]) != 1) continue;
         FusedElt fz{};
         fz.res_tensor = e.in[1 - conv_in]; fz.elt_tensor = e.out[0]; fz.out_tensor = e.out[0]; fz.type = ty;
         fz.conv_is_first = conv_in == 0; fz.relu = false;
@@ -743,7 +742,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
     if (general) {
         // any axis of a dense tensor (the SSD tail: Reshape -> Softmax(axis 2) on [N, priors, classes]) and the spatial
         // axes of an NHWC tensor -- the same kernel with strided addressing (kernels.h: SoftmaxI8Args)
-        if (ax < 0 || ax >= (int)x.dims.size() || x.dims[ax] < 1 || x.dims[ax] > kSoftmaxI8MaxC) {
+        if (ax < 0 || ax >= (int)x.dims.size() || !softmax_i8_axis_fits(x.dims[ax])) {
             set_error("softmax %s: axis %d of at most %d values", n.name.c_str(), ax, kSoftmaxI8MaxC);
             return -1;
         }
@@ -768,7 +767,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
         g->steps.push_back(st);
         return 0;
     }
-    if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || x.c < 1 || x.c > kSoftmaxI8MaxC) {
+    if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || !softmax_i8_axis_fits(x.c)) {
         set_error("softmax %s is not supported on the device: int8 softmax runs over the channel axis of a 2-D / 4-D tensor of at most %d channels",
                   n.name.c_str(), kSoftmaxI8MaxC);
         return -1;
@@ -845,7 +844,7 @@ static int plan_upsample(tamd_graph* g, HNode& n)
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
     const int sc = (int)n.p.ups.scale;
-    if (x.dims.size() != 4 || sc < 1 || (float)sc != n.p.ups.scale) { set_error("upsample %s: only an integer factor of a 4-D tensor runs on the device", n.name.c_str()); return -1; }
+    if (x.dims.size() != 4 || !upsample_factor_on_device(n.p.ups.scale)) { set_error("upsample %s: only an integer factor of a 4-D tensor runs on the device", n.name.c_str()); return -1; }
     if (x.scales.empty() || y.scales.empty()) { set_error("upsample %s: missing quant params", n.name.c_str()); return -1; }
     if (y.n != x.n || y.c != x.c || y.h != x.h * sc || y.w != x.w * sc) { set_error("upsample %s: output shape mismatch", n.name.c_str()); return -1; }
     // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
@@ -874,7 +873,7 @@ static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, size_t ni)
     EltArgs a{};
     a.a = (const int8_t*)xa.dptr; a.b = (const int8_t*)xb.dptr; a.count = (size_t)xa.n * xa.h * xa.w * xa.cs;
     a.type = n.p.elt.type; a.sa = xa.scales[0]; a.sb = xb.scales[0]; a.out_scale = y->scales[0];
-    if (a.type != 0 && a.type != 2 && a.type != 4 && a.type != 6) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
+    if (!eltwise_type_on_device(a.type)) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
     std::string kname = "eltwise_i8";
     double bytes = 3.0 * xa.n * xa.h * xa.w * xa.c;
     // fuse the standalone ReLU that follows (ResNet: 16 x eltwise -> relu), SURVEY §8f-1

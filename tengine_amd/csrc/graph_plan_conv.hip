@@ -289,7 +289,7 @@ static int conv_i8_gemm_args(ConvI8& c, ConvArgs* args, std::vector<int8_t>* wp)
     const int ktot = KH * KW * ckp;
     const int kpad = rup(ktot, 64);
     const int cout_pad = rup(cout, 128);
-    if (KH * KW > 128) { set_error("conv %s: kernel %dx%d too large", c.n.name.c_str(), KH, KW); return -1; }
+    if (!conv_i8_gemm_taps_fit(KH, KW)) { set_error("conv %s: kernel %dx%d too large", c.n.name.c_str(), KH, KW); return -1; }
     wp->assign((size_t)cout_pad * kpad + 256, 0);      // + tail: deep-K stages may read past the last row
     for (int co = 0; co < cout; co++)
         for (int ci = 0; ci < cin; ci++)

@@ -599,7 +599,7 @@ static int plan_fc_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
     if (q_of(x, &qx, "tensor") || q_of(w, &qw, "weight") || q_of(y, &qy, "tensor")) return -1;
     const int batch = x.dims[0], hidden = (int)(x.elems() / batch), nout = y.c, nout_pad = rup(nout, 64);
     if (w.dtype != TAMD_DT_UINT8 || (size_t)hidden * nout != w.data.size()) { set_error("fc %s: weight mismatch", n.name.c_str()); return -1; }
-    if (hidden * 4 > 60000) { set_error("fc %s: hidden %d too large for the LDS row", n.name.c_str(), hidden); return -1; }
+    if (!fc_u8_row_fits_lds((size_t)hidden)) { set_error("fc %s: hidden %d too large for the LDS row", n.name.c_str(), hidden); return -1; }
     std::vector<float> wf((size_t)hidden * nout_pad, 0.f);
     for (int o = 0; o < nout; o++)
         for (int j = 0; j < hidden; j++)
@@ -661,8 +661,7 @@ static int plan_map_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* out)
 
 static int plan_permute_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* out)
 {
-    const int* o = n.p.perm.order;
-    if (!(o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1)) { set_error("permute %s: only order (0,2,3,1) is supported on the device", n.name.c_str()); return -1; }
+    if (!permute_order_on_device(n.p.perm.order)) { set_error("permute %s: only order (0,2,3,1) is supported on the device", n.name.c_str()); return -1; }
     U8CatArgs a{};
     a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
     a.N = x.dims[0]; a.in_img = (int)(x.elems() / x.dims[0]);
@@ -764,7 +763,7 @@ static int plan_eltwise_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
     U8EltArgs a{};
     a.a = (const uint8_t*)xa.dptr; a.b = (const uint8_t*)xb.dptr; a.y = (uint8_t*)y.dptr;
     a.count = xa.elems(); a.type = n.p.elt.type;
-    if (a.type != 0 && a.type != 2 && a.type != 4 && a.type != 6) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
+    if (!eltwise_type_on_device(a.type)) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
     if (q_of(xa, &a.qa, "tensor") || q_of(xb, &a.qb, "tensor") || q_of(y, &a.out, "tensor")) return -1;
     out->push_back(make_step(n.name, "eltwise_u8", 0, 3.0 * xa.elems(), [a](hipStream_t s) { return launch_eltwise_u8(a, s); }));
     return 0;
@@ -783,8 +782,7 @@ static std::vector<int> find_permute_concats(const tamd_graph* g, std::vector<ch
     if (pe && atoi(pe) == 0) return perm_src;
     for (size_t pi = 0; pi < g->nodes.size(); pi++) {
         const HNode& pn = g->nodes[pi];
-        const int* o = pn.p.perm.order;
-        if (pn.op != TAMD_OP_PERMUTE || !(o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1)) continue;
+        if (pn.op != TAMD_OP_PERMUTE || !permute_order_on_device(pn.p.perm.order)) continue;
         if (count_consumers(g, pn.out[0]) != 1) continue;
         const HNode* fl = nullptr;
         for (auto& m : g->nodes)

@@ -1,0 +1,31 @@
+// Node-local rules that the support query (graph.hip: tamd_node_supported), validate_graph and the planners all apply: each is
+// stated here once, with the reason for its number.  Only rules that are written at more than one site live here; what a single
+// planner alone decides stays in that planner.
+#pragma once
+#include "kernels.h"
+
+namespace tamd {
+
+// Eltwise: the binary forms over two tensors of one shape -- ELT_PROD 0, ELT_SUM 2, ELT_SUB 4, ELT_MAX 6 (eltwise_param.h); the odd
+// values next to them are the tensor-with-scalar forms, 7 and up the unary ones: no device kernel for those
+inline bool eltwise_type_on_device(int type) { return type == 0 || type == 2 || type == 4 || type == 6; }
+
+// Permute: NCHW -> NHWC, the one order SSD heads use (Permute -> Flatten -> Concat)
+inline bool permute_order_on_device(const int* o) { return o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1; }
+
+// uint8 FC: fc_u8 keeps the dequantised input row of one image in LDS as floats (u8_kernels.hip: xrow), 4 bytes per value, inside
+// the 64 KB a block may take
+inline bool fc_u8_row_fits_lds(size_t hidden) { return hidden * 4 <= 60000; }
+
+// int8 implicit GEMM: the (ky, kx) offsets of a kernel window sit in an LDS table of 128 entries (conv_igemm.hip: tap_lut).  The
+// first-layer, depthwise and generic direct forms have no such table.
+inline bool conv_i8_gemm_taps_fit(int kernel_h, int kernel_w) { return kernel_h * kernel_w <= 128; }
+
+// int8 softmax: the exponentials of one axis live in LDS as floats (kSoftmaxI8MaxC, kernels.h)
+inline bool softmax_i8_axis_fits(int len) { return len >= 1 && len <= kSoftmaxI8MaxC; }
+
+// Upsample: nearest neighbour by a whole factor >= 1 (upsample_ref.c indexes with 1 / scale; the device kernels take an int, and
+// shape inference multiplies by it)
+inline bool upsample_factor_on_device(float scale) { return scale >= 1.f && scale == (float)(int)scale; }
+
+}  // namespace tamd

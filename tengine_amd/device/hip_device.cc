@@ -68,37 +68,39 @@ struct HipSubgraph {
     std::vector<uint16_t> in_ir, out_ir;   // ir tensor indices of the subgraph inputs / outputs, in tamd order
 };
 
-// OP_* (source/operator/op.h:38-145) -> TAMD_OP_*
-int map_op(int op)
+// The operators the plugin hands to the device: OP_* (source/operator/op.h:38-145) -> TAMD_OP_*.  quantised_only: SSD head plumbing
+// (Permute -> Flatten -> Concat, Reshape, PriorBox), on the device for the QUANTISED graphs (uint8 since round 3, int8 since round 6:
+// csrc/graph_plan.hip "dense tensors") -- an fp32 graph keeps these on the CPU without dragging the convolutions around them back there
+struct OpRow { int op; int tamd_op; bool quantised_only; };
+const OpRow kOps[] = {
+    {OP_INPUT, TAMD_OP_INPUT, false},       {OP_CONST, TAMD_OP_CONST, false},     {OP_CONV, TAMD_OP_CONV, false},
+    {OP_FC, TAMD_OP_FC, false},             {OP_POOL, TAMD_OP_POOL, false},       {OP_RELU, TAMD_OP_RELU, false},
+    {OP_ELTWISE, TAMD_OP_ELTWISE, false},   {OP_CONCAT, TAMD_OP_CONCAT, false},   {OP_DROPOUT, TAMD_OP_DROPOUT, false},
+    {OP_UPSAMPLE, TAMD_OP_UPSAMPLE, false}, {OP_SOFTMAX, TAMD_OP_SOFTMAX, false}, {OP_RELU6, TAMD_OP_RELU6, false},
+    {OP_PERMUTE, TAMD_OP_PERMUTE, true},    {OP_FLATTEN, TAMD_OP_FLATTEN, true},  {OP_RESHAPE, TAMD_OP_RESHAPE, true},
+    {OP_PRIORBOX, TAMD_OP_PRIORBOX, true},
+};
+
+const OpRow* find_op(int op)
 {
-    switch (op) {
-    case OP_INPUT: return TAMD_OP_INPUT;
-    case OP_CONST: return TAMD_OP_CONST;
-    case OP_CONV: return TAMD_OP_CONV;
-    case OP_FC: return TAMD_OP_FC;
-    case OP_POOL: return TAMD_OP_POOL;
-    case OP_RELU: return TAMD_OP_RELU;
-    case OP_ELTWISE: return TAMD_OP_ELTWISE;
-    case OP_CONCAT: return TAMD_OP_CONCAT;
-    case OP_DROPOUT: return TAMD_OP_DROPOUT;
-    case OP_UPSAMPLE: return TAMD_OP_UPSAMPLE;
-    case OP_SOFTMAX: return TAMD_OP_SOFTMAX;
-    case OP_RELU6: return TAMD_OP_RELU6;
-    case OP_FLATTEN: return TAMD_OP_FLATTEN;
-    case OP_PERMUTE: return TAMD_OP_PERMUTE;
-    case OP_RESHAPE: return TAMD_OP_RESHAPE;
-    case OP_PRIORBOX: return TAMD_OP_PRIORBOX;
-    default: return -1;
-    }
+    for (const OpRow& r : kOps)
+        if (r.op == op) return &r;
+    return nullptr;
 }
 
-const int kSupportedOps[] = {OP_INPUT, OP_CONST, OP_CONV, OP_FC, OP_POOL, OP_RELU, OP_ELTWISE, OP_CONCAT, OP_DROPOUT, OP_UPSAMPLE,
-                             OP_SOFTMAX, OP_RELU6};
+int map_op(int op)
+{
+    const OpRow* r = find_op(op);
+    return r ? r->tamd_op : -1;
+}
 
-// SSD head plumbing (Permute -> Flatten -> Concat, Reshape, PriorBox): on the device for the QUANTISED graphs (uint8 since round 3,
-// int8 since round 6: csrc/graph_plan.hip "dense tensors"), so these are added to the allowed list per graph (hip_split_graph)
-// instead of globally -- an fp32 graph keeps them on the CPU without dragging the convolutions around them back there
-const int kQuantisedOnlyOps[] = {OP_PERMUTE, OP_FLATTEN, OP_RESHAPE, OP_PRIORBOX};
+// may a graph of activation type `dtype` (-1: unknown) hand this operator to the device at all?
+bool op_supported(int op, int dtype)
+{
+    const OpRow* r = find_op(op);
+    return r && (!r->quantised_only || dtype == TENGINE_DT_UINT8 || dtype == TENGINE_DT_INT8);
+}
+
 
 // struct priorbox_param (priorbox_param.h:28-52, float vectors on the heap) -> the inline-array form of the C ABI
 bool translate_priorbox(const struct priorbox_param* p, tamd_priorbox_param* q)
@@ -116,14 +118,75 @@ bool translate_priorbox(const struct priorbox_param* p, tamd_priorbox_param* q)
     return true;
 }
 
-bool op_supported(int op, int dtype)
+// descriptor of an IR tensor.  with_payload: the constant's bytes and the quantisation values travel too (pre_run); without, shapes
+// and the quantisation form alone (tamd_node_supported looks at nothing else).  The pointers stay the IR tensor's own.
+tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 {
-    for (int o : kSupportedOps)
-        if (o == op) return true;
-    if (dtype == TENGINE_DT_UINT8 || dtype == TENGINE_DT_INT8)
-        for (int o : kQuantisedOnlyOps)
-            if (o == op) return true;
-    return false;
+    tamd_tensor_desc d;
+    memset(&d, 0, sizeof(d));
+    d.dtype = t->data_type; d.ttype = t->tensor_type; d.dim_num = t->dim_num;
+    for (int i = 0; i < t->dim_num && i < 8; i++) d.dims[i] = t->dims[i];
+    d.quant_num = t->quant_param_num;
+    d.name = t->name;
+    if (!with_payload) return d;
+    d.data = (t->tensor_type == TENSOR_TYPE_CONST) ? t->data : nullptr;
+    if (t->quant_param_num == 1) { d.scales = &t->scale; d.zero_points = &t->zero_point; }      // (tensor.h:84-98: value and list share a union)
+    else if (t->quant_param_num > 1) { d.scales = t->scale_list; d.zero_points = t->zp_list; }
+    return d;
+}
+
+// IR node -> the parameter struct the C ABI takes for its operator: written into `s`, *param points at it (nullptr: the operator has
+// none).  The one translation: pre_run and the support query of the splitter both come here.  false: a PriorBox the ABI cannot carry.
+union NodeParams {
+    tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
+    tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
+};
+
+bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
+{
+    *param = s;
+    switch (map_op(n->op.type)) {
+    case TAMD_OP_PRIORBOX: return translate_priorbox((const struct priorbox_param*)n->op.param_mem, &s->priorbox);
+    case TAMD_OP_SOFTMAX: s->softmax.axis = ((const struct softmax_param*)n->op.param_mem)->axis; break;
+    case TAMD_OP_RESHAPE: {          // the resolved shape (reshape.c infer_shape already ran)
+        struct tensor* ot = get_ir_graph_tensor(ir, n->output_tensors[0]);
+        s->reshape.dim_num = ot->dim_num;
+        for (int k = 0; k < ot->dim_num && k < 8; k++) s->reshape.dims[k] = ot->dims[k];
+        break;
+    }
+    case TAMD_OP_CONV: {
+        const struct conv_param* p = (const struct conv_param*)n->op.param_mem;
+        s->conv = {p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0, p->pad_h1, p->pad_w0, p->pad_w1,
+                   p->dilation_h, p->dilation_w, p->input_channel, p->output_channel, p->group, p->activation};
+        break;
+    }
+    case TAMD_OP_POOL: {
+        const struct pool_param* p = (const struct pool_param*)n->op.param_mem;
+        // hand over the ORIGINAL (model) pads: the backend re-resolves them like infer_shape does
+        s->pool = {p->pool_method, p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0_org, p->pad_h1_org,
+                   p->pad_w0_org, p->pad_w1_org, p->global, p->caffe_flavor};
+        if (p->global) {   // infer_shape already rewrote kernel/stride for global pooling (pooling.c:52-66)
+            s->pool.pad_h0 = s->pool.pad_h1 = s->pool.pad_w0 = s->pool.pad_w1 = 0;
+        }
+        break;
+    }
+    case TAMD_OP_FC: s->fc.num_output = ((const struct fc_param*)n->op.param_mem)->num_output; break;
+    case TAMD_OP_RELU: s->relu.negative_slope = ((const struct relu_param*)n->op.param_mem)->negative_slope; break;
+    case TAMD_OP_ELTWISE: {
+        const struct eltwise_param* p = (const struct eltwise_param*)n->op.param_mem;
+        s->elt = {p->type, p->caffe_flavor, p->shift, p->power, p->scale};
+        break;
+    }
+    case TAMD_OP_CONCAT: s->concat.axis = ((const struct concat_param*)n->op.param_mem)->axis; break;
+    case TAMD_OP_UPSAMPLE: s->ups.scale = ((const struct upsample_param*)n->op.param_mem)->scale; break;
+    case TAMD_OP_PERMUTE: {
+        const struct permute_param* p = (const struct permute_param*)n->op.param_mem;
+        s->perm = {{p->order0, p->order1, p->order2, p->order3}};
+        break;
+    }
+    default: *param = nullptr; break;
+    }
+    return true;
 }
 
 int hip_dev_init(struct device* dev)
@@ -136,45 +199,29 @@ int hip_dev_init(struct device* dev)
 
 int g_split_subgraphs = 0;       // subgraphs preran as two half-batch graphs since the plugin was loaded (hip_device_split_subgraphs: tests)
 
-// Does this subgraph run as two half-batch device graphs?  TAMD_SPLIT_BATCH=0: never; =2: whenever it is possible (tests); default: from
-// batch 8 on.  Possible = an even batch B carried as dimension 0 by EVERY activation tensor of the subgraph (inputs and outputs included:
-// their host buffers are then two contiguous halves), and only operators that treat the images of a batch independently.
+// Does this subgraph ask the library for two half-batch device graphs?  What only the plugin knows: its switch (TAMD_SPLIT_BATCH=0:
+// never; =2: from batch 2 on (tests); default: from batch 8 on) and the batch, dimension 0 of the subgraph's non-constant inputs -- all
+// of them, or there is no batch to speak of.  Whether the operators treat the images of a batch independently and every activation
+// tensor carries the batch in front is the library's test (csrc/graph_pair.hip: pair_try_prerun keeps one launch list where it fails).
 bool split_wanted(struct graph* ir, struct subgraph* subgraph)
 {
     const char* e = getenv("TAMD_SPLIT_BATCH");
     const int mode = e ? atoi(e) : 1;
-    if (mode == 0 || subgraph->input_num < 1) return false;
+    if (mode == 0) return false;
     int B = 0;
-    for (int i = 0; i < subgraph->node_num; i++) {
-        struct node* n = get_ir_graph_node(ir, subgraph->node_list[i]);
-        switch (map_op(n->op.type)) {
-        case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU: case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT: break;
-        case TAMD_OP_CONCAT: if (((const struct concat_param*)n->op.param_mem)->axis < 1) return false; break;
-        case TAMD_OP_SOFTMAX: if (((const struct softmax_param*)n->op.param_mem)->axis < 1) return false; break;
-        case TAMD_OP_INPUT: case TAMD_OP_CONST: continue;
-        default: return false;
-        }
-        for (int k = 0; k < n->input_num + n->output_num; k++) {
-            struct tensor* t = get_ir_graph_tensor(ir, k < n->input_num ? n->input_tensors[k] : n->output_tensors[k - n->input_num]);
-            if (t->tensor_type == TENSOR_TYPE_CONST) continue;
-            if (t->dim_num < 2 || t->dims[0] < 2) return false;
-            if (B == 0) B = t->dims[0];
-            if (t->dims[0] != B) return false;
-        }
+    for (int i = 0; i < subgraph->input_num; i++) {
+        struct tensor* t = get_ir_graph_tensor(ir, subgraph->input_tensor_list[i]);
+        if (t->tensor_type == TENSOR_TYPE_CONST) continue;
+        if (t->dim_num < 1 || (B != 0 && t->dims[0] != B)) return false;
+        B = t->dims[0];
     }
     return B >= (mode == 2 ? 2 : 8) && B % 2 == 0;          // (profiles/r06_plugin_split_threshold.txt: batch 8 +1 .. +22 %, batch 4 0 .. +3 %, batch 2 -3 .. +2 %)
 }
 
-int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
+// the device graph of a subgraph; hs->in_ir / out_ir: its inputs / outputs as IR tensor indices, in tamd order
+tamd_graph* build_device_graph(struct graph* ir, struct subgraph* subgraph, HipSubgraph* hs)
 {
-    (void)dev;
-    struct graph* ir = subgraph->graph;
-    HipSubgraph* hs = new HipSubgraph();
-    // builds the device graph of this subgraph; div 2: every activation tensor with half the batch (split_wanted() has checked that all
-    // of them carry the batch as their first dimension)
-    auto build = [&](int div) -> tamd_graph* {
     tamd_graph* tg = tamd_graph_create();
-    hs->in_ir.clear(); hs->out_ir.clear();
     std::map<int, int> tmap;   // ir tensor index -> tamd tensor index
 
     auto is_sub_input = [&](uint16_t t) {
@@ -186,30 +233,18 @@ int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
         auto it = tmap.find(idx);
         if (it != tmap.end()) return it->second;
         struct tensor* t = get_ir_graph_tensor(ir, idx);
-        tamd_tensor_desc d;
-        memset(&d, 0, sizeof(d));
-        d.dtype = t->data_type;
-        d.ttype = t->tensor_type;
+        tamd_tensor_desc d = describe_tensor(t, true);
         if (t->tensor_type == TENSOR_TYPE_VAR && is_sub_input(idx)) d.ttype = TAMD_TT_INPUT;   // produced by another subgraph
-        d.dim_num = t->dim_num;
-        for (int i = 0; i < t->dim_num && i < 8; i++) d.dims[i] = t->dims[i];
-        if (div > 1 && t->tensor_type != TENSOR_TYPE_CONST && t->dim_num >= 1) d.dims[0] /= div;
-        d.data = (t->tensor_type == TENSOR_TYPE_CONST) ? t->data : nullptr;
-        d.quant_num = t->quant_param_num;
-        float one_scale = t->scale;
-        int one_zp = t->zero_point;
-        if (t->quant_param_num == 1) { d.scales = &one_scale; d.zero_points = &one_zp; }
-        else if (t->quant_param_num > 1) { d.scales = t->scale_list; d.zero_points = t->zp_list; }
-        d.name = t->name;
-        int id = tamd_graph_add_tensor(tg, &d);
-        tmap[idx] = id;
-        return id;
+        return tmap[idx] = tamd_graph_add_tensor(tg, &d);
     };
 
     for (int i = 0; i < subgraph->node_num; i++) {
         struct node* n = get_ir_graph_node(ir, subgraph->node_list[i]);
-        int op = map_op(n->op.type);
-        if (op < 0) {
+        NodeParams params;
+        tamd_node_desc nd;
+        memset(&nd, 0, sizeof(nd));
+        nd.op = map_op(n->op.type);
+        if (nd.op < 0 || !translate_node(ir, n, &params, &nd.param)) {
             TLOG_ERR("Tengine HIP: op %d (%s) is not supported on the device\n", n->op.type, n->name ? n->name : "?");
             tamd_graph_destroy(tg);
             return nullptr;
@@ -217,70 +252,7 @@ int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
         std::vector<int> ins, outs;
         for (int k = 0; k < n->input_num; k++) ins.push_back(add_tensor(n->input_tensors[k]));
         for (int k = 0; k < n->output_num; k++) outs.push_back(add_tensor(n->output_tensors[k]));
-        tamd_conv_param cp;
-        tamd_pool_param pp;
-        tamd_fc_param fp;
-        tamd_relu_param rp;
-        tamd_eltwise_param ep;
-        tamd_concat_param ccp;
-        tamd_upsample_param up;
-        tamd_permute_param pmp;
-        tamd_softmax_param smp;
-        tamd_reshape_param rsp;
-        tamd_priorbox_param pbp;
-        const void* param = nullptr;
-        switch (op) {
-        case TAMD_OP_PRIORBOX:
-            if (translate_priorbox((const struct priorbox_param*)n->op.param_mem, &pbp)) param = &pbp;
-            break;
-        case TAMD_OP_SOFTMAX: smp.axis = ((const struct softmax_param*)n->op.param_mem)->axis; param = &smp; break;
-        case TAMD_OP_RESHAPE: {          // the resolved shape (reshape.c infer_shape already ran)
-            struct tensor* ot = get_ir_graph_tensor(ir, n->output_tensors[0]);
-            rsp.dim_num = ot->dim_num;
-            for (int k = 0; k < ot->dim_num && k < 8; k++) rsp.dims[k] = ot->dims[k];
-            param = &rsp;
-            break;
-        }
-        case TAMD_OP_CONV: {
-            const struct conv_param* p = (const struct conv_param*)n->op.param_mem;
-            cp = {p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0, p->pad_h1, p->pad_w0, p->pad_w1,
-                  p->dilation_h, p->dilation_w, p->input_channel, p->output_channel, p->group, p->activation};
-            param = &cp;
-            break;
-        }
-        case TAMD_OP_POOL: {
-            const struct pool_param* p = (const struct pool_param*)n->op.param_mem;
-            // hand over the ORIGINAL (model) pads: the backend re-resolves them like infer_shape does
-            pp = {p->pool_method, p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0_org, p->pad_h1_org,
-                  p->pad_w0_org, p->pad_w1_org, p->global, p->caffe_flavor};
-            if (p->global) {   // infer_shape already rewrote kernel/stride for global pooling (pooling.c:52-66)
-                pp.pad_h0 = pp.pad_h1 = pp.pad_w0 = pp.pad_w1 = 0;
-            }
-            param = &pp;
-            break;
-        }
-        case TAMD_OP_FC: fp.num_output = ((const struct fc_param*)n->op.param_mem)->num_output; param = &fp; break;
-        case TAMD_OP_RELU: rp.negative_slope = ((const struct relu_param*)n->op.param_mem)->negative_slope; param = &rp; break;
-        case TAMD_OP_ELTWISE: {
-            const struct eltwise_param* p = (const struct eltwise_param*)n->op.param_mem;
-            ep = {p->type, p->caffe_flavor, p->shift, p->power, p->scale};
-            param = &ep;
-            break;
-        }
-        case TAMD_OP_CONCAT: ccp.axis = ((const struct concat_param*)n->op.param_mem)->axis; param = &ccp; break;
-        case TAMD_OP_UPSAMPLE: up.scale = ((const struct upsample_param*)n->op.param_mem)->scale; param = &up; break;
-        case TAMD_OP_PERMUTE: {
-            const struct permute_param* p = (const struct permute_param*)n->op.param_mem;
-            pmp = {{p->order0, p->order1, p->order2, p->order3}};
-            param = &pmp;
-            break;
-        }
-        default: break;
-        }
-        tamd_node_desc nd;
-        memset(&nd, 0, sizeof(nd));
-        nd.op = op; nd.input_num = (int)ins.size(); nd.inputs = ins.data(); nd.output_num = (int)outs.size();
-        nd.outputs = outs.data(); nd.param = param; nd.name = n->name;
+        nd.input_num = (int)ins.size(); nd.inputs = ins.data(); nd.output_num = (int)outs.size(); nd.outputs = outs.data(); nd.name = n->name;
         if (tamd_graph_add_node(tg, &nd) < 0) {
             TLOG_ERR("Tengine HIP: %s\n", tamd_last_error());
             tamd_graph_destroy(tg);
@@ -305,8 +277,14 @@ int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
     tamd_graph_set_inputs(tg, (int)gi.size(), gi.data());
     tamd_graph_set_outputs(tg, (int)go.size(), go.data());
     return tg;
-    };
-    hs->g = build(1);
+}
+
+int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
+{
+    (void)dev;
+    struct graph* ir = subgraph->graph;
+    HipSubgraph* hs = new HipSubgraph();
+    hs->g = build_device_graph(ir, subgraph, hs);
     if (!hs->g) { delete hs; return -1; }
 
     tamd_options opt;
@@ -320,12 +298,12 @@ int hip_dev_prerun(struct device* dev, struct subgraph* subgraph, void* options)
         const tamd_options* o = (const tamd_options*)options;
         if (o->dev_name && 0 == strcmp(o->dev_name, HIP_DEV_NAME)) {
             const int have = o->size;
-            if (have >= (int)(offsetof(tamd_options, gpu_index) + sizeof(int))) opt.gpu_index = o->gpu_index;
-            if (have >= (int)(offsetof(tamd_options, use_hip_graph) + sizeof(int))) opt.use_hip_graph = o->use_hip_graph;
-            if (have >= (int)(offsetof(tamd_options, profile) + sizeof(int))) opt.profile = o->profile;
-            if (have >= (int)(offsetof(tamd_options, direct_dispatch) + sizeof(int))) opt.direct_dispatch = o->direct_dispatch;
-            if (have >= (int)(offsetof(tamd_options, keep_tensors) + sizeof(int))) opt.keep_tensors = o->keep_tensors;
-            if (have >= (int)(offsetof(tamd_options, u8_integer) + sizeof(int))) opt.u8_integer = o->u8_integer;
+            if (TAMD_OPTIONS_HAS(have, gpu_index)) opt.gpu_index = o->gpu_index;
+            if (TAMD_OPTIONS_HAS(have, use_hip_graph)) opt.use_hip_graph = o->use_hip_graph;
+            if (TAMD_OPTIONS_HAS(have, profile)) opt.profile = o->profile;
+            if (TAMD_OPTIONS_HAS(have, direct_dispatch)) opt.direct_dispatch = o->direct_dispatch;
+            if (TAMD_OPTIONS_HAS(have, keep_tensors)) opt.keep_tensors = o->keep_tensors;
+            if (TAMD_OPTIONS_HAS(have, u8_integer)) opt.u8_integer = o->u8_integer;
         }
     }
     const char* env = getenv("TG_HIP_DEVICE");
@@ -435,25 +413,20 @@ int hip_dev_release(struct device* dev)
     return tamd_shutdown();
 }
 
-// allowed / blocked operator lists for a graph of activation type `dtype` (-1: unknown)
-void fill_op_lists(struct vector* allowed_ops, struct vector* blocked_ops, int dtype)
+// allowed / blocked operator lists for a graph of activation type `dtype` (-1: unknown), and the precisions of the device
+void fill_op_lists(struct vector* allowed_ops, struct vector* blocked_ops, struct vector* precision, int dtype)
 {
     for (int i = 0; i < OP_BUILTIN_LAST; i++) {
         if (op_supported(i, dtype)) push_vector_data(allowed_ops, &i);
         else push_vector_data(blocked_ops, &i);
     }
+    for (int p : {TENGINE_DT_INT8, TENGINE_DT_UINT8, TENGINE_DT_FP32}) push_vector_data(precision, &p);
 }
 
 int hip_describe(struct device* device, struct vector* allowed_ops, struct vector* blocked_ops, struct vector* precision)
 {
     (void)device;
-    fill_op_lists(allowed_ops, blocked_ops, -1);
-    int p = TENGINE_DT_INT8;
-    push_vector_data(precision, &p);
-    p = TENGINE_DT_UINT8;
-    push_vector_data(precision, &p);
-    p = TENGINE_DT_FP32;
-    push_vector_data(precision, &p);
+    fill_op_lists(allowed_ops, blocked_ops, precision, -1);
     return 0;
 }
 
@@ -480,82 +453,22 @@ int hip_release(struct device* device, struct subgraph* sub_graph)
     return device ? 0 : -1;
 }
 
-// descriptor of an IR tensor (no payload: tamd_node_supported looks at shapes and quantisation only)
-static tamd_tensor_desc describe_tensor(struct tensor* t)
-{
-    tamd_tensor_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = t->data_type; d.ttype = t->tensor_type; d.dim_num = t->dim_num;
-    for (int i = 0; i < t->dim_num && i < 8; i++) d.dims[i] = t->dims[i];
-    d.quant_num = t->quant_param_num;
-    d.name = t->name;
-    return d;
-}
-
-// parameters the C ABI takes, from the IR node (the same translation pre_run does)
+// the node as the C ABI describes it (the same translation pre_run does), asked of the backend itself
 static bool node_supported(struct graph* ir, struct node* n)
 {
     const int op = map_op(n->op.type);
     if (op < 0) return false;
     if (op == TAMD_OP_INPUT || op == TAMD_OP_CONST) return true;
     std::vector<tamd_tensor_desc> in, out;
-    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k])));
-    for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k])));
-    tamd_conv_param cp; tamd_pool_param pp; tamd_fc_param fp; tamd_eltwise_param ep; tamd_concat_param ccp; tamd_upsample_param up;
-    tamd_permute_param pmp;
-    tamd_softmax_param smp;
-    tamd_reshape_param rsp;
-    tamd_priorbox_param pbp;
-    const void* param = nullptr;
-    switch (op) {
-    case TAMD_OP_PRIORBOX:
-        if (!translate_priorbox((const struct priorbox_param*)n->op.param_mem, &pbp)) return false;
-        param = &pbp;
-        break;
-    case TAMD_OP_SOFTMAX: smp.axis = ((const struct softmax_param*)n->op.param_mem)->axis; param = &smp; break;
-    case TAMD_OP_RESHAPE: {
-        struct tensor* ot = get_ir_graph_tensor(ir, n->output_tensors[0]);
-        rsp.dim_num = ot->dim_num;
-        for (int k = 0; k < ot->dim_num && k < 8; k++) rsp.dims[k] = ot->dims[k];
-        param = &rsp;
-        break;
-    }
-    case TAMD_OP_CONV: {
-        const struct conv_param* p = (const struct conv_param*)n->op.param_mem;
-        cp = {p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0, p->pad_h1, p->pad_w0, p->pad_w1,
-              p->dilation_h, p->dilation_w, p->input_channel, p->output_channel, p->group, p->activation};
-        param = &cp;
-        break;
-    }
-    case TAMD_OP_POOL: {
-        const struct pool_param* p = (const struct pool_param*)n->op.param_mem;
-        pp = {p->pool_method, p->kernel_h, p->kernel_w, p->stride_h, p->stride_w, p->pad_h0_org, p->pad_h1_org, p->pad_w0_org,
-              p->pad_w1_org, p->global, p->caffe_flavor};
-        param = &pp;
-        break;
-    }
-    case TAMD_OP_FC: fp.num_output = ((const struct fc_param*)n->op.param_mem)->num_output; param = &fp; break;
-    case TAMD_OP_ELTWISE: {
-        const struct eltwise_param* p = (const struct eltwise_param*)n->op.param_mem;
-        ep = {p->type, p->caffe_flavor, p->shift, p->power, p->scale};
-        param = &ep;
-        break;
-    }
-    case TAMD_OP_CONCAT: ccp.axis = ((const struct concat_param*)n->op.param_mem)->axis; param = &ccp; break;
-    case TAMD_OP_UPSAMPLE: up.scale = ((const struct upsample_param*)n->op.param_mem)->scale; param = &up; break;
-    case TAMD_OP_PERMUTE: {
-        const struct permute_param* p = (const struct permute_param*)n->op.param_mem;
-        pmp = {{p->order0, p->order1, p->order2, p->order3}};
-        param = &pmp;
-        break;
-    }
-    default: break;
-    }
+    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), false));
+    for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), false));
+    NodeParams params;
     std::vector<int> ii(in.size()), oi(out.size());
     tamd_node_desc nd;
     memset(&nd, 0, sizeof(nd));
+    if (!translate_node(ir, n, &params, &nd.param)) return false;
     nd.op = op; nd.input_num = (int)in.size(); nd.inputs = ii.data(); nd.output_num = (int)out.size(); nd.outputs = oi.data();
-    nd.param = param; nd.name = n->name;
+    nd.name = n->name;
     return tamd_node_supported(&nd, in.data(), (int)in.size(), out.data(), (int)out.size()) == 1;
 }
 
@@ -594,10 +507,6 @@ bool node_runs_on_device(struct graph* ir, struct node* n)
         if (t->data_type != TENGINE_DT_INT8 && t->data_type != TENGINE_DT_UINT8 && t->data_type != TENGINE_DT_FP32) return false;
         if (!tamd_op_supported(map_op(n->op.type), t->data_type)) return false;
         if (t->data_type != TENGINE_DT_FP32 && t->quant_param_num != 1) return false;
-    }
-    if (n->op.type == OP_ELTWISE) {
-        const int ty = ((const struct eltwise_param*)n->op.param_mem)->type;
-        if (ty != ELT_PROD && ty != ELT_SUM && ty != ELT_SUB && ty != ELT_MAX) return false;
     }
     if (n->op.type == OP_FLATTEN && ((const struct flatten_param*)n->op.param_mem)->axis != 1) return false;
     if (n->op.type == OP_SOFTMAX && out_dt == TENGINE_DT_INT8 && n->input_num >= 1) {
@@ -886,22 +795,15 @@ int hip_split_graph(struct graph* ir_graph)
     if (!(getenv("TG_HIP_SCHEDULER") && atoi(getenv("TG_HIP_SCHEDULER")) == 0))
         ir_graph->attribute->context->scheduler = &hip_scheduler;      // (the context is counted when this graph's prerun succeeds: hip_sched_prerun)
 
-    struct vector* allowed_ops = create_vector(sizeof(int), nullptr);
-    struct vector* blocked_ops = create_vector(sizeof(int), nullptr);
-    struct vector* precision = create_vector(sizeof(int), nullptr);
-    cur_dev->allocator->describe(cur_dev, allowed_ops, blocked_ops, precision);
     int graph_dt = -1;
     if (ir_graph->input_num > 0) {
         struct node* in_node = get_ir_graph_node(ir_graph, ir_graph->input_nodes[0]);
         if (in_node->output_num > 0) graph_dt = get_ir_graph_tensor(ir_graph, in_node->output_tensors[0])->data_type;
     }
-    if (graph_dt == TENGINE_DT_UINT8 || graph_dt == TENGINE_DT_INT8) {          // the quantised-only operators join the allowed list for this graph
-        release_vector(allowed_ops);
-        release_vector(blocked_ops);
-        allowed_ops = create_vector(sizeof(int), nullptr);
-        blocked_ops = create_vector(sizeof(int), nullptr);
-        fill_op_lists(allowed_ops, blocked_ops, graph_dt);
-    }
+    struct vector* allowed_ops = create_vector(sizeof(int), nullptr);
+    struct vector* blocked_ops = create_vector(sizeof(int), nullptr);
+    struct vector* precision = create_vector(sizeof(int), nullptr);
+    fill_op_lists(allowed_ops, blocked_ops, precision, graph_dt);      // (a quantised graph: the quantised-only operators are allowed too)
     split_graph_node_to_sub_graph(ir_graph, allowed_ops, blocked_ops, precision);
     release_vector(allowed_ops);
     release_vector(blocked_ops);
@@ -969,12 +871,12 @@ __attribute__((visibility("default"))) int hip_wait_graph(void* graph, int try_w
     return sch->wait(sch, ir);
 }
 
-// Introspection for tests and tools: where did the splitter put the nodes of a prerun graph?  One line per subgraph,
-// "<index> <device name> <nodes> <nodes that are not Input/Const> <their operator names, comma separated>"; returns the number of
-// subgraphs, or -1 when `cap` is too small.  (struct graph is the reference's own; this library is compiled against its headers.)
 // how many subgraphs were compiled as two half-batch device graphs so far (tests: the split is asserted, not assumed)
 __attribute__((visibility("default"))) int hip_device_split_subgraphs(void) { return g_split_subgraphs; }
 
+// Introspection for tests and tools: where did the splitter put the nodes of a prerun graph?  One line per subgraph,
+// "<index> <device name> <nodes> <nodes that are not Input/Const> <their operator names, comma separated>"; returns the number of
+// subgraphs, or -1 when `cap` is too small.  (struct graph is the reference's own; this library is compiled against its headers.)
 __attribute__((visibility("default"))) int hip_device_placement(void* graph, char* buf, int cap)
 {
     struct graph* ir = (struct graph*)graph;

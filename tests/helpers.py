@@ -684,3 +684,40 @@ I8_HEAD_CASES["single_head_concat_is_a_copy"] = dict(seed=11, n=2, cin=16, h=3, 
 I8_HEAD_CASES["single_flattened_map_concat_is_a_copy"] = dict(seed=12, n=2, cin=16, h=3, w=4, couts=(24,), tail="flatcat")
 I8_HEAD_CASES["reshape_of_a_map_softmax"] = dict(seed=13, n=2, cin=8, h=3, w=7, couts=(12,), tail="reshape_map", softmax_axis=2)
 I8_HEAD_CASES["reshape_of_a_map_softmax_middle"] = dict(seed=14, n=2, cin=8, h=2, w=5, couts=(20,), tail="reshape_map", softmax_axis=1)
+
+
+def node_supported(g):
+    """what tamd_node_supported answers for the LAST node of a builder graph (Convolution / FullyConnected / Softmax): the question the
+    Tengine plugin asks before it claims the node, put to the library the same way -- shapes and quantisation form, no payloads"""
+    import ctypes as C
+    from tengine_amd import capi
+
+    class T(C.Structure):          # tamd_tensor_desc
+        _fields_ = [("dtype", C.c_int), ("ttype", C.c_int), ("dim_num", C.c_int), ("dims", C.c_int * 8), ("data", C.c_void_p),
+                    ("quant_num", C.c_int), ("scales", C.c_void_p), ("zero_points", C.c_void_p), ("name", C.c_char_p)]
+
+    class N(C.Structure):          # tamd_node_desc
+        _fields_ = [("op", C.c_int), ("input_num", C.c_int), ("inputs", C.c_void_p), ("output_num", C.c_int), ("outputs", C.c_void_p),
+                    ("param", C.c_void_p), ("name", C.c_char_p)]
+
+    def desc(i):
+        t, d = g.tensors[i], T()
+        d.dtype, d.ttype, d.dim_num, d.quant_num = t.dtype, t.ttype, len(t.dims), len(t.scales or [])
+        for k, v in enumerate(t.dims):
+            d.dims[k] = v
+        return d
+
+    node = g.nodes[-1]
+    p = node.params
+    if node.op == "Convolution":   # tamd_conv_param
+        op, param = 2, (C.c_int * 14)(p["kernel_h"], p["kernel_w"], p["stride_h"], p["stride_w"], p["pad_h0"], p["pad_h1"], p["pad_w0"], p["pad_w1"],
+                                      p["dilation_h"], p["dilation_w"], p["input_channel"], p["output_channel"], p["group"], p["activation"])
+    elif node.op == "FullyConnected":
+        op, param = 3, (C.c_int * 1)(p["num_output"])
+    else:
+        assert node.op == "Softmax", node.op
+        op, param = 12, (C.c_int * 1)(p.get("axis", 1))
+    n = N()
+    n.op, n.input_num, n.output_num, n.param = op, len(node.inputs), len(node.outputs), C.cast(C.pointer(param), C.c_void_p)
+    ins, outs = [desc(i) for i in node.inputs], [desc(i) for i in node.outputs]
+    return capi.lib().tamd_node_supported(C.byref(n), (T * len(ins))(*ins), len(ins), (T * len(outs))(*outs), len(outs))

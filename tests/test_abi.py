@@ -171,6 +171,38 @@ def test_node_supported_query():
     assert ask(13, [t(F32, VAR, [1, 12, 5, 5], 0)], [t(F32, VAR, [1, 5, 5, 12], 0)], perm) == 0
     pb.max_size_num = 2
     assert ask(15, [feat, img], [t(U8, VAR, [1, 2, 600, 1])], pb) == 0           # max sizes must pair with min sizes (priorbox.c:48-61)
+    # ---- the boundaries of the rules that the query shares with the planners (csrc/node_rules.h) ----
+    for ty in range(9):                                                         # Eltwise: PROD, SUM, SUB, MAX of two tensors
+        assert ask(6, [a, a], [a], (C.c_int * 5)(ty, 0, 0, 0, 0)) == (1 if ty in (0, 2, 4, 6) else 0), ty
+    for dt in (I8, U8, F32):                                                    # Upsample: an integer factor >= 1
+        q = 0 if dt == F32 else 1
+        for factor, side, want in ((1.0, 4, 1), (2.0, 8, 1), (1.5, 6, 0), (0.5, 2, 0)):
+            assert ask(9, [t(dt, VAR, [1, 16, 4, 4], q)], [t(dt, VAR, [1, 16, side, side], q)], C.c_float(factor)) == want, (dt, factor)
+    for hidden, want in ((15000, 1), (15001, 0)):                               # uint8 FC: the input row as floats in LDS
+        assert ask(3, [t(U8, VAR, [1, hidden]), t(U8, CONST, [4, hidden])], [t(U8, VAR, [1, 4])], (C.c_int * 1)(4)) == want, hidden
+    xm = t(I8, VAR, [1, 16, 16, 24])                                            # int8 conv, group 1: 128 taps in the implicit GEMM's table
+    k8x16 = (C.c_int * 14)(8, 16, 1, 1, 0, 0, 0, 0, 1, 1, 16, 8, 1, 0)
+    assert ask(2, [xm, t(I8, CONST, [8, 16, 8, 16], 8)], [t(I8, VAR, [1, 8, 9, 9])], k8x16) == 1
+    k11x12 = (C.c_int * 14)(11, 12, 1, 1, 0, 0, 0, 0, 1, 1, 16, 8, 1, 0)
+    assert ask(2, [xm, t(I8, CONST, [8, 16, 11, 12], 8)], [t(I8, VAR, [1, 8, 6, 13])], k11x12) == 0
+    dw11x12 = (C.c_int * 14)(11, 12, 1, 1, 0, 0, 0, 0, 1, 1, 16, 16, 16, 0)     # .. depthwise: the direct kernel, no table
+    assert ask(2, [xm, t(I8, CONST, [16, 1, 11, 12], 16)], [t(I8, VAR, [1, 16, 6, 13])], dw11x12) == 1
+    for c, want in ((16000, 1), (16001, 0)):                                    # int8 softmax: the axis' exponentials in LDS
+        assert ask(12, [t(I8, VAR, [1, c])], [t(I8, VAR, [1, c])]) == want, c
+
+
+def test_fractional_upsample_is_refused_by_name_for_every_dtype():
+    """the uint8 / fp32 planners and shape inference take the Upsample factor as an int (1.5 would run as 1): validate_graph refuses such
+    a node by name before the device is touched, as the int8 planner and tamd_node_supported always did"""
+    from helpers import u8_unary_graph
+    from tengine_amd import tm2
+    g, _ = u8_unary_graph(3, "Upsample", [1, 16, 4, 4], [1, 16, 6, 6], scale=1.5)
+    assert "upsample" in _prerun_error(g)
+    g = tm2.Graph(name="f32_upsample_case")
+    x = g.add_input("data", [1, 16, 4, 4], tm2.DT_FP32, None, None)
+    y = g.add_tensor("out", [1, 16, 6, 6], tm2.DT_FP32, tm2.TT_VAR, None, None, None)
+    g.output_nodes = [g.add_node("upsample", "Upsample", [x], [y], scale=1.5)]
+    assert "upsample" in _prerun_error(g)
 
 
 def test_launch_recorder_packs_arguments_like_the_code_object(tmp_path):

@@ -196,6 +196,19 @@ def test_split_cuts_around_an_unsupported_node_instead_of_surrendering(ref):
     assert pl[1][0] != "HIP"
 
 
+def test_split_leaves_an_int8_relu6_to_the_cpu(ref):
+    """conv -> ReLU6 in int8: ReLU6 is in the plugin's operator table, the library has it for fp32 alone (tamd_op_supported) -- the
+    convolution stays on "HIP", the ReLU6 goes to the CPU device"""
+    _load_plugin(ref)
+    g, x = conv_graph(6, 1, 16, 6, 6, 16, 1, act=-1)
+    y = g.nodes[-1].outputs[0]
+    o = g.add_tensor("r6", list(g.tensors[y].dims), tm2.DT_INT8, tm2.TT_VAR, None, list(g.tensors[y].scales), [0])
+    g.output_nodes = [g.add_node("relu6", "ReLU6", [y], [o])]
+    pl = _split_only(ref, g, x, ref.MODE_INT8)
+    assert [(dev, ops) for dev, _, _, ops in pl if ops] == [("HIP", ["Convolution"]), (pl[1][0], ["ReLU6"])], pl
+    assert pl[1][0] != "HIP"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["conv3x3", "resblock_tail", "resnet50_prob", "mobilenet_v1"])
 def test_hip_device_equals_reference_cpu_device(ref, case):
