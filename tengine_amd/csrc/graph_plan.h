@@ -11,6 +11,7 @@ int conv_mode(const tamd_conv_param& p, int batch, int cin, int cout);
 struct RqFold { float m1, lo, hi, out_scale; std::vector<float> m2; };
 RqFold fold_requant(int mode, int act, float in_s, float out_s, const HTensor& w, int cout);
 int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, RqArgs* rq);
+int upload_rq_m2(tamd_graph* g, const RqFold& r, int cpad, std::vector<float>* mf, RqArgs* rq);
 bool exp_plain_kernels();
 std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps);
 
@@ -51,6 +52,12 @@ int plan_pool(tamd_graph* g, HNode& n, Planned* out);
 int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod);
 int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Planned& a, const Planned& b, Step* fused);
 int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& d, const Planned& c, Step* fused);
+// two adjacent pwdw pairs -- producer conv, depthwise (stride 1), pointwise conv, depthwise -- in one launch: chain4.hip.  find_chain4: the
+// pointwise conv and the depthwise behind the pair (ni, its tail `tail`) where the four nodes fit the kernel AND the switches / default rule
+// want the chain; fused[nj] / has_fuse[nj]: node nj already belongs to another launch / takes an eltwise tail (I8Layout).  The chain runs
+// at ni's position and writes the last depthwise's output while it reads ni's input: plan_buffers' birth rule keeps the two apart
+bool find_chain4(tamd_graph* g, size_t ni, int tail, int prod, const std::vector<char>& fused, const std::vector<char>& has_fuse, int* pw2, int* dw2);
+int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int prod, const Planned& a, const Planned& b, const Planned& c, const Planned& d, Step* fused);
 // an identity bottleneck block (1x1 -> 3x3 -> 1x1 + residual [+ ReLU]) in one launch: block_i8.hip.  c carries the eltwise tail fz
 bool fuse_block_enabled();
 int plan_block(tamd_graph* g, HNode& na, HNode& nb, HNode& nc, const FusedElt& fz, const Planned& a, const Planned& b, const Planned& c, Step* fused);

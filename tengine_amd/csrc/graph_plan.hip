@@ -314,8 +314,10 @@ static int plan_input_staging(tamd_graph* g)
 // than the 256 MB last-level cache, but never has more than ~65 MB of them alive.  Lifetime of a buffer, in node positions
 // (the launch list follows the node order, except that a fused tail runs at ITS PRODUCER's position and a fused
 // eltwise / ReLU at the position of the convolution that absorbs it): written from `birth` = the earliest producer within two
-// hops above the node that produces it (covers both exceptions, conservatively), read until `death` = the last node that
-// names it (or a view / alias of it) as an input.  A launch reads and writes in one go, so buffers with birth == death of
+// hops above the node that produces it (covers both exceptions, conservatively) -- THREE hops for the output of a depthwise conv
+// behind a pointwise conv behind a depthwise conv: chain4.hip runs those three at the position of the conv in front of them, so its
+// launch writes that output while it reads that conv's input, and the two must never share memory -- read until `death` = the last
+// node that names it (or a view / alias of it) as an input.  A launch reads and writes in one go, so buffers with birth == death of
 // another never share.  Graph inputs / outputs and tensors with padding channels (cs != c: their padding bytes are zero from
 // the allocation on and stay zero) keep their own buffers.
 static int plan_buffers(tamd_graph* g, I8Layout& L)
@@ -353,6 +355,12 @@ static int plan_buffers(tamd_graph* g, I8Layout& L)
         if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST) continue;
         int e = ni;
         for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST && prod[i] >= 0) e = std::min(e, up(prod[i]));
+        // the chain of four (find_chain4's node shape, whether or not the chain is taken later): dw <- 1x1 conv <- dw <- its producer
+        auto conv_in = [&](int k) { const HNode& c = g->nodes[k]; return c.op == TAMD_OP_CONV && !c.in.empty() ? prod[c.in[0]] : -1; };
+        if (n.op == TAMD_OP_CONV && n.p.conv.group > 1) {
+            const int p2 = conv_in(ni), d1 = p2 >= 0 && g->nodes[p2].op == TAMD_OP_CONV && g->nodes[p2].p.conv.group == 1 ? conv_in(p2) : -1;
+            if (d1 >= 0 && g->nodes[d1].op == TAMD_OP_CONV && g->nodes[d1].p.conv.group > 1) e = std::min(e, up(d1));
+        }
         for (int o : n.out) { const int r = root_of(o); birth[r] = std::min(birth[r], e); death[r] = std::max(death[r], ni); }
         for (int i : n.in) if (g->tensors[i].ttype != TAMD_TT_CONST) { const int r = root_of(i); death[r] = std::max(death[r], ni); }
     }
@@ -674,7 +682,7 @@ static int try_block(tamd_graph* g, I8Layout& L, size_t ni)
 }
 
 // A convolution node and its fusions: the bottleneck block (opt-in), then the three pairings conv + pool (stem), pointwise + its tail
-// (pwdw), depthwise + pointwise (dwpw).  Each plans the launches involved as values and pushes either the fused launch or the
+// (pwdw; two adjacent ones as a chain of four: chain4), depthwise + pointwise (dwpw).  Each plans the launches involved as values and pushes either the fused launch or the
 // planned ones.
 static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
 {
@@ -709,6 +717,20 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
         if (plan_conv(g, n, false, nullptr, &a)) return -1;
         if (tmode == 0 ? plan_pool(g, g->nodes[tail], &b) : plan_conv(g, g->nodes[tail], false, nullptr, &b)) return -1;
         L.fused[tail] = 1;
+        // Two adjacent pairs -- this one and the pointwise + depthwise behind it -- as ONE launch where the four nodes fit chain4.hip and
+        // the switches / the default rule (batch 1) want it: the second pair is planned here as well, ahead of its node order.  Where
+        // no tile configuration fits, this pair goes on as before and the second pair is planned again at its own node (try_dwpw's known
+        // waste).  The chain's launch runs HERE and writes the second depthwise's output while it reads this conv's input: safe only
+        // because plan_buffers starts that output's lifetime three hops up for this node shape (dw <- 1x1 <- dw <- this conv); a change to
+        // that rule or to this look-ahead has to keep the two apart
+        int pw2 = -1, dw2 = -1;
+        if (tmode == 1 && find_chain4(g, ni, tail, prod, L.fused, L.has_fuse, &pw2, &dw2)) {
+            Planned c, d;
+            if (plan_conv(g, g->nodes[pw2], false, nullptr, &c) || plan_conv(g, g->nodes[dw2], false, nullptr, &d)) return -1;
+            const int chained = plan_chain4(g, n, g->nodes[tail], g->nodes[pw2], g->nodes[dw2], prod, a, b, c, d, &st);
+            if (chained < 0) return -1;
+            if (chained) { L.fused[pw2] = 1; L.fused[dw2] = 1; g->steps.push_back(st); return 0; }
+        }
         // Where the depthwise tail can go together with ITS consumer (dwpw.hip: batched 14x14-class maps, stride 1), that pairing is
         // tried FIRST.  In a chain pw, dw, pw, dw, .. either pairing covers every layer once per period, and in a pass dwpw is the
         // cheaper period (MobileNet-v1 b64: 16.4 us against 22.9 us for the pwdw pair with two slices per block) -- but the

@@ -113,6 +113,17 @@ int upload_rq(tamd_graph* g, const RqFold& r, int cpad, const float** wscale, Rq
     return 0;
 }
 
+// as upload_rq, but the fast-path multipliers stay on the host in *mf (chain4.hip stages them into LDS together with its weights)
+int upload_rq_m2(tamd_graph* g, const RqFold& r, int cpad, std::vector<float>* mf, RqArgs* rq)
+{
+    std::vector<float> m2;
+    *rq = host_rq(r, cpad, mf, &m2);
+    float* d1;
+    if (upload(g, m2, &d1)) return -1;
+    rq->m2 = d1;
+    return 0;
+}
+
 // pointwise weight panel in MFMA fragment order: [16-channel slice][64-deep K step][lane = (k block of 16) * 16 + channel][16 B];
 // `wd` = [C][K] int8 rows (1x1 conv: K = cin; first conv: K = cin*KH*KW in OIHW order), zero padded to nsteps * 64
 std::vector<int8_t> pack_pw_panel(const int8_t* wd, int C, int K, int nsteps)

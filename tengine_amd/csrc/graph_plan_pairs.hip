@@ -1,5 +1,6 @@
 // int8 planner, the pair fusions: pointwise conv + its single consumer (depthwise 3x3 | global pooling) in one launch (pwdw.hip), and
-// depthwise 3x3 + the pointwise conv behind it (dwpw.hip); and the one triple: an identity bottleneck block (block_i8.hip).
+// depthwise 3x3 + the pointwise conv behind it (dwpw.hip); two adjacent pwdw pairs as one launch (chain4.hip); and the one triple: an
+// identity bottleneck block (block_i8.hip).
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
@@ -264,6 +265,209 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
         st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
     }
     g->fused_away[pw.out[0]] = 1;
+    return 1;
+}
+
+// ---- two adjacent pwdw pairs in one launch: producer conv -> depthwise 3x3 (stride 1) -> pointwise conv -> depthwise 3x3: chain4.hip --------
+// Which chains run by DEFAULT (batch 1 only): bit 0 the chain behind the network's first convolution (MobileNet-v1: conv1 .. conv2_2/dw),
+// bit 1 a chain behind a pointwise conv (conv2_2/sep .. conv3_2/dw).  Set per kind from the interleaved A/B of profiles/chain4_ab.txt
+// (parent build against a build with ONE kind on): the first-conv chain took the MobileNet-v1 batch-1 step from 51.62 to 50.38 us
+// (median of 7, spreads 0.35 / 0.14 us) and is on; the pointwise chain left it where it was (51.59 against 51.62 us: its launch takes
+// 7.1 us against 3.7 + 3.7 for the two it replaces) and stays reachable through TAMD_PIN=chain4=2 only.
+#ifndef TAMD_CHAIN4_DEFAULT
+#define TAMD_CHAIN4_DEFAULT 1
+#endif
+
+// The pair (ni, tail) was found by find_pwdw_tail (tmode 1).  Looks one pair further: the tail's sole consumer must be a 1x1 / stride-1 /
+// unpadded conv whose own find_pwdw_tail is again a depthwise 3x3.  Limits of the kernel: dw1 stride 1, every depthwise pad 0 | 1,
+// C1, C2 <= 128, a pointwise producer of K <= 128; each of the three intermediates has one consumer and is neither a graph output nor a
+// view (find_pwdw_tail asks that of a pair's intermediate; the middle one is checked here).  TAMD_FUSE_PWDW=0 disables the chain with the
+// pairs it is made of; TAMD_PIN=chain4=0 never, =2 always where applicable (also at batch > 1: tests); default: batch 1, a link of a
+// latency chain, fused by construction (plan_pwdw: why not by a race).
+bool find_chain4(tamd_graph* g, size_t ni, int tail, int prod, const std::vector<char>& fused, const std::vector<char>& has_fuse, int* pw2, int* dw2)
+{
+    auto taken = [&](int nj) { return fused[nj] || has_fuse[nj]; };
+    const char* fenv = getenv("TAMD_FUSE_PWDW");
+    const int pin = tamd_pin_int("chain4", 1);
+    if ((fenv && atoi(fenv) == 0) || pin == 0) return false;
+    const HNode& n0 = g->nodes[ni];
+    const HNode& d1 = g->nodes[tail];
+    const HTensor& x = g->tensors[n0.in[0]];
+    const HTensor& y1 = g->tensors[d1.out[0]];
+    if (pin != 2 && !(x.n == 1 && (TAMD_CHAIN4_DEFAULT & (prod == 1 ? 1 : 2)))) return false;
+    auto pads01 = [](const tamd_conv_param& q) { return q.pad_h0 >= 0 && q.pad_h0 <= 1 && q.pad_w0 >= 0 && q.pad_w0 <= 1 && q.pad_h1 >= 0 && q.pad_h1 <= 1 && q.pad_w1 >= 0 && q.pad_w1 <= 1; };
+    if (d1.p.conv.stride_h != 1 || !pads01(d1.p.conv) || y1.is_view || count_consumers(g, d1.out[0]) != 1) return false;
+    for (auto& o : g->outputs) if (o.tensor == d1.out[0]) return false;
+    if (g->tensors[n0.out[0]].c > 128 || (prod == 0 && x.c > 128)) return false;
+    int pj = -1;
+    for (size_t nj = (size_t)tail + 1; nj < g->nodes.size() && pj < 0; nj++)
+        if (!g->nodes[nj].in.empty() && g->nodes[nj].in[0] == d1.out[0]) pj = (int)nj;
+    if (pj < 0 || taken(pj) || g->nodes[pj].op != TAMD_OP_CONV) return false;
+    int tmode = -1, prod2 = 0;
+    const int dj = find_pwdw_tail(g, (size_t)pj, &tmode, &prod2);
+    if (dj < 0 || tmode != 1 || prod2 != 0 || taken(dj) || g->tensors[g->nodes[pj].out[0]].c > 128 || !pads01(g->nodes[dj].p.conv)) return false;
+    *pw2 = pj; *dw2 = dj;
+    return true;
+}
+
+// The four nodes were just planned as pa .. pd (their macs / bytes; the fused launch folds its own constants with the functions those
+// plans used).  TAMD_PIN=chain4_cfg=THxTWxthreads pins the tile.  0: no tile configuration fits -- the pairs stay as they are.
+int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int prod, const Planned& pa, const Planned& pb, const Planned& pc, const Planned& pd, Step* fused)
+{
+    HTensor& x = g->tensors[n0.in[0]];
+    HTensor& w0 = g->tensors[n0.in[1]];
+    HTensor* b0 = n0.in.size() > 2 ? &g->tensors[n0.in[2]] : nullptr;
+    HTensor& m0 = g->tensors[n0.out[0]];
+    HTensor& m1 = g->tensors[d1.out[0]];
+    HTensor& w2 = g->tensors[p2.in[1]];
+    HTensor* b2 = p2.in.size() > 2 ? &g->tensors[p2.in[2]] : nullptr;
+    HTensor& m2 = g->tensors[p2.out[0]];
+    HTensor& y = g->tensors[d2.out[0]];
+    const tamd_conv_param& pp = n0.p.conv;
+    const int cin = x.c, C1 = m0.c, C2 = m2.c, ns1 = (C1 + 15) / 16, ns2 = (C2 + 15) / 16;
+    const int Kw = prod == 1 ? cin * pp.kernel_h * pp.kernel_w : cin;           // weight row length in the model
+    const int K = prod == 1 ? cin * pp.kernel_h * 4 : cin;                      // reduction length as the kernel walks it (plan_pwdw)
+    const int ks0 = ((prod == 1 ? K : rup(cin, 16)) + 63) / 64, ks2 = (ns1 * 16 + 63) / 64;
+    if (w0.elems() != (size_t)C1 * Kw || (b0 && b0->elems() < (size_t)C1) || w2.elems() != (size_t)C2 * C1 || (b2 && b2->elems() < (size_t)C2)) return 0;
+    if (m1.c != C1 || y.c != C2 || m1.h != m2.h || m1.w != m2.w || ks0 > 2 || ks2 > 2 || (prod == 1 && ks0 != 1)) return 0;
+    Chain4Args a{};
+    RqArgs rq[4];
+    std::vector<float> mf0, mf2;
+    // the two GEMM nodes: panels, bias and multiplier vectors go into the blob the kernel stages into LDS
+    std::vector<int8_t> wf0, wf2;
+    {
+        const int8_t* wd = (const int8_t*)w0.data.data();
+        std::vector<int8_t> wrows;
+        if (prod == 1) {                // k = (c*KH + ky)*4 + kx: rows padded to 4 taps (plan_pwdw)
+            wrows.assign((size_t)C1 * K, 0);
+            for (int c = 0; c < C1; c++)
+                for (int r = 0; r < cin * pp.kernel_h; r++)
+                    for (int kx = 0; kx < pp.kernel_w; kx++) wrows[(size_t)c * K + r * 4 + kx] = wd[(size_t)c * Kw + r * pp.kernel_w + kx];
+            wd = wrows.data();
+        }
+        wf0 = pack_pw_panel(wd, C1, K, ks0);
+        // pw2's K is C1 rounded up to 16 and padded to 64-deep steps with zero weights: the slack channels of a slice meet zeros
+        wf2 = pack_pw_panel((const int8_t*)w2.data.data(), C2, C1, ks2);
+        if (upload_rq_m2(g, fold_requant(RQ_CONV_HCL, pp.activation, x.scales[0], m0.scales[0], w0, C1), ns1 * 16, &mf0, &rq[0])) return -1;
+        if (upload_rq_m2(g, fold_requant(RQ_CONV_HCL, p2.p.conv.activation, m1.scales[0], m2.scales[0], w2, C2), ns2 * 16, &mf2, &rq[2])) return -1;
+    }
+    // the two depthwise nodes: taps, bias and multipliers per thread from memory (DwArgs layout).  The reference picks the depthwise
+    // formula by batch == 1 (conv_mode)
+    auto fold_dw = [&](HNode& dn, const HTensor& in, const HTensor& out, int C, int cw, const int8_t** w, const int32_t** bias, const float** ws, RqArgs* r) {
+        const tamd_conv_param& q = dn.p.conv;
+        HTensor& dwt = g->tensors[dn.in[1]];
+        HTensor* db = dn.in.size() > 2 ? &g->tensors[dn.in[2]] : nullptr;
+        if (dwt.elems() != (size_t)C * 9 || (db && db->elems() < (size_t)C)) return 1;
+        const RqFold f = fold_requant(conv_mode(q, g->formula_batch ? g->formula_batch : in.n, C, C), q.activation, in.scales[0], out.scales[0], dwt, C);
+        const std::vector<int8_t> wp = pack_dw3x3((const int8_t*)dwt.data.data(), C, cw);
+        const std::vector<int32_t> bp = padded_bias(db ? (const int32_t*)db->data.data() : nullptr, C, cw);
+        int8_t* d0; int32_t* dd1;
+        if (upload(g, wp, &d0) || upload(g, bp, &dd1) || upload_rq(g, f, cw, ws, r)) return -1;
+        *w = d0; *bias = dd1;
+        return 0;
+    };
+    if (int e = fold_dw(d1, m0, m1, C1, ns1 * 16, &a.dw1_w, &a.dw1_bias, &a.dw1_wscale, &rq[1])) return e < 0 ? -1 : 0;
+    if (int e = fold_dw(d2, m2, y, C2, ns2 * 16, &a.dw2_w, &a.dw2_bias, &a.dw2_wscale, &rq[3])) return e < 0 ? -1 : 0;
+    {
+        std::vector<int8_t> blob;
+        auto put = [&](const void* p, size_t bytes) { const int off = (int)blob.size(); blob.insert(blob.end(), (const int8_t*)p, (const int8_t*)p + bytes); return off; };
+        const std::vector<int32_t> bp0 = padded_bias(b0 ? (const int32_t*)b0->data.data() : nullptr, C1, ns1 * 16);
+        const std::vector<int32_t> bp2 = padded_bias(b2 ? (const int32_t*)b2->data.data() : nullptr, C2, ns2 * 16);
+        put(wf0.data(), wf0.size());
+        a.off_wf2 = put(wf2.data(), wf2.size());
+        a.off_b0 = put(bp0.data(), bp0.size() * 4);
+        a.off_s0 = put(mf0.data(), mf0.size() * 4);
+        a.off_b2 = put(bp2.data(), bp2.size() * 4);
+        a.off_s2 = put(mf2.data(), mf2.size() * 4);
+        a.off_rq = put(rq, sizeof(rq));
+        blob.resize(rup((int)blob.size(), 16), 0);
+        a.blob_q = (int)(blob.size() / 16);
+        int8_t* d0;
+        if (upload(g, blob, &d0)) return -1;
+        a.blob = d0;
+    }
+    a.win = rq_win(rq[0]) && rq_win(rq[1]) && rq_win(rq[2]) && rq_win(rq[3]) ? 1 : 0;
+    a.prod = prod;
+    a.coherent = (g->opt.direct_dispatch && !exp_plain_kernels()) ? 1 : 0;
+    if (prod == 1) {
+        std::vector<unsigned> rows(16, 0u);
+        for (int r = 0; r < cin * pp.kernel_h; r++) {
+            const int ky = r % pp.kernel_h, ci = r / pp.kernel_h;
+            rows[r] = (unsigned)(ci * x.h * x.w + ky * pp.dilation_h * x.w) | ((unsigned)(ky * pp.dilation_h) << 28);
+        }
+        unsigned* dt;
+        if (upload(g, rows, &dt)) return -1;
+        a.taps = dt; a.in_C = cin; a.in_H = x.h; a.in_W = x.w;
+        a.fSH = pp.stride_h; a.fSW = pp.stride_w; a.fPH = pp.pad_h0; a.fPW = pp.pad_w0;
+    }
+    a.x = (const int8_t*)x.dptr + (prod == 1 ? 0 : x.c_off);
+    a.N = x.n; a.cs_in = x.cs; a.H0 = m0.h; a.W0 = m0.w; a.H1 = m1.h; a.W1 = m1.w; a.OH = y.h; a.OW = y.w;
+    a.P1H = d1.p.conv.pad_h0; a.P1W = d1.p.conv.pad_w0; a.S2 = d2.p.conv.stride_h; a.P2H = d2.p.conv.pad_h0; a.P2W = d2.p.conv.pad_w0;
+    a.ns1 = ns1; a.ns2 = ns2; a.ks0 = ks0; a.ks2 = ks2;
+    while ((1 << a.qsh1) < ns1 * 4) a.qsh1++;
+    while ((1 << a.qsh2) < ns2 * 4) a.qsh2++;
+    a.y = (int8_t*)y.dptr; a.ldc = y.cs; a.c_off = y.c_off; a.c_limit = store_limit(y, C2);
+
+    // ---- tile configurations: a short list, ranked by the instruction slots of the busiest wave, the fastest by plan_race ---------
+    struct Cfg { int th, tw, threads; double cost; };
+    std::vector<Cfg> cfgs;
+    auto with_tiles = [&](Chain4Args v, int th, int tw) {
+        v.TH = th; v.TW = tw; v.tiles_y = (v.OH + th - 1) / th; v.tiles_x = (v.OW + tw - 1) / tw;
+        v.RCH = (th - 1) * v.S2 + 3; v.RCW = (tw - 1) * v.S2 + 3;
+        return v;
+    };
+    const int shapes[5][2] = {{2, 2}, {2, 4}, {4, 4}, {4, 7}, {7, 7}};
+    for (auto& sh : shapes)
+        for (int threads : {256, 512}) {
+            const int th = std::min(sh[0], a.OH), tw = std::min(sh[1], a.OW);
+            bool dup = false;
+            for (auto& c : cfgs) dup |= c.th == th && c.tw == tw && c.threads == threads;
+            const Chain4Args v = with_tiles(a, th, tw);
+            if (dup || !chain4_config_ok(v, threads)) continue;
+            const double nw = threads / 64, ap = (double)std::min(v.RCH + 2, a.H0) * std::min(v.RCW + 2, a.W0), cp = (double)std::min(v.RCH, a.H1) * std::min(v.RCW, a.W1);
+            const double block = 300.0 + std::ceil(std::ceil(ap / 16.0) / nw) * (45.0 + 30.0 * ns1) + std::ceil(cp * ns1 * 4.0 / threads) * 90.0
+                                 + std::ceil(std::ceil(cp / 16.0) * ns2 / nw) * (40.0 + 4.0 * ks2) + std::ceil((double)th * tw * ns2 * 4.0 / threads) * 90.0;
+            const double blocks = (double)a.N * v.tiles_y * v.tiles_x;
+            cfgs.push_back({th, tw, threads, std::ceil(blocks / (256.0 * (threads == 256 ? 2 : 1))) * block});
+        }
+    std::sort(cfgs.begin(), cfgs.end(), [](const Cfg& l, const Cfg& r) { return l.cost < r.cost; });
+    if (const char* pin = tamd_pin("chain4_cfg")) {
+        int th = 0, tw = 0, threads = 0;
+        if (sscanf(pin, "%dx%dx%d", &th, &tw, &threads) == 3) {
+            th = std::min(th, a.OH); tw = std::min(tw, a.OW);
+            if (th >= 1 && tw >= 1 && chain4_config_ok(with_tiles(a, th, tw), threads)) { cfgs.clear(); cfgs.push_back({th, tw, threads, 0.0}); }
+        }
+    }
+    if (cfgs.empty()) return 0;
+    const std::string node = pa.step.node + "+" + pb.step.node + "+" + pc.step.node + "+" + pd.step.node;
+    std::vector<RaceCand> tiles;
+    for (size_t c = 0; c < cfgs.size(); c++) {
+        const Chain4Args v = with_tiles(a, cfgs[c].th, cfgs[c].tw);
+        const int threads = cfgs[c].threads;
+        char tag[32];
+        snprintf(tag, sizeof(tag), "%dx%dx%d", cfgs[c].th, cfgs[c].tw, threads);
+        tiles.push_back({tag, [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); }, std::string("chain4 ") + tag});
+    }
+    char ckey[256];
+    snprintf(ckey, sizeof(ckey), "chain4|%s|n%d %dx%d c%d>%d s%d p%d c%zu", pa.step.node.c_str(), a.N, a.H0, a.W0, C1, C2, a.S2, prod, cfgs.size());
+    const int best = tiles.size() > 1 ? plan_race(g, pa.step.node, tiles, ckey, 1.0f, autotune_enabled()) : 0;
+    if (best < 0) return -1;
+    const Chain4Args v = with_tiles(a, cfgs[best].th, cfgs[best].tw);
+    const int threads = cfgs[best].threads;
+    Step& st = *fused;
+    st.node = node;
+    char nm[64];
+    snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d>", prod == 1 ? "firstchain4" : "chain4", a.S2, v.TH, v.TW, threads);
+    st.kernel = nm;
+    st.macs = pa.step.macs + pb.step.macs + pc.step.macs + pd.step.macs;
+    st.bytes = pa.step.bytes + pb.step.bytes + pc.step.bytes + pd.step.bytes;      // SURVEY 8(d) accounting, per layer: the three intermediate maps still count
+    st.fn = [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); };
+    if (prod == 1) {                     // reads the graph input, writes the last depthwise's output, nothing else (plan_pwdw: the first layer pair)
+        st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
+    }
+    g->fused_away[n0.out[0]] = 1;
+    g->fused_away[d1.out[0]] = 1;
+    g->fused_away[p2.out[0]] = 1;
     return 1;
 }
 

@@ -159,6 +159,34 @@ struct PwDwArgs {          // pointwise conv + its consumer in one launch (pwdw.
     float p_in_scale, p_out_scale;
 };
 
+struct Chain4Args {        // producer conv -> depthwise 3x3 (stride 1) -> pointwise conv -> depthwise 3x3 (stride 1 | 2) in one launch (chain4.hip):
+                           // a block owns a spatial tile with all channels; the three intermediate maps only exist in LDS
+    const int8_t* x;       // prod 0: NHWC input of the producer (channel offset applied); prod 1: the NCHW graph input
+    const int8_t* blob;    // [producer panel | pw2 panel | producer bias | producer M[c] | pw2 bias | pw2 M[c] | RqArgs of producer, dw1, pw2, dw2]:
+                           // both pointwise weight sets in MFMA fragment order (pack_pw_panel) with their vectors and the four nodes'
+                           // requantisation constants, staged into LDS once per block; blob_q 16-byte pieces
+    const unsigned* taps;  // prod 1: PwDwArgs::taps
+    const int8_t* dw1_w; const int32_t* dw1_bias; const float* dw1_wscale;     // as DwArgs::w / bias / wscale, rows of ns1 * 16 channels
+    const int8_t* dw2_w; const int32_t* dw2_bias; const float* dw2_wscale;     // .. of ns2 * 16
+    int8_t* y;             // NHWC output of the last depthwise
+    int prod, coherent;    // as PwDwArgs
+    int win;               // 1: all four requantisation windows are in the one-binade form (epilogue.h: rq_win)
+    int N;
+    int in_C, in_H, in_W, fSH, fSW, fPH, fPW;      // prod 1: the NCHW input, the first conv's stride / leading pads
+    int cs_in;             // prod 0: bytes between consecutive input pixels
+    int H0, W0;            // the producer's output map (= its input map for prod 0)
+    int H1, W1;            // dw1's output map = pw2's map
+    int OH, OW;            // dw2's output map
+    int P1H, P1W, S2, P2H, P2W;        // leading pads of dw1; stride and leading pads of dw2
+    int ns1, ns2;          // 16-channel slices of C1 (producer / dw1) and C2 (pw2 / dw2), <= 8 each
+    int ks0, ks2;          // 64-deep K steps of the producer's and pw2's panel (1 | 2)
+    int qsh1, qsh2;        // log2 of the threads per pixel in the depthwise phases (channel quads rounded up to a power of two)
+    int blob_q, off_b0, off_s0, off_wf2, off_b2, off_s2, off_rq;       // blob: size in 16-byte pieces, byte offsets of its parts (the producer panel is at 0)
+    int ldc, c_off, c_limit;
+    int TH, TW, tiles_x, tiles_y;      // dw2 output tile per block, grid (tiles_x, tiles_y, N)
+    int RCH, RCW;          // dw2's input region of a tile: (TH-1)*S2+3, (TW-1)*S2+3; dw1's is two more each way
+};
+
 #ifdef TAMD_PWDW_CHAIN_EXPERIMENT      // tools/exp/chain_anatomy.hip only (why the chained launch is not in the product)
 struct PwChainArgs {       // several PwDwArgs layers as ONE launch, ordered by counters (pwdw.hip: pwdw_chain_kernel)
     const PwDwArgs* layers;    // device array [nlayers]
@@ -354,6 +382,9 @@ int pwdw_chain_variant(const PwDwArgs& a, int threads, int* gx, int* gy, int* gz
 hipError_t launch_pwdw_chain(const PwChainArgs& c, int threads, size_t lds, hipStream_t s);
 #endif
 bool pwdw_config_ok(const PwDwArgs& a, int threads);
+hipError_t launch_chain4(const Chain4Args& a, int threads, hipStream_t s);
+size_t chain4_lds_bytes(const Chain4Args& a);
+bool chain4_config_ok(const Chain4Args& a, int threads);
 int pwdw_steps(int nsteps);
 hipError_t launch_pool(const PoolArgs& a, hipStream_t s);
 hipError_t launch_relu_pool(const ReluPoolArgs& a, hipStream_t s);   // (never the global form)

@@ -4,7 +4,8 @@ fresh process that imports a private copy of the tengine_amd package holding the
 library only once), plans from its own plan file, checks its bytes against the other build's and times the step as bench.py does.
 
 usage: ab_lib.py model batch dtype iters rounds  NAME=/path/to/libtengine_amd.so  NAME=...   (NAME=product: the tree's own build)
-       [env TAMD_U8_INT=1 etc. is inherited; AB_LAYERS=1 adds a per-launch table (isolated launches, HIP events) of two builds side by side]"""
+       [env TAMD_U8_INT=1 etc. is inherited; AB_LAYERS=1 adds per-launch tables (isolated launches, HIP events): the first build beside each other one;
+        a worker that dies ends the run with exit status 1: nothing more is started on a GPU that may have faulted]"""
 import hashlib
 import json
 import os
@@ -54,11 +55,14 @@ def main():
             p = subprocess.run([sys.executable, "-c", WORKER, name, batch, dtype, iters], env=env, capture_output=True, text=True, timeout=900)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode or not line:
-                print("  %s: FAILED\n%s" % (nm, p.stderr[-800:]))
-                continue
+                # a dead worker may have faulted the GPU: nothing more is started on it (the machines are shared)
+                print("  %s: FAILED (exit status %d), stopping\n%s" % (nm, p.returncode, p.stderr[-800:]))
+                shutil.rmtree(tmp, ignore_errors=True)
+                sys.exit(1)
             j = json.loads(line[-1])
             res[nm].append(j["us"])
             sha[nm] = j["sha"]
+            print("  round %d %-20s %9.2f us  %d launches  sha %s" % (r, nm, j["us"], j["launches"], j["sha"]), flush=True)
             for node, kern, us in j.get("layers", []):
                 key = (node, kern)
                 layers.setdefault(nm, {})
@@ -68,8 +72,8 @@ def main():
         v = sorted(res[nm])
         if v:
             print("  %-28s min %9.2f  median %9.2f  max %9.2f | output sha %s%s" % (nm, v[0], v[len(v) // 2], v[-1], sha.get(nm), "" if len(set(sha.values())) == 1 else "  (DIFFERS between builds)"))
-    if layers and len(variants) == 2:          # AB_LAYERS=1: isolated launches (HIP events), min over the rounds, side by side
-        a, b = variants[0][0], variants[1][0]
+    for other in variants[1:] if layers else []:          # AB_LAYERS=1: isolated launches (HIP events), min over the rounds, the first build beside each other one
+        a, b = variants[0][0], other[0]
         print("  per launch, isolated (us): %-24s %-34s %8s | %-34s %8s" % ("node", a, "", b, ""))
         nodes = []
         for nm in (a, b):
@@ -81,6 +85,9 @@ def main():
             eb = sorted((us, k) for (n, k), us in layers.get(b, {}).items() if n == node)
             if ea and eb:
                 print("    %-38s %-34s %8.2f | %-34s %8.2f  %+6.1f%%" % (node[:38], ea[0][1][:34], ea[0][0], eb[0][1][:34], eb[0][0], 100 * (eb[0][0] / ea[0][0] - 1)))
+            elif ea or eb:                                  # a node one build runs inside another launch (a fused chain): listed on its own side
+                e = (ea or eb)[0]
+                print("    %-38s %-34s %8s | %-34s %8s" % ((node[:38], e[1][:34], "%.2f" % e[0], "-", "") if ea else (node[:38], "-", "", e[1][:34], "%.2f" % e[0])))
     shutil.rmtree(tmp, ignore_errors=True)
 
 
