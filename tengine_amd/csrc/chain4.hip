@@ -39,6 +39,21 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kChain4Stage = 8;       // 16-byte pieces of the weight blob a thread stages at most
 
+// One depthwise 3x3 position of a channel quad from an LDS region [pixel][16 ch] of `pitch` pixels per row: `row` = this thread's dword of
+// the window's top-left pixel, `w` its taps, acc = the bias on entry (the dot chain starts there).  The 4th column meets a zero tap; it
+// may lie past the region row (the buffer has 4 pixels of slack)
+__device__ __forceinline__ void dw3x3_from_lds(const unsigned* row, int pitch, const unsigned (&w)[3][4], int (&acc)[4])
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const unsigned d[4] = {row[(r * pitch + 0) * 4], row[(r * pitch + 1) * 4], row[(r * pitch + 2) * 4], row[(r * pitch + 3) * 4]};
+        unsigned frag[4];
+        transpose4x4(d, frag);
+#pragma unroll
+        for (int c = 0; c < 4; c++) acc[c] = __builtin_amdgcn_sdot4((int)frag[c], (int)w[r][c], acc[c], false);
+    }
+}
+
 template <int PROD, bool COH, int WIN>
 __device__ __forceinline__ void chain4_block(const Chain4Args& a, unsigned* __restrict__ lds)
 {
@@ -119,22 +134,7 @@ __device__ __forceinline__ void chain4_block(const Chain4Args& a, unsigned* __re
                 if (a.ks0 > 1) bf[1] = *reinterpret_cast<const v4i*>(xp + 64);
             }
         } else {
-            // patch rows of conv output pixel (piy, pix): pwdw.hip's PROD 1 gather (the graph input: ordinary loads in both instances)
-            const int iyb = piy * a.fSH - a.fPH, ixb = pix * a.fSW - a.fPW;
-            const int sft = max(-ixb, 0), xs = max(ixb, 0), nvalid = a.in_W - ixb;
-            const bool colok = nvalid > 0 && sft < 4;
-            const unsigned cmask = nvalid < 4 ? (1u << (8 * max(nvalid, 0))) - 1u : ~0u;
-            const int base = iyb * a.in_W + xs;
-            unsigned raw[4];
-            bool ok[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int iy = iyb + (int)(rows[j] >> 28);
-                ok[j] = colok && (unsigned)iy < (unsigned)a.in_H;
-                __builtin_memcpy(&raw[j], xn + (ok[j] ? base + (int)(rows[j] & 0xffffffu) : 0), 4);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) bf[0][j] = ok[j] ? (int)((raw[j] << (8 * sft)) & cmask) : 0;
+            gather_patch_rows(a, xn, rows, piy, pix, bf[0]);       // (dw_common.h; the graph input: ordinary loads in both instances)
         }
     };
     const int ntilesA = (AVP + 15) >> 4;
@@ -185,15 +185,7 @@ __device__ __forceinline__ void chain4_block(const Chain4Args& a, unsigned* __re
             const int ly = cvy0 + vy - cy0, lx = cvx0 + vx - cx0;        // B / C region coordinates; A's are the same + the tap
             const unsigned* row = src + (ly * RAW + lx) * 4;
             int acc[4] = {db1.x, db1.y, db1.z, db1.w};                   // the dot chain starts at the bias
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                // the 4th column meets a zero tap; it may lie past the region row (the buffer has 4 pixels of slack)
-                const unsigned d[4] = {row[(r * RAW + 0) * 4], row[(r * RAW + 1) * 4], row[(r * RAW + 2) * 4], row[(r * RAW + 3) * 4]};
-                unsigned frag[4];
-                transpose4x4(d, frag);
-#pragma unroll
-                for (int c = 0; c < 4; c++) acc[c] = __builtin_amdgcn_sdot4((int)frag[c], (int)w1[r][c], acc[c], false);
-            }
+            dw3x3_from_lds(row, RAW, w1, acc);
             dst[(ly * RCW + lx) * 4] = requant4<WIN>(acc[0], acc[1], acc[2], acc[3], ds1, c1, rq);
         }
     }
@@ -237,14 +229,7 @@ __device__ __forceinline__ void chain4_block(const Chain4Args& a, unsigned* __re
             const int oyl = (int)(((float)q + 0.5f) * inv_tw), oxl = q - oyl * tw;
             const unsigned* row = src + ((oyl * S2) * RCW + oxl * S2) * 4;
             int acc[4] = {db2.x, db2.y, db2.z, db2.w};
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                const unsigned d[4] = {row[(r * RCW + 0) * 4], row[(r * RCW + 1) * 4], row[(r * RCW + 2) * 4], row[(r * RCW + 3) * 4]};
-                unsigned frag[4];
-                transpose4x4(d, frag);
-#pragma unroll
-                for (int c = 0; c < 4; c++) acc[c] = __builtin_amdgcn_sdot4((int)frag[c], (int)w2[r][c], acc[c], false);
-            }
+            dw3x3_from_lds(row, RCW, w2, acc);
             const unsigned p = requant4<WIN>(acc[0], acc[1], acc[2], acc[3], ds2, c2, rq);
             if (c2 < a.c_limit) {
                 unsigned* dstp = reinterpret_cast<unsigned*>(yn + ((size_t)oyl * a.OW + oxl) * a.ldc);

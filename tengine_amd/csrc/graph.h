@@ -75,7 +75,8 @@ struct Step {                  // one device launch of the compiled plan
     std::function<hipError_t(hipStream_t)> fn;
     bool once = false;         // every input is a prerun constant (PriorBox outputs): launched once at the end of prerun
     // rd / wr list EVERYTHING the step's launch reads / writes in device memory that another step may write (constants left
-    // out) -- only then is deps set, and only a step with deps may run beside its predecessors (graph_exec.hip run_steps)
+    // out) -- only then is deps set, and only a step with deps may run beside its predecessors (graph_exec.hip run_steps).  A step may
+    // list them without deps: the int8 planner refuses a launch whose wr overlaps its rd (graph_plan.hip plan_i8)
     bool deps = false;
     std::vector<Access> rd, wr;
 };

@@ -1,5 +1,10 @@
 // What the three units of the int8 planner share (graph_plan.hip, graph_plan_conv.hip, graph_plan_pairs.hip); private.
+// Planned launches are values (Planned): a fuser is handed the launches of the nodes it covers, reads the constants they folded and
+// uploaded out of their kernel arguments, and builds its one launch with fused_step.  The rules every fuser shares are stated once
+// here: sole_reader (the one node behind a tensor), fused_step / reads_writes (the step of a launch that covers several nodes).
 #pragma once
+#include <initializer_list>
+
 #include "graph_internal.h"
 #include "epilogue.h"
 
@@ -44,6 +49,36 @@ struct Planned {
     PoolArgs pool{};
 };
 
+// The node that reads `tensor` as its FIRST input, where that node is the tensor's only consumer of any kind (a second operand of another
+// node and a graph output count as consumers: count_consumers); -1 otherwise.  What else a fusion asks of that node or of the tensor
+// (is_view, I8Layout::fused / has_fuse) stays with the caller
+inline int sole_reader(const tamd_graph* g, int tensor)
+{
+    if (count_consumers(g, tensor) != 1) return -1;
+    for (size_t nj = 0; nj < g->nodes.size(); nj++)
+        if (!g->nodes[nj].in.empty() && g->nodes[nj].in[0] == tensor) return (int)nj;
+    return -1;
+}
+
+// all a launch touches in device memory besides constants: it reads x and writes y.  plan_i8 checks that the two do not overlap; `deps`:
+// the step may also run beside its predecessors (Step::deps)
+inline void reads_writes(Step& st, const HTensor& x, const HTensor& y, bool deps = true)
+{
+    st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = deps;
+}
+
+// the one launch for the planned launches `parts`: their node names joined by '+', their macs and bytes summed (SURVEY 8(d) accounting,
+// per layer: the intermediate tensors still count as algorithmic bytes)
+inline Step fused_step(std::initializer_list<const Planned*> parts, const std::string& kernel, std::function<hipError_t(hipStream_t)> fn)
+{
+    Step st = make_step("", kernel, 0, 0, std::move(fn));
+    for (const Planned* p : parts) {
+        st.node += (p == *parts.begin() ? "" : "+") + p->step.node;
+        st.macs += p->step.macs; st.bytes += p->step.bytes;
+    }
+    return st;
+}
+
 // graph_plan_conv.hip.  One convolution / FC (as_fc) / pooling node as ONE launch, handed out in *out; fz: the eltwise tail it takes
 int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* out);
 int plan_pool(tamd_graph* g, HNode& n, Planned* out);
@@ -55,7 +90,8 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& d, const Plann
 // two adjacent pwdw pairs -- producer conv, depthwise (stride 1), pointwise conv, depthwise -- in one launch: chain4.hip.  find_chain4: the
 // pointwise conv and the depthwise behind the pair (ni, its tail `tail`) where the four nodes fit the kernel AND the switches / default rule
 // want the chain; fused[nj] / has_fuse[nj]: node nj already belongs to another launch / takes an eltwise tail (I8Layout).  The chain runs
-// at ni's position and writes the last depthwise's output while it reads ni's input: plan_buffers' birth rule keeps the two apart
+// at ni's position and writes the last depthwise's output while it reads ni's input: plan_buffers' birth rule keeps the two apart (plan_i8
+// checks every step for it)
 bool find_chain4(tamd_graph* g, size_t ni, int tail, int prod, const std::vector<char>& fused, const std::vector<char>& has_fuse, int* pw2, int* dw2);
 int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int prod, const Planned& a, const Planned& b, const Planned& c, const Planned& d, Step* fused);
 // an identity bottleneck block (1x1 -> 3x3 -> 1x1 + residual [+ ReLU]) in one launch: block_i8.hip.  c carries the eltwise tail fz

@@ -459,15 +459,11 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
         FusedElt fz{};
         fz.res_tensor = e.in[1 - conv_in]; fz.elt_tensor = e.out[0]; fz.out_tensor = e.out[0]; fz.type = ty;
         fz.conv_is_first = conv_in == 0; fz.relu = false;
-        size_t relu_node = 0;
-        if (count_consumers(g, e.out[0]) == 1)
-            for (size_t nj = ei + 1; nj < g->nodes.size(); nj++) {
-                HNode& r = g->nodes[nj];
-                if (r.op == TAMD_OP_RELU && r.in[0] == e.out[0] && r.p.relu.negative_slope == 0.f && !g->tensors[r.out[0]].is_view) {
-                    fz.relu = true; fz.out_tensor = r.out[0]; relu_node = nj;
-                    break;
-                }
-            }
+        const int relu_node = sole_reader(g, e.out[0]);
+        if (relu_node >= 0) {
+            const HNode& r = g->nodes[relu_node];
+            if (r.op == TAMD_OP_RELU && r.p.relu.negative_slope == 0.f && !g->tensors[r.out[0]].is_view) { fz.relu = true; fz.out_tensor = r.out[0]; }
+        }
         L.fuse_at[later] = fz; L.has_fuse[later] = 1; L.fused[ei] = 1;
         g->fused_away[e.in[conv_in]] = 1;        // the conv's own int8 result only exists in registers
         if (fz.relu) { L.fused[relu_node] = 1; g->fused_away[e.out[0]] = 1; }
@@ -599,13 +595,8 @@ static int fuse_stem(tamd_graph* g, HNode& conv, HNode& pool, const Planned& c, 
 {
     if (c.kind != Planned::FIRST || !conv_first_pool_applicable(c.first, p.pool)) return 0;
     const FirstPoolArgs fa = conv_first_pool_args(c.first, p.pool);
-    Step& st = *fused;
-    st.node = c.step.node + "+" + p.step.node;
-    st.kernel = "conv_first_pool_i8";
-    st.macs = c.step.macs;
-    st.bytes = c.step.bytes + p.step.bytes;      // SURVEY 8(d) accounting, per layer: the conv map still counts
-    st.fn = [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); };
-    st.rd.push_back(access_of(g->tensors[conv.in[0]])); st.wr.push_back(access_of(g->tensors[pool.out[0]])); st.deps = true;
+    *fused = fused_step({&c, &p}, "conv_first_pool_i8", [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); });
+    reads_writes(*fused, g->tensors[conv.in[0]], g->tensors[pool.out[0]]);
     g->fused_away[conv.out[0]] = 1;
     return 1;
 }
@@ -620,16 +611,13 @@ static int try_dwpw(tamd_graph* g, I8Layout& L, size_t dwi, const Planned& pd, S
     HNode& d = g->nodes[dwi];
     const HTensor& dy = g->tensors[d.out[0]];
     const char* dp_env = getenv("TAMD_FUSE_DWPW");
-    if ((dp_env && atoi(dp_env) == 0) || pd.kind != Planned::DW3X3 || d.p.conv.stride_h != 1 || count_consumers(g, d.out[0]) != 1 || dy.is_view) return 0;
+    if ((dp_env && atoi(dp_env) == 0) || pd.kind != Planned::DW3X3 || d.p.conv.stride_h != 1 || dy.is_view) return 0;
     if ((long)dy.n * dy.h * dy.w < 4096 && !(dp_env && atoi(dp_env) == 2)) return 0;
-    for (auto& o : g->outputs) if (o.tensor == d.out[0]) return 0;
-    int pw_node = -1;
-    for (size_t nj = dwi + 1; nj < g->nodes.size(); nj++)
-        if (g->nodes[nj].op == TAMD_OP_CONV && g->nodes[nj].in.size() >= 2 && g->nodes[nj].in[0] == d.out[0] && !L.fused[nj] && !L.has_fuse[nj]
-            && g->nodes[nj].p.conv.group == 1 && g->nodes[nj].p.conv.kernel_h == 1 && g->nodes[nj].p.conv.kernel_w == 1) { pw_node = (int)nj; break; }
-    if (pw_node < 0) return 0;
+    const int pw_node = sole_reader(g, d.out[0]);
+    if (pw_node < 0 || g->nodes[pw_node].op != TAMD_OP_CONV || g->nodes[pw_node].in.size() < 2 || L.fused[pw_node] || L.has_fuse[pw_node]) return 0;
     // what dwpw_applicable will ask of the shapes, before the consumer is planned (and its weights uploaded) for nothing
     const tamd_conv_param& q = g->nodes[pw_node].p.conv;
+    if (q.group != 1 || q.kernel_h != 1 || q.kernel_w != 1) return 0;
     if (!dwpw_pw_shape_ok(g->tensors[g->nodes[pw_node].out[0]].c, dy.w, q.kernel_h, q.kernel_w, q.stride_h, q.stride_w, q.pad_h0 || q.pad_w0 || q.pad_h1 || q.pad_w1)) return 0;
     Planned pc;
     if (plan_conv(g, g->nodes[pw_node], false, nullptr, &pc)) return -1;
@@ -652,17 +640,13 @@ static int try_block(tamd_graph* g, I8Layout& L, size_t ni)
     if (!fuse_block_enabled()) return 0;
     HNode& na = g->nodes[ni];
     if (L.has_fuse[ni] || na.in.size() < 2 || g->tensors[na.in[0]].nchw_raw) return 0;
-    auto sole_conv_behind = [&](size_t from, int tensor) {
-        if (count_consumers(g, tensor) != 1 || g->tensors[tensor].is_view) return -1;
-        for (size_t nj = from + 1; nj < g->nodes.size(); nj++) {
-            const HNode& c = g->nodes[nj];
-            if (c.op == TAMD_OP_CONV && c.in.size() >= 2 && c.in[0] == tensor && !L.fused[nj]) return (int)nj;
-        }
-        return -1;
+    auto sole_conv_behind = [&](int tensor) {
+        const int nj = g->tensors[tensor].is_view ? -1 : sole_reader(g, tensor);
+        return nj >= 0 && g->nodes[nj].op == TAMD_OP_CONV && g->nodes[nj].in.size() >= 2 && !L.fused[nj] ? nj : -1;
     };
-    const int ib = sole_conv_behind(ni, na.out[0]);
+    const int ib = sole_conv_behind(na.out[0]);
     if (ib < 0 || L.has_fuse[ib]) return 0;
-    const int ic = sole_conv_behind((size_t)ib, g->nodes[ib].out[0]);
+    const int ic = sole_conv_behind(g->nodes[ib].out[0]);
     if (ic < 0 || !L.has_fuse[ic] || L.fuse_at[ic].res_tensor != na.in[0] || L.fuse_at[ic].type != 2) return 0;
     // what block_applicable will ask of the nodes' own shapes, before three convolutions are planned ahead of their order for nothing
     auto shape_ok = [](const tamd_conv_param& q, int k) {
@@ -691,14 +675,10 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
     const int blk = try_block(g, L, ni);
     if (blk) return blk < 0 ? -1 : 0;
     // stem (TAMD_FIRST_POOL=0: two launches, for A/B runs and the fused == unfused tests)
-    if (!L.has_fuse[ni] && g->tensors[n.in[0]].nchw_raw && count_consumers(g, n.out[0]) == 1) {
-        int pool_node = -1;
-        for (size_t nj = ni + 1; nj < g->nodes.size(); nj++)
-            if (g->nodes[nj].op == TAMD_OP_POOL && g->nodes[nj].in[0] == n.out[0] && !L.fused[nj]) { pool_node = (int)nj; break; }
+    if (!L.has_fuse[ni] && g->tensors[n.in[0]].nchw_raw) {
+        const int pool_node = sole_reader(g, n.out[0]);
         const char* fp_env = tamd_pin("first_pool");
-        bool is_out = false;
-        for (auto& o : g->outputs) is_out |= (o.tensor == n.out[0]);
-        if (pool_node >= 0 && !is_out && !(fp_env && atoi(fp_env) == 0)) {
+        if (pool_node >= 0 && g->nodes[pool_node].op == TAMD_OP_POOL && !L.fused[pool_node] && !(fp_env && atoi(fp_env) == 0)) {
             Planned c, p;
             if (plan_conv(g, n, false, nullptr, &c)) return -1;
             if (plan_pool(g, g->nodes[pool_node], &p)) return -1;
@@ -722,7 +702,7 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
         // no tile configuration fits, this pair goes on as before and the second pair is planned again at its own node (try_dwpw's known
         // waste).  The chain's launch runs HERE and writes the second depthwise's output while it reads this conv's input: safe only
         // because plan_buffers starts that output's lifetime three hops up for this node shape (dw <- 1x1 <- dw <- this conv); a change to
-        // that rule or to this look-ahead has to keep the two apart
+        // that rule or to this look-ahead that lets the two share memory fails prerun (plan_i8: writes_what_it_reads)
         int pw2 = -1, dw2 = -1;
         if (tmode == 1 && find_chain4(g, ni, tail, prod, L.fused, L.has_fuse, &pw2, &dw2)) {
             Planned c, d;
@@ -819,18 +799,16 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
 // The pool may sit anywhere behind the ReLU in node order: its output is then written at the RELU's position, while the ReLU's input is
 // still being read.  That is safe only because plan_buffers starts a buffer's lifetime at the earliest producer within TWO hops above the
 // node that produces it (pool <- relu <- the ReLU's producer), so the pool's output can never share memory with the ReLU's input; a change
-// to that rule or to this look-ahead has to keep the two apart.  The ReLU's never-written output still owns its (shared) buffer.
+// to that rule or to this look-ahead that lets the two share memory fails prerun: the step carries what it reads and writes, and plan_i8
+// checks it (writes_what_it_reads).  The ReLU's never-written output still owns its (shared) buffer.
 static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni)
 {
     HNode& n = g->nodes[ni];
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
     if (!tamd_pin_int("relu_pool", 1) || !(n.p.relu.negative_slope >= 0.f) || x.is_view || y.is_view || x.nchw_raw) return 0;
-    if (count_consumers(g, n.out[0]) != 1) return 0;             // (a graph output counts as a consumer)
-    int pool_node = -1;
-    for (size_t nj = ni + 1; nj < g->nodes.size(); nj++)
-        if (g->nodes[nj].op == TAMD_OP_POOL && g->nodes[nj].in[0] == n.out[0] && !L.fused[nj]) { pool_node = (int)nj; break; }
-    if (pool_node < 0 || g->nodes[pool_node].p.pool.pool_method != 0) return 0;
+    const int pool_node = sole_reader(g, n.out[0]);              // (a graph output counts as a consumer)
+    if (pool_node < 0 || g->nodes[pool_node].op != TAMD_OP_POOL || L.fused[pool_node] || g->nodes[pool_node].p.pool.pool_method != 0) return 0;
     Planned p;
     if (plan_pool(g, g->nodes[pool_node], &p)) return -1;
     if (pool_is_global(p.pool)) return 0;                        // (plan_pool uploads nothing: the trial costs nothing)
@@ -839,6 +817,7 @@ static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni)
     a.p.x = (const int8_t*)x.dptr; a.p.cs_in = x.cs;
     a.slope = n.p.relu.negative_slope; a.relu_in_scale = x.scales[0];
     Step st = make_step(n.name + "+" + g->nodes[pool_node].name, "relu_pool_i8", 0, p.step.bytes, [a](hipStream_t s) { return launch_relu_pool(a, s); });
+    reads_writes(st, x, g->tensors[g->nodes[pool_node].out[0]], false);
     g->steps.push_back(st);
     L.fused[pool_node] = 1;
     g->fused_away[n.out[0]] = 1;
@@ -886,7 +865,7 @@ static int plan_upsample(tamd_graph* g, HNode& n)
     return 0;
 }
 
-static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, size_t ni)
+static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n)
 {
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
@@ -899,18 +878,12 @@ static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, size_t ni)
     std::string kname = "eltwise_i8";
     double bytes = 3.0 * xa.n * xa.h * xa.w * xa.c;
     // fuse the standalone ReLU that follows (ResNet: 16 x eltwise -> relu), SURVEY §8f-1
-    if (count_consumers(g, n.out[0]) == 1) {
-        for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
-            HNode& r = g->nodes[nj];
-            if (r.op == TAMD_OP_RELU && r.in[0] == n.out[0] && r.p.relu.negative_slope == 0.f) {
-                HTensor& ry = g->tensors[r.out[0]];
-                if (ry.is_view) break;
-                a.fuse_relu = ry.scales[0] == a.out_scale ? 2 : 1; a.relu_out_scale = ry.scales[0];
-                y = &ry; L.fused[nj] = 1; kname = "eltwise_relu_i8";
-                g->fused_away[n.out[0]] = 1;
-                break;
-            }
-        }
+    const int nj = sole_reader(g, n.out[0]);
+    if (nj >= 0 && g->nodes[nj].op == TAMD_OP_RELU && g->nodes[nj].p.relu.negative_slope == 0.f && !g->tensors[g->nodes[nj].out[0]].is_view) {
+        HTensor& ry = g->tensors[g->nodes[nj].out[0]];
+        a.fuse_relu = ry.scales[0] == a.out_scale ? 2 : 1; a.relu_out_scale = ry.scales[0];
+        y = &ry; L.fused[nj] = 1; kname = "eltwise_relu_i8";
+        g->fused_away[n.out[0]] = 1;
     }
     a.y = (int8_t*)y->dptr;
     Step st; st.node = n.name; st.kernel = kname; st.bytes = bytes;
@@ -934,6 +907,21 @@ static int plan_outputs(tamd_graph* g)
         st.fn = [a](hipStream_t s) { return launch_nhwc_to_nchw(a, s); };
         g->out_steps.push_back(st);
     }
+    return 0;
+}
+
+// A launch that writes what it reads is an error.  A fused launch runs at its first node's position -- chain4 and ReLU + pool even ahead
+// of node order -- and writes its output while other blocks still read its input; only plan_buffers' birth rule keeps the two out of one
+// shared buffer.  Every step that states what it reads and writes (reads_writes) is checked
+static int writes_what_it_reads(const tamd_graph* g)
+{
+    for (auto& st : g->steps)
+        for (auto& w : st.wr)
+            for (auto& r : st.rd)
+                if (access_overlap(w, r)) {
+                    set_error("launch %s (%s) writes memory that it reads: its output shares a buffer with its input", st.kernel.c_str(), st.node.c_str());
+                    return -1;
+                }
     return 0;
 }
 
@@ -961,14 +949,14 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n); break;
         case TAMD_OP_RELU: r = plan_relu(g, L, ni); break;
         case TAMD_OP_UPSAMPLE: r = plan_upsample(g, n); break;
-        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, ni); break;
+        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;
         }
         if (r) return -1;
     }
-    return plan_outputs(g);
+    return writes_what_it_reads(g) ? -1 : plan_outputs(g);
 }
 
 }  // namespace tamd

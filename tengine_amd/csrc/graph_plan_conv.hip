@@ -490,9 +490,7 @@ int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* 
     default: r = conv_i8_direct(c, out); break;
     }
     if (r) return -1;
-    if (!fz) {                           // reads its input, writes its output (constants aside), one launch: all a convolution / FC step touches
-        st.rd.push_back(access_of(c.x)); st.wr.push_back(access_of(c.y)); st.deps = true;
-    }
+    if (!fz) reads_writes(st, c.x, c.y);      // its input, its output (constants aside), one launch: all a convolution / FC step touches
     return 0;
 }
 

@@ -25,7 +25,7 @@ int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod)
     const tamd_conv_param& p = n.p.conv;
     const HTensor& x = g->tensors[n.in[0]];
     const HTensor& y = g->tensors[n.out[0]];
-    if (p.group != 1 || y.is_view || x.dtype != TAMD_DT_INT8 || count_consumers(g, n.out[0]) != 1) return -1;
+    if (p.group != 1 || y.is_view || x.dtype != TAMD_DT_INT8) return -1;
     if (x.nchw_raw) {
         // the network's first conv, gathered from the NCHW graph input: patch rows of 4 consecutive bytes (KW <= 4, no
         // x dilation), at most 16 rows (c, ky) = one 64-deep K step; row offsets of 24 bits, ky*DH of 4
@@ -37,27 +37,24 @@ int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod)
         if (p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_h0 || p.pad_h1 || p.pad_w0 || p.pad_w1) return -1;
         *prod = 0;
     }
-    for (auto& o : g->outputs) if (o.tensor == n.out[0]) return -1;
-    for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
-        const HNode& c = g->nodes[nj];
-        if (c.in.empty() || c.in[0] != n.out[0]) continue;
-        const HTensor& o = g->tensors[c.out[0]];
-        if (c.op == TAMD_OP_CONV && c.in.size() >= 2) {
-            const tamd_conv_param& q = c.p.conv;
-            const bool dw3 = is_dw3x3(q, y.c, o.c) && q.pad_h0 >= 0 && q.pad_w0 >= 0 && q.pad_h0 <= 2 && q.pad_w0 <= 2;
-            if (!dw3 || o.scales.empty() || g->tensors[c.in[1]].scales.empty()) return -1;
-            *tmode = 1;
-            return (int)nj;
-        }
-        if (c.op == TAMD_OP_POOL && *prod == 0) {
-            const PoolGeom pg = pool_geom(c.p.pool, y.h, y.w);
-            const int m = c.p.pool.pool_method;
-            if (pg.oh != 1 || pg.ow != 1 || pg.kh != y.h || pg.kw != y.w || pg.ph0 || pg.pw0 || (m != 0 && m != 1) || y.h * y.w > 1024 || o.scales.empty())
-                return -1;
-            *tmode = 0;
-            return (int)nj;
-        }
-        return -1;
+    const int nj = sole_reader(g, n.out[0]);
+    if (nj < 0) return -1;
+    const HNode& c = g->nodes[nj];
+    const HTensor& o = g->tensors[c.out[0]];
+    if (c.op == TAMD_OP_CONV && c.in.size() >= 2) {
+        const tamd_conv_param& q = c.p.conv;
+        const bool dw3 = is_dw3x3(q, y.c, o.c) && q.pad_h0 >= 0 && q.pad_w0 >= 0 && q.pad_h0 <= 2 && q.pad_w0 <= 2;
+        if (!dw3 || o.scales.empty() || g->tensors[c.in[1]].scales.empty()) return -1;
+        *tmode = 1;
+        return nj;
+    }
+    if (c.op == TAMD_OP_POOL && *prod == 0) {
+        const PoolGeom pg = pool_geom(c.p.pool, y.h, y.w);
+        const int m = c.p.pool.pool_method;
+        if (pg.oh != 1 || pg.ow != 1 || pg.kh != y.h || pg.kw != y.w || pg.ph0 || pg.pw0 || (m != 0 && m != 1) || y.h * y.w > 1024 || o.scales.empty())
+            return -1;
+        *tmode = 0;
+        return nj;
     }
     return -1;
 }
@@ -69,9 +66,56 @@ static RaceCand two_launches(const std::string& tag, const Step& sa, const Step&
     return {tag, [fa, fb](hipStream_t s) { const hipError_t e = fa(s); return e != hipSuccess ? e : fb(s); }, sa.kernel + " + " + sb.kernel};
 }
 
+// ---- what plan_pwdw and plan_chain4 share ------------------------------------------------------------------------------------------
+// The depthwise 3x3 launch `p` planned for node `dn` of C channels: its kernel arguments hold the taps, the bias and the requantisation
+// that plan_conv folded (conv_mode at the graph's batch) and uploaded -- DwArgs::w / bias / wscale / rq, rows of rup(C, 16) channels --
+// and a fused launch reads those.  null: not planned in that form, or a weight / bias tensor of the wrong size (plan_conv does not look)
+static const DwArgs* planned_dw(tamd_graph* g, const HNode& dn, const Planned& p, int C)
+{
+    const HTensor& w = g->tensors[dn.in[1]];
+    const HTensor* b = dn.in.size() > 2 ? &g->tensors[dn.in[2]] : nullptr;
+    if (p.kind != Planned::DW3X3 || w.elems() != (size_t)C * 9 || (b && b->elems() < (size_t)C)) return nullptr;
+    return &p.dw;
+}
+
+// The producer that is the network's first convolution (prod 1; find_pwdw_tail checked its limits), for PwDwArgs | Chain4Args: the
+// weight rows as the kernels walk them in *wrows -- [C][cin*KH*4], k = (c*KH + ky)*4 + kx, a patch row padded to 4 taps -- the 16-entry
+// row table (c, ky) -> (c*H*W + ky*DH*W) | ky*DH << 28 uploaded (a->taps), and the geometry of the NCHW input
+template <typename Args>
+static int first_conv_producer(tamd_graph* g, const HTensor& x, const HTensor& w, const tamd_conv_param& pp, int C, std::vector<int8_t>* wrows, Args* a)
+{
+    const int nrows = x.c * pp.kernel_h, Kw = nrows * pp.kernel_w, K = nrows * 4;
+    const int8_t* wd = (const int8_t*)w.data.data();
+    wrows->assign((size_t)C * K, 0);
+    for (int c = 0; c < C; c++)
+        for (int r = 0; r < nrows; r++)
+            for (int kx = 0; kx < pp.kernel_w; kx++) (*wrows)[(size_t)c * K + r * 4 + kx] = wd[(size_t)c * Kw + r * pp.kernel_w + kx];
+    std::vector<unsigned> rows(16, 0u);
+    for (int r = 0; r < nrows; r++) {
+        const int ky = r % pp.kernel_h, ci = r / pp.kernel_h;
+        rows[r] = (unsigned)(ci * x.h * x.w + ky * pp.dilation_h * x.w) | ((unsigned)(ky * pp.dilation_h) << 28);
+    }
+    unsigned* dt;
+    if (upload(g, rows, &dt)) return -1;
+    a->taps = dt; a->in_C = x.c; a->in_H = x.h; a->in_W = x.w;
+    a->fSH = pp.stride_h; a->fSW = pp.stride_w; a->fPH = pp.pad_h0; a->fPW = pp.pad_w0;
+    return 0;
+}
+
+// TAMD_PIN=<key>=THxTWxthreads[xSL] (tests): the pinned tile, clamped to the OH x OW map; *sl = 1 where none is given.  false: no such pin
+static bool pinned_tile(const char* key, int OH, int OW, int* th, int* tw, int* threads, int* sl)
+{
+    const char* pin = tamd_pin(key);
+    *sl = 1;
+    if (!pin || sscanf(pin, "%dx%dx%dx%d", th, tw, threads, sl) < 3) return false;
+    *th = std::min(*th, OH); *tw = std::min(*tw, OW);
+    return *th >= 1 && *tw >= 1;
+}
 
 // The two nodes were just planned as `pa` (the pointwise conv) and `pb` (its tail); build the fused launch, and keep whichever is
-// faster (plan-time measurement; without autotune: fuse the small-map cases where launches, not bytes, are the cost).
+// faster (plan-time measurement; without autotune: fuse the small-map cases where launches, not bytes, are the cost).  The producer's
+// constants are folded here (a first conv of more than 128 outputs is planned as a generic direct launch and keeps none), the
+// depthwise tail's are the ones `pb` uploaded.
 // TAMD_FUSE_PWDW=0 never fuses, =2 always fuses; TAMD_PWDW_CFG="TH,TW,threads" pins the tile configuration (tests).
 int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Planned& pa, const Planned& pb, Step* fused)
 {
@@ -89,16 +133,15 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     const int K = prod == 1 ? cin * pp.kernel_h * 4 : cin;                      // reduction length as the kernel walks it
     const int ktot = prod == 1 ? K : rup(cin, 16), steps = pwdw_steps((ktot + 63) / 64), nsteps = rup((ktot + 63) / 64, steps);
     if (w.elems() != (size_t)C * Kw || (b && b->elems() < (size_t)C)) return 0;
+    const DwArgs* dwp = tmode == 1 ? planned_dw(g, tl, pb, C) : nullptr;
+    if (tmode == 1 && !dwp) return 0;
     PwDwArgs a{};
     {
         const RqFold rq = fold_requant(RQ_CONV_HCL, pp.activation, x.scales[0], mid.scales[0], w, C);
         const int8_t* wd = (const int8_t*)w.data.data();
         std::vector<int8_t> wrows;
-        if (prod == 1) {                // k = (c*KH + ky)*4 + kx: rows padded to 4 taps
-            wrows.assign((size_t)C * K, 0);
-            for (int c = 0; c < C; c++)
-                for (int r = 0; r < cin * pp.kernel_h; r++)
-                    for (int kx = 0; kx < pp.kernel_w; kx++) wrows[(size_t)c * K + r * 4 + kx] = wd[(size_t)c * Kw + r * pp.kernel_w + kx];
+        if (prod == 1) {
+            if (first_conv_producer(g, x, w, pp, C, &wrows, &a)) return -1;
             wd = wrows.data();
         }
         const std::vector<int8_t> wf = pack_pw_panel(wd, C, K, nsteps);
@@ -112,17 +155,6 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     // the larger operand is the one every XCD should fetch only its share of (pwdw.hip: block -> XCD mapping)
     a.tile_major = (double)x.h * x.w * (prod == 1 ? x.c : x.cs) * (slices >= 8 ? 8 : slices) > (double)C * ktot * 8.0 ? 1 : 0;
     if (slices > 65535) a.tile_major = 0;
-    if (prod == 1) {
-        std::vector<unsigned> rows(16, 0u);
-        for (int r = 0; r < cin * pp.kernel_h; r++) {
-            const int ky = r % pp.kernel_h, ci = r / pp.kernel_h;
-            rows[r] = (unsigned)(ci * x.h * x.w + ky * pp.dilation_h * x.w) | ((unsigned)(ky * pp.dilation_h) << 28);
-        }
-        unsigned* dt;
-        if (upload(g, rows, &dt)) return -1;
-        a.taps = dt; a.in_C = cin; a.in_H = x.h; a.in_W = x.w;
-        a.fSH = pp.stride_h; a.fSW = pp.stride_w; a.fPH = pp.pad_h0; a.fPW = pp.pad_w0;
-    }
     a.x = (const int8_t*)x.dptr + (prod == 1 ? 0 : x.c_off);
     a.N = x.n; a.H = mid.h; a.W = mid.w; a.cs_in = x.cs; a.ktot = ktot; a.nsteps = nsteps; a.steps = steps;
     a.mode = tmode; a.cw = cw; a.slices = slices;
@@ -130,17 +162,8 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     a.c_limit = store_limit(y, C);
     a.S = 1; a.OH = a.OW = 1; a.TH = a.TW = 1; a.tiles_x = a.tiles_y = 1; a.RH = mid.h; a.RW = mid.w;
     if (tmode == 1) {
-        const tamd_conv_param& q = tl.p.conv;
-        HTensor& dwt = g->tensors[tl.in[1]];
-        HTensor* db = tl.in.size() > 2 ? &g->tensors[tl.in[2]] : nullptr;
-        if (dwt.elems() != (size_t)C * 9 || (db && db->elems() < (size_t)C)) return 0;
-        const RqFold rq = fold_requant(conv_mode(q, g->formula_batch ? g->formula_batch : mid.n, C, C), q.activation, mid.scales[0], y.scales[0], dwt, C);
-        const std::vector<int8_t> wp = pack_dw3x3((const int8_t*)dwt.data.data(), C, cw);
-        const std::vector<int32_t> bp = padded_bias(db ? (const int32_t*)db->data.data() : nullptr, C, cw);
-        int8_t* d0; int32_t* d1;
-        if (upload(g, wp, &d0) || upload(g, bp, &d1) || upload_rq(g, rq, cw, &a.dw_wscale, &a.d_rq)) return -1;
-        a.dw_w = d0; a.dw_bias = d1;
-        a.S = q.stride_h; a.PH = q.pad_h0; a.PW = q.pad_w0; a.OH = y.h; a.OW = y.w;
+        a.dw_w = dwp->w; a.dw_bias = dwp->bias; a.dw_wscale = dwp->wscale; a.d_rq = dwp->rq;
+        a.S = dwp->S; a.PH = dwp->PH; a.PW = dwp->PW; a.OH = dwp->OH; a.OW = dwp->OW;
     } else {
         a.pool_method = tl.p.pool.pool_method; a.p_in_scale = mid.scales[0]; a.p_out_scale = y.scales[0];
     }
@@ -194,13 +217,10 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
         }
         cfgs = keep;
     }
-    if (const char* pin = tamd_pin("pwdw_cfg")) {
-        int th = 0, tw = 0, threads = 0, sl = 1;      // "THxTWxthreads" or "THxTWxthreadsx2" / "..x4" (two / four slices per block)
-        if (sscanf(pin, "%dx%dx%dx%d", &th, &tw, &threads, &sl) >= 3 && tmode == 1) {
-            th = std::min(th, a.OH); tw = std::min(tw, a.OW);
-            if ((sl != 2 && sl != 4) || slices % sl != 0 || nsteps > steps) sl = 1;
-            if (th >= 1 && tw >= 1 && pwdw_config_ok(with_tiles(a, th, tw, sl), threads)) { cfgs.clear(); cfgs.push_back({th, tw, threads, 0.0, sl}); }
-        }
+    int pth = 0, ptw = 0, pthreads = 0, psl = 1;      // "THxTWxthreads" or "THxTWxthreadsx2" / "..x4" (two / four slices per block)
+    if (tmode == 1 && pinned_tile("pwdw_cfg", a.OH, a.OW, &pth, &ptw, &pthreads, &psl)) {
+        if ((psl != 2 && psl != 4) || slices % psl != 0 || nsteps > steps) psl = 1;
+        if (pwdw_config_ok(with_tiles(a, pth, ptw, psl), pthreads)) { cfgs.clear(); cfgs.push_back({pth, ptw, pthreads, 0.0, psl}); }
     }
     if (cfgs.empty()) return 0;
     const Step& sa = pa.step;
@@ -252,18 +272,12 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     if (!fuse) return 0;
     const PwDwArgs v = tmode == 1 ? with_tiles(a, cfgs[best].th, cfgs[best].tw, cfgs[best].sl) : a;
     const int threads = cfgs[best].threads;
-    Step& st = *fused;
-    st.node = sa.node + "+" + sb.node;
     char nm[48];
     if (tmode == 1) snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d%s>", prod == 1 ? "firstdw" : "pwdw", a.S, v.TH, v.TW, threads, v.sl == 4 ? ",c64" : v.sl == 2 ? ",c32" : "");
     else snprintf(nm, sizeof(nm), "pwpool_i8<%d>", threads);
-    st.kernel = nm;
-    st.macs = sa.macs + sb.macs;
-    st.bytes = sa.bytes + sb.bytes;      // SURVEY 8(d) accounting, per layer: the intermediate tensor still counts as algorithmic bytes
-    st.fn = [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); };
-    if (prod == 1 && tmode == 1) {       // the first layer pair: reads the graph input, writes the depthwise output, nothing else (run_steps: wrap)
-        st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
-    }
+    *fused = fused_step({&pa, &pb}, nm, [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); });
+    // reads the pointwise input, writes the tail's output, nothing else; the first layer pair may run beside its predecessors (run_steps: wrap)
+    reads_writes(*fused, x, y, prod == 1 && tmode == 1);
     g->fused_away[pw.out[0]] = 1;
     return 1;
 }
@@ -296,12 +310,9 @@ bool find_chain4(tamd_graph* g, size_t ni, int tail, int prod, const std::vector
     const HTensor& y1 = g->tensors[d1.out[0]];
     if (pin != 2 && !(x.n == 1 && (TAMD_CHAIN4_DEFAULT & (prod == 1 ? 1 : 2)))) return false;
     auto pads01 = [](const tamd_conv_param& q) { return q.pad_h0 >= 0 && q.pad_h0 <= 1 && q.pad_w0 >= 0 && q.pad_w0 <= 1 && q.pad_h1 >= 0 && q.pad_h1 <= 1 && q.pad_w1 >= 0 && q.pad_w1 <= 1; };
-    if (d1.p.conv.stride_h != 1 || !pads01(d1.p.conv) || y1.is_view || count_consumers(g, d1.out[0]) != 1) return false;
-    for (auto& o : g->outputs) if (o.tensor == d1.out[0]) return false;
+    if (d1.p.conv.stride_h != 1 || !pads01(d1.p.conv) || y1.is_view) return false;
     if (g->tensors[n0.out[0]].c > 128 || (prod == 0 && x.c > 128)) return false;
-    int pj = -1;
-    for (size_t nj = (size_t)tail + 1; nj < g->nodes.size() && pj < 0; nj++)
-        if (!g->nodes[nj].in.empty() && g->nodes[nj].in[0] == d1.out[0]) pj = (int)nj;
+    const int pj = sole_reader(g, d1.out[0]);
     if (pj < 0 || taken(pj) || g->nodes[pj].op != TAMD_OP_CONV) return false;
     int tmode = -1, prod2 = 0;
     const int dj = find_pwdw_tail(g, (size_t)pj, &tmode, &prod2);
@@ -310,8 +321,9 @@ bool find_chain4(tamd_graph* g, size_t ni, int tail, int prod, const std::vector
     return true;
 }
 
-// The four nodes were just planned as pa .. pd (their macs / bytes; the fused launch folds its own constants with the functions those
-// plans used).  TAMD_PIN=chain4_cfg=THxTWxthreads pins the tile.  0: no tile configuration fits -- the pairs stay as they are.
+// The four nodes were just planned as pa .. pd.  The two GEMM nodes' constants are folded here (the multipliers go into the blob the
+// kernel stages into LDS, and a first conv may have been planned in a form that keeps none); the two depthwise nodes' are the ones pb
+// and pd uploaded.  TAMD_PIN=chain4_cfg=THxTWxthreads pins the tile.  0: no tile configuration fits -- the pairs stay as they are.
 int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int prod, const Planned& pa, const Planned& pb, const Planned& pc, const Planned& pd, Step* fused)
 {
     HTensor& x = g->tensors[n0.in[0]];
@@ -330,19 +342,23 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
     const int ks0 = ((prod == 1 ? K : rup(cin, 16)) + 63) / 64, ks2 = (ns1 * 16 + 63) / 64;
     if (w0.elems() != (size_t)C1 * Kw || (b0 && b0->elems() < (size_t)C1) || w2.elems() != (size_t)C2 * C1 || (b2 && b2->elems() < (size_t)C2)) return 0;
     if (m1.c != C1 || y.c != C2 || m1.h != m2.h || m1.w != m2.w || ks0 > 2 || ks2 > 2 || (prod == 1 && ks0 != 1)) return 0;
+    // the two depthwise nodes: taps, bias and multipliers per thread from memory (DwArgs layout), as planned.  (The reference picks the
+    // depthwise formula by batch == 1: conv_mode)
+    const DwArgs *dw1 = planned_dw(g, d1, pb, C1), *dw2 = planned_dw(g, d2, pd, C2);
+    if (!dw1 || !dw2) return 0;
     Chain4Args a{};
     RqArgs rq[4];
+    rq[1] = dw1->rq; rq[3] = dw2->rq;
+    a.dw1_w = dw1->w; a.dw1_bias = dw1->bias; a.dw1_wscale = dw1->wscale;
+    a.dw2_w = dw2->w; a.dw2_bias = dw2->bias; a.dw2_wscale = dw2->wscale;
     std::vector<float> mf0, mf2;
     // the two GEMM nodes: panels, bias and multiplier vectors go into the blob the kernel stages into LDS
     std::vector<int8_t> wf0, wf2;
     {
         const int8_t* wd = (const int8_t*)w0.data.data();
         std::vector<int8_t> wrows;
-        if (prod == 1) {                // k = (c*KH + ky)*4 + kx: rows padded to 4 taps (plan_pwdw)
-            wrows.assign((size_t)C1 * K, 0);
-            for (int c = 0; c < C1; c++)
-                for (int r = 0; r < cin * pp.kernel_h; r++)
-                    for (int kx = 0; kx < pp.kernel_w; kx++) wrows[(size_t)c * K + r * 4 + kx] = wd[(size_t)c * Kw + r * pp.kernel_w + kx];
+        if (prod == 1) {
+            if (first_conv_producer(g, x, w0, pp, C1, &wrows, &a)) return -1;
             wd = wrows.data();
         }
         wf0 = pack_pw_panel(wd, C1, K, ks0);
@@ -351,23 +367,6 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
         if (upload_rq_m2(g, fold_requant(RQ_CONV_HCL, pp.activation, x.scales[0], m0.scales[0], w0, C1), ns1 * 16, &mf0, &rq[0])) return -1;
         if (upload_rq_m2(g, fold_requant(RQ_CONV_HCL, p2.p.conv.activation, m1.scales[0], m2.scales[0], w2, C2), ns2 * 16, &mf2, &rq[2])) return -1;
     }
-    // the two depthwise nodes: taps, bias and multipliers per thread from memory (DwArgs layout).  The reference picks the depthwise
-    // formula by batch == 1 (conv_mode)
-    auto fold_dw = [&](HNode& dn, const HTensor& in, const HTensor& out, int C, int cw, const int8_t** w, const int32_t** bias, const float** ws, RqArgs* r) {
-        const tamd_conv_param& q = dn.p.conv;
-        HTensor& dwt = g->tensors[dn.in[1]];
-        HTensor* db = dn.in.size() > 2 ? &g->tensors[dn.in[2]] : nullptr;
-        if (dwt.elems() != (size_t)C * 9 || (db && db->elems() < (size_t)C)) return 1;
-        const RqFold f = fold_requant(conv_mode(q, g->formula_batch ? g->formula_batch : in.n, C, C), q.activation, in.scales[0], out.scales[0], dwt, C);
-        const std::vector<int8_t> wp = pack_dw3x3((const int8_t*)dwt.data.data(), C, cw);
-        const std::vector<int32_t> bp = padded_bias(db ? (const int32_t*)db->data.data() : nullptr, C, cw);
-        int8_t* d0; int32_t* dd1;
-        if (upload(g, wp, &d0) || upload(g, bp, &dd1) || upload_rq(g, f, cw, ws, r)) return -1;
-        *w = d0; *bias = dd1;
-        return 0;
-    };
-    if (int e = fold_dw(d1, m0, m1, C1, ns1 * 16, &a.dw1_w, &a.dw1_bias, &a.dw1_wscale, &rq[1])) return e < 0 ? -1 : 0;
-    if (int e = fold_dw(d2, m2, y, C2, ns2 * 16, &a.dw2_w, &a.dw2_bias, &a.dw2_wscale, &rq[3])) return e < 0 ? -1 : 0;
     {
         std::vector<int8_t> blob;
         auto put = [&](const void* p, size_t bytes) { const int off = (int)blob.size(); blob.insert(blob.end(), (const int8_t*)p, (const int8_t*)p + bytes); return off; };
@@ -389,17 +388,6 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
     a.win = rq_win(rq[0]) && rq_win(rq[1]) && rq_win(rq[2]) && rq_win(rq[3]) ? 1 : 0;
     a.prod = prod;
     a.coherent = (g->opt.direct_dispatch && !exp_plain_kernels()) ? 1 : 0;
-    if (prod == 1) {
-        std::vector<unsigned> rows(16, 0u);
-        for (int r = 0; r < cin * pp.kernel_h; r++) {
-            const int ky = r % pp.kernel_h, ci = r / pp.kernel_h;
-            rows[r] = (unsigned)(ci * x.h * x.w + ky * pp.dilation_h * x.w) | ((unsigned)(ky * pp.dilation_h) << 28);
-        }
-        unsigned* dt;
-        if (upload(g, rows, &dt)) return -1;
-        a.taps = dt; a.in_C = cin; a.in_H = x.h; a.in_W = x.w;
-        a.fSH = pp.stride_h; a.fSW = pp.stride_w; a.fPH = pp.pad_h0; a.fPW = pp.pad_w0;
-    }
     a.x = (const int8_t*)x.dptr + (prod == 1 ? 0 : x.c_off);
     a.N = x.n; a.cs_in = x.cs; a.H0 = m0.h; a.W0 = m0.w; a.H1 = m1.h; a.W1 = m1.w; a.OH = y.h; a.OW = y.w;
     a.P1H = d1.p.conv.pad_h0; a.P1W = d1.p.conv.pad_w0; a.S2 = d2.p.conv.stride_h; a.P2H = d2.p.conv.pad_h0; a.P2W = d2.p.conv.pad_w0;
@@ -431,15 +419,11 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
             cfgs.push_back({th, tw, threads, std::ceil(blocks / (256.0 * (threads == 256 ? 2 : 1))) * block});
         }
     std::sort(cfgs.begin(), cfgs.end(), [](const Cfg& l, const Cfg& r) { return l.cost < r.cost; });
-    if (const char* pin = tamd_pin("chain4_cfg")) {
-        int th = 0, tw = 0, threads = 0;
-        if (sscanf(pin, "%dx%dx%d", &th, &tw, &threads) == 3) {
-            th = std::min(th, a.OH); tw = std::min(tw, a.OW);
-            if (th >= 1 && tw >= 1 && chain4_config_ok(with_tiles(a, th, tw), threads)) { cfgs.clear(); cfgs.push_back({th, tw, threads, 0.0}); }
-        }
+    int pth = 0, ptw = 0, pthreads = 0, psl = 1;
+    if (pinned_tile("chain4_cfg", a.OH, a.OW, &pth, &ptw, &pthreads, &psl) && chain4_config_ok(with_tiles(a, pth, ptw), pthreads)) {
+        cfgs.clear(); cfgs.push_back({pth, ptw, pthreads, 0.0});
     }
     if (cfgs.empty()) return 0;
-    const std::string node = pa.step.node + "+" + pb.step.node + "+" + pc.step.node + "+" + pd.step.node;
     std::vector<RaceCand> tiles;
     for (size_t c = 0; c < cfgs.size(); c++) {
         const Chain4Args v = with_tiles(a, cfgs[c].th, cfgs[c].tw);
@@ -454,17 +438,10 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
     if (best < 0) return -1;
     const Chain4Args v = with_tiles(a, cfgs[best].th, cfgs[best].tw);
     const int threads = cfgs[best].threads;
-    Step& st = *fused;
-    st.node = node;
     char nm[64];
     snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d>", prod == 1 ? "firstchain4" : "chain4", a.S2, v.TH, v.TW, threads);
-    st.kernel = nm;
-    st.macs = pa.step.macs + pb.step.macs + pc.step.macs + pd.step.macs;
-    st.bytes = pa.step.bytes + pb.step.bytes + pc.step.bytes + pd.step.bytes;      // SURVEY 8(d) accounting, per layer: the three intermediate maps still count
-    st.fn = [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); };
-    if (prod == 1) {                     // reads the graph input, writes the last depthwise's output, nothing else (plan_pwdw: the first layer pair)
-        st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = true;
-    }
+    *fused = fused_step({&pa, &pb, &pc, &pd}, nm, [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); });
+    reads_writes(*fused, x, y, prod == 1);      // reads the producer's input, writes the last depthwise's output, nothing else (deps: as plan_pwdw)
     g->fused_away[n0.out[0]] = 1;
     g->fused_away[d1.out[0]] = 1;
     g->fused_away[p2.out[0]] = 1;
@@ -494,25 +471,18 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& pd, const Plan
     a.y = c.y;
     a.N = d.N; a.H = d.H; a.W = d.W; a.C = d.C; a.cs_in = d.cs_in; a.cw = d.cw; a.OH = d.OH; a.OW = d.OW; a.PH = d.PH; a.PW = d.PW;
     a.cout = c.cout; a.ldc = c.ldc; a.c_off = c.c_off; a.c_limit = c.c_limit;
-    const Step& sa = pd.step;
-    const Step& sb = pc.step;
     bool fuse = fmode == 2;
     if (fmode != 2) {
         char ckey[256];
-        snprintf(ckey, sizeof(ckey), "dwpw|%s|n%d %dx%d c%d>%d", sa.node.c_str(), d.N, d.OH, d.OW, d.C, c.cout);
+        snprintf(ckey, sizeof(ckey), "dwpw|%s|n%d %dx%d c%d>%d", pd.step.node.c_str(), d.N, d.OH, d.OW, d.C, c.cout);
         const RaceCand one{"1", [a](hipStream_t s) { return launch_dwpw(a, s); }, "dwpw_i8"};
-        const int w = plan_race(g, sa.node, {two_launches("0", sa, sb), one}, ckey, 0.97f, autotune_enabled());
+        const int w = plan_race(g, pd.step.node, {two_launches("0", pd.step, pc.step), one}, ckey, 0.97f, autotune_enabled());
         if (w < 0) return -1;
         fuse = w == 1;
     }
     if (!fuse) return 0;
-    Step& st = *fused;
-    st.node = sa.node + "+" + sb.node;
-    st.kernel = "dwpw_i8";
-    st.macs = sa.macs + sb.macs;
-    st.bytes = sa.bytes + sb.bytes;      // SURVEY 8(d) accounting, per layer: the intermediate tensor still counts as algorithmic bytes
-    st.fn = [a](hipStream_t s) { return launch_dwpw(a, s); };
-    st.rd.push_back(access_of(g->tensors[dw.in[0]])); st.wr.push_back(access_of(g->tensors[pw.out[0]])); st.deps = true;
+    *fused = fused_step({&pd, &pc}, "dwpw_i8", [a](hipStream_t s) { return launch_dwpw(a, s); });
+    reads_writes(*fused, g->tensors[dw.in[0]], g->tensors[pw.out[0]]);
     g->fused_away[dw.out[0]] = 1;
     return 1;
 }
@@ -541,13 +511,8 @@ int plan_block(tamd_graph* g, HNode& na, HNode& nb, HNode& nc, const FusedElt& f
     int8_t* dwp = nullptr;
     if (upload(g, wp, &dwp)) return -1;
     const BlockArgs v = block_args(a, pb.gemm, pc.gemm_tail, dwp);
-    Step& st = *fused;
-    st.node = pa.step.node + "+" + pb.step.node + "+" + pc.step.node;
-    st.kernel = "block_i8";
-    st.macs = pa.step.macs + pb.step.macs + pc.step.macs;
-    st.bytes = pa.step.bytes + pb.step.bytes + pc.step.bytes;      // SURVEY 8(d) accounting, per layer: both intermediate maps still count
-    st.fn = [v](hipStream_t s) { return launch_block(v, s); };
-    st.rd.push_back(access_of(g->tensors[na.in[0]])); st.wr.push_back(access_of(g->tensors[fz.out_tensor])); st.deps = true;
+    *fused = fused_step({&pa, &pb, &pc}, "block_i8", [v](hipStream_t s) { return launch_block(v, s); });
+    reads_writes(*fused, g->tensors[na.in[0]], g->tensors[fz.out_tensor]);
     g->fused_away[na.out[0]] = 1;
     g->fused_away[nb.out[0]] = 1;
     return 1;

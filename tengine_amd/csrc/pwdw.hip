@@ -208,24 +208,7 @@ __device__ __forceinline__ void pwdw_block(const PwDwArgs& a, unsigned* __restri
 #pragma unroll
             for (int u = 0; u < STEPS; u++) bf[u] = *reinterpret_cast<const v4i*>(xp + (chunk * STEPS + u) * 64);
         } else {
-            // patch rows of conv output pixel (piy, pix).  Column handling is the same for every row: bytes left of the image
-            // are shifted in as zeros, bytes right of it masked; rows above / below the image are zero.  All four loads are
-            // unconditional (clamped addresses) so they fly together.
-            const int iyb = piy * a.fSH - a.fPH, ixb = pix * a.fSW - a.fPW;
-            const int sft = max(-ixb, 0), xs = max(ixb, 0), nvalid = a.in_W - ixb;
-            const bool colok = nvalid > 0 && sft < 4;
-            const unsigned cmask = nvalid < 4 ? (1u << (8 * max(nvalid, 0))) - 1u : ~0u;
-            const int base = iyb * a.in_W + xs;
-            unsigned raw[4];
-            bool ok[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int iy = iyb + (int)(rows[j] >> 28);
-                ok[j] = colok && (unsigned)iy < (unsigned)a.in_H;
-                __builtin_memcpy(&raw[j], xp + (ok[j] ? base + (int)(rows[j] & 0xffffffu) : 0), 4);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) bf[0][j] = ok[j] ? (int)((raw[j] << (8 * sft)) & cmask) : 0;
+            gather_patch_rows(a, xp, rows, piy, pix, bf[0]);       // (dw_common.h)
         }
     };
     const int soff = (a.RH * a.RW + 4) * 4;               // dwords between the slices' copies of the region

@@ -291,9 +291,11 @@ def i8_concat_graph(seed, n, c, h, w, axis=1, shrink=False):
     return g, rng.integers(-127, 128, size=(n, c, h, w)).astype(np.int8)
 
 
-def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", pool_alg=1, bias=True, first=None):
+def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", pool_alg=1, bias=True, first=None, mid_output=False, sum_tail=False):
     """int8: pointwise 1x1 conv (cin -> c) -> depthwise 3x3 (stride s, pad p) | global pooling: the pair pwdw.hip fuses.
-    `first` = (k, stride, pad[, dilation]): the producer is a k x k conv on the graph input instead (network's first layer)"""
+    `first` = (k, stride, pad[, dilation]): the producer is a k x k conv on the graph input instead (network's first layer);
+    `mid_output`: the pointwise output is a graph output as well; `sum_tail`: an eltwise SUM (depthwise output, pointwise output) behind
+    the pair (stride 1, pad 1), so the pointwise output has a second reader that takes it as its SECOND input"""
     rng = np.random.default_rng(seed)
     fk, fs, fp, fd = (list(first) + [1])[:4] if first else (1, 1, 0, 1)
     g = Graph(name="pwdw_case")
@@ -308,7 +310,7 @@ def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", p
     h = (h - fd * (fk - 1) - 1 + 2 * fp) // fs + 1          # from here on: the producer's output map
     w = (w - fd * (fk - 1) - 1 + 2 * fp) // fs + 1
     mid = g.add_tensor("mid", [n, c, h, w], DT_INT8, tm2.TT_VAR, None, [ms], [0])
-    g.add_node("pw", "Convolution", ins, [mid], kernel_h=fk, kernel_w=fk, stride_h=fs, stride_w=fs, dilation_h=fd, dilation_w=fd,
+    pw = g.add_node("pw", "Convolution", ins, [mid], kernel_h=fk, kernel_w=fk, stride_h=fs, stride_w=fs, dilation_h=fd, dilation_w=fd,
                input_channel=cin, output_channel=c, group=1, activation=act_pw, pad_h0=fp, pad_w0=fp, pad_h1=fp, pad_w1=fp)
     if tail == "pool":
         os_ = float(np.float32(ms * rng.uniform(0.3, 0.9)))
@@ -328,7 +330,10 @@ def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", p
         ni = g.add_node("dw", "Convolution", dins, [y], kernel_h=3, kernel_w=3, stride_h=s, stride_w=s, dilation_h=1,
                         dilation_w=1, input_channel=c, output_channel=c, group=c, activation=act_dw, pad_h0=p, pad_w0=p,
                         pad_h1=p, pad_w1=p)
-    g.output_nodes = [ni]
+    if sum_tail:
+        e = g.add_tensor("sum", g.tensors[y].dims, DT_INT8, tm2.TT_VAR, None, [float(np.float32(max(ms, g.tensors[y].scales[0]) * 1.5))], [0])
+        ni = g.add_node("sum", "Eltwise", [y, mid], [e], type=tm2.ELT_SUM, caffe_flavor=1)
+    g.output_nodes = [pw, ni] if mid_output else [ni]
     return g, rng.integers(-127, 128, size=g.tensors[x].dims).astype(np.int8)
 
 

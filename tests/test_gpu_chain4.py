@@ -81,6 +81,7 @@ FIRST = (3, 2, 1)
 CASES = {
     "first_20x22": (dict(seed=11, n=1, cin=3, h=20, w=22, c1=32, c2=64, s2=2, first=FIRST), ["2x2x256", "4x4x512", "7x7x512"], True),
     "first_b2_odd_ragged": (dict(seed=12, n=2, cin=3, h=37, w=41, c1=24, c2=40, s2=2, first=FIRST), [None], False),
+    "first_b1_odd_ragged": (dict(seed=19, n=1, cin=3, h=37, w=41, c1=24, c2=40, s2=2, first=FIRST), [None], False),     # (batch 1: the other depthwise formula)
     "first_s1": (dict(seed=13, n=1, cin=3, h=30, w=30, c1=16, c2=32, s2=1, first=(3, 1, 1)), [None], False),
     "first_acts": (dict(seed=14, n=1, cin=3, h=26, w=18, c1=32, c2=64, s2=2, first=FIRST, acts=(NONE, RELU6, RELU, NONE)), [None], False),
     "pw_pairB_toy": (dict(seed=15, n=1, cin=64, h=12, w=10, c1=128, c2=128, s2=2), [None], True),

@@ -158,6 +158,64 @@ def test_first_conv_plus_depthwise(case):
     assert name.startswith("firstdw_i8"), name
 
 
+def run_all(g, x, fuse):
+    """every graph output and the launch list, with TAMD_FUSE_PWDW=fuse"""
+    os.environ["TAMD_FUSE_PWDW"] = str(fuse)
+    try:
+        gr = capi.Graph(tm2.write_tm2(g))
+    finally:
+        os.environ.pop("TAMD_FUSE_PWDW", None)
+    gr.set_input(x)
+    outs = gr.run()
+    names = [k["kernel"] for k in gr.profile(1)]
+    gr.close()
+    return outs, names
+
+
+def not_degenerate(want):
+    return len(np.unique(want)) >= 16 and np.count_nonzero(want == 0) < 0.8 * want.size
+
+
+def test_pointwise_output_that_is_a_graph_output_is_not_fused():
+    """the pointwise output has the depthwise AND the graph output behind it: two launches even where the switch says always"""
+    g, x = pwdw_graph(41, 1, 32, 9, 9, 32, mid_output=True)
+    want = oracle.run_graph(g, x)
+    outs, names = run_all(g, x, 2)
+    assert len(names) == 2 and not any(k.startswith(("pwdw", "firstdw")) for k in names), names
+    assert len(outs) == len(want) == 2
+    for got, ref in zip(outs, want):
+        assert not_degenerate(ref)
+        assert np.array_equal(got.reshape(ref.shape), ref)
+
+
+def test_pointwise_output_with_a_second_reader_is_not_fused():
+    """an eltwise SUM (depthwise output, pointwise output) behind the pair: the pointwise output is the first input of one node and the
+    second input of another"""
+    g, x = pwdw_graph(42, 1, 32, 9, 9, 32, sum_tail=True)
+    want = oracle.run_graph(g, x)[0]
+    assert not_degenerate(want)
+    outs, names = run_all(g, x, 2)
+    assert len(names) == 3 and not any(k.startswith(("pwdw", "firstdw")) for k in names), names
+    assert np.array_equal(outs[0].reshape(want.shape), want)
+
+
+# the depthwise constants of the fused launch are the ones the stand-alone depthwise launch folded and uploaded: ragged widths (C = 24, 40:
+# rows padded to 32, 48), both strides, and both depthwise formulas (batch 1: the hand-written kernel's, batch > 1: the naive reference's)
+RAGGED = [(n, c, s) for c in (24, 40) for s in (1, 2) for n in (1, 2)]
+
+
+@pytest.mark.parametrize("n,c,s", RAGGED)
+def test_ragged_pairs_share_the_planned_depthwise_constants(n, c, s):
+    g, x = pwdw_graph(1100 + 10 * c + 2 * s + n, n, 20, 13, 11, c, s, 1)
+    want = oracle.run_graph(g, x)[0]
+    assert not_degenerate(want)
+    (fused,), names_f = run_all(g, x, 2)
+    (unfused,), names_u = run_all(g, x, 0)
+    assert len(names_f) == 1 and names_f[0].startswith("pwdw_i8") and len(names_u) == 2, (names_f, names_u)
+    assert np.array_equal(fused.reshape(want.shape), want)
+    assert np.array_equal(fused, unfused)
+
+
 def test_fused_equals_unfused_on_device_and_intermediate_is_refused():
     g, x = pwdw_graph(77, 1, 128, 28, 28, 128, 1, 1)
     fused, names_f = run(g, x, 2)
