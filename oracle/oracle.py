@@ -43,8 +43,33 @@ def conv_variant(batch, p, cin, cout):
                                        p.get("pad_w1", 0), p.get("dilation_h", 1), p.get("dilation_w", 1))
 
 
+def _same_axis(inp, k, s, code):
+    """convolution.c:79-97 / :103-121 for one axis: (pad0, pad1) of a SAME pad code (-1: the smaller half first, any other
+    negative value: the larger half first).  pad_num holds no dilation; C's division truncates towards zero."""
+    out = (inp - 1) // s + 1
+    pad_num = (out - 1) * s + k - inp
+    half = int(pad_num / 2)
+    return (half, pad_num - half) if code == -1 else (pad_num - half, half)
+
+
+def conv_resolve_same(xd, p):
+    """What the reference's infer_shape leaves in conv_param (convolution.c:76-121): pad_h0 / pad_w0 < 0 are SAME codes, replaced
+    by explicit pads -- before the reference selects its kernel, so conv_variant and the kernels see these."""
+    if p.get("pad_h0", 0) >= 0 and p.get("pad_w0", 0) >= 0:
+        return p
+    p = dict(p)
+    for ax, inp in (("h", xd[2]), ("w", xd[3])):
+        if p.get("pad_%s0" % ax, 0) < 0:
+            p["pad_%s0" % ax], p["pad_%s1" % ax] = _same_axis(inp, p["kernel_" + ax], p["stride_" + ax], p["pad_%s0" % ax])
+    return p
+
+
 def conv_out_dims(xd, wd, p):
-    """source/operator/prototype/convolution.c:35-145 (explicit-pad branch)."""
+    """source/operator/prototype/convolution.c:35-145 as the reference ends up at run time.  infer_shape gives a SAME axis
+    (in - 1) / stride + 1 outputs and writes the resolved pads into conv_param; every run then calls the node's reshape
+    (cpu_device.c:115; conv_hcl_x86.c:196-240, conv_ref.c:115-160), which finds pads >= 0 and takes the explicit-pad formula.  The
+    two agree at dilation 1; with dilation the SAME pads hold none of it and the explicit formula's smaller map is what is computed."""
+    p = conv_resolve_same(xd, p)
     n, _, h, w = xd
     oh = (h - p.get("dilation_h", 1) * (p["kernel_h"] - 1) - 1 + p.get("pad_h0", 0) + p.get("pad_h1", 0)) // p["stride_h"] + 1
     ow = (w - p.get("dilation_w", 1) * (p["kernel_w"] - 1) - 1 + p.get("pad_w0", 0) + p.get("pad_w1", 0)) // p["stride_w"] + 1
@@ -55,6 +80,7 @@ def conv2d_int8(x, w, bias, p, in_scale, w_scales, out_scale, variant=None):
     x = np.ascontiguousarray(x, np.int8)
     w = np.ascontiguousarray(w, np.int8)
     n, cin, h, wd = x.shape
+    p = conv_resolve_same(x.shape, p)
     od = conv_out_dims(x.shape, w.shape, p)
     if variant is None:
         variant = conv_variant(n, p, cin, od[1])
@@ -73,6 +99,7 @@ def conv2d_fp32(x, w, bias, p):
     x = np.ascontiguousarray(x, np.float32)
     w = np.ascontiguousarray(w, np.float32)
     n, cin, h, wd = x.shape
+    p = conv_resolve_same(x.shape, p)
     od = conv_out_dims(x.shape, w.shape, p)
     y = np.empty(od, np.float32)
     b = None if bias is None else np.ascontiguousarray(bias, np.float32)
@@ -171,6 +198,7 @@ def conv2d_uint8(x, w, bias, p, in_q, w_q, out_q, variant=None):
     x = np.ascontiguousarray(x, np.uint8)
     w = np.ascontiguousarray(w, np.uint8)
     n, cin, h, wd = x.shape
+    p = conv_resolve_same(x.shape, p)
     od = conv_out_dims(x.shape, w.shape, p)
     if variant is None:
         variant = CONV_HCL if p.get("group", 1) == 1 else CONV_REF

@@ -434,7 +434,7 @@ bool conv_igemm_cfg_ok(const ConvArgs& a, int cfg) { return cfg < 5 || cfg >= 10
 
 hipError_t launch_conv_igemm(const ConvArgs& a, hipStream_t s)
 {
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0);
+    const bool is1x1 = conv_is_pointwise(a);
     switch (pick_cfg(a)) {
     case 0: return launch_cfg<128, 128, 64, 2, 2>(a, s, is1x1);
     case 1: return launch_cfg<128, 32, 64, 4, 1>(a, s, is1x1);

@@ -215,7 +215,7 @@ hipError_t launch_conv_igemm2(const ConvArgs& a, hipStream_t s)
 {
     static const int stages = env_int("TAMD_IGEMM2_STAGES", 3);
     const ConvArgs& b = a;
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0);
+    const bool is1x1 = conv_is_pointwise(a);
     if (use_bn128(a)) {
         if (stages <= 3) return launch2<128, 3>(b, s, is1x1);
         if (stages == 4) return launch2<128, 4>(b, s, is1x1);

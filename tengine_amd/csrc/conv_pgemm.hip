@@ -273,9 +273,11 @@ static int pg_env(const char* name, int dflt)
 }
 
 enum { PG_ROWS = 0, PG_PATCH = 2 };      // 1x1 | any other k x k (generic patch kernel; 3x3 has its own kernels in conv_pgemm_w.hip)
+// (PG_ROWS addresses input pixel (oy*SH, ox*SW) unchecked: every output must lie inside the image, so no pad on either side.
+// The trailing pads are not in ConvArgs; they show in the last output's position.  Such a 1x1 layer is a patch like any other k x k.)
 static int pg_kind(const ConvArgs& a)
 {
-    return (a.KH == 1 && a.KW == 1 && a.PH == 0 && a.PW == 0) ? PG_ROWS : PG_PATCH;
+    return (a.KH == 1 && a.KW == 1 && a.PH == 0 && a.PW == 0 && (a.OH - 1) * a.SH < a.H && (a.OW - 1) * a.SW < a.W) ? PG_ROWS : PG_PATCH;
 }
 
 // patch pixels the worst pixel tile of `bm` outputs needs (rows it touches, halo included, times the padded row length)

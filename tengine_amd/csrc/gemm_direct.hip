@@ -105,7 +105,7 @@ static int direct_max_m()
 
 bool gemm_direct_applicable(const ConvArgs& a)
 {
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0);
+    const bool is1x1 = conv_is_pointwise(a);
     return is1x1 && a.M <= direct_max_m();
 }
 

@@ -177,21 +177,23 @@ int infer_shapes(tamd_graph* g)
             if (p.dilation_w == 0) p.dilation_w = 1;
             p.input_channel = x.dims[1];
             const HTensor& w = g->tensors[n.in[1]];
-            int h = x.dims[2], wd = x.dims[3], oh, ow;
+            int h = x.dims[2], wd = x.dims[3];
+            // SAME codes (-1 | -2): the reference's infer_shape resolves them into conv_param with a pad_num that holds no dilation and
+            // sizes the axis (in - 1) / stride + 1; at every run its node's reshape (conv_hcl_x86.c:196-240, conv_ref.c:115-160) then finds
+            // pads >= 0 and takes the explicit formula below -- the same size at dilation 1, a smaller map with dilation.  That is the
+            // map the reference computes, so it is the one computed here.
             if (p.pad_h0 < 0) {
-                oh = (h - 1) / p.stride_h + 1;
-                int pad_num = (oh - 1) * p.stride_h + p.kernel_h - h;
+                const int pad_num = (h - 1) / p.stride_h * p.stride_h + p.kernel_h - h;
                 if (p.pad_h0 == -1) { p.pad_h0 = pad_num / 2; p.pad_h1 = pad_num - pad_num / 2; }
                 else { p.pad_h1 = pad_num / 2; p.pad_h0 = pad_num - pad_num / 2; }
-            } else
-                oh = (h - p.dilation_h * (p.kernel_h - 1) - 1 + p.pad_h0 + p.pad_h1) / p.stride_h + 1;
+            }
             if (p.pad_w0 < 0) {
-                ow = (wd - 1) / p.stride_w + 1;
-                int pad_num = (ow - 1) * p.stride_w + p.kernel_w - wd;
+                const int pad_num = (wd - 1) / p.stride_w * p.stride_w + p.kernel_w - wd;
                 if (p.pad_w0 == -1) { p.pad_w0 = pad_num / 2; p.pad_w1 = pad_num - pad_num / 2; }
                 else { p.pad_w1 = pad_num / 2; p.pad_w0 = pad_num - pad_num / 2; }
-            } else
-                ow = (wd - p.dilation_w * (p.kernel_w - 1) - 1 + p.pad_w0 + p.pad_w1) / p.stride_w + 1;
+            }
+            const int oh = (h - p.dilation_h * (p.kernel_h - 1) - 1 + p.pad_h0 + p.pad_h1) / p.stride_h + 1;
+            const int ow = (wd - p.dilation_w * (p.kernel_w - 1) - 1 + p.pad_w0 + p.pad_w1) / p.stride_w + 1;
             y.dims = {x.dims[0], w.dims[0], oh ? oh : 1, ow ? ow : 1};
             break;
         }

@@ -78,6 +78,14 @@ struct ConvArgs {
     EltFuse elt;           // fused eltwise(+relu) tail (conv_igemm / conv_igemm2 only); y/ldc/c_off then describe ITS output
 };
 
+// The pointwise form of the GEMM family: output pixel m reads input pixel m.  ConvArgs carries the leading pads only; a trailing pad
+// (pad_h1 / pad_w1 of a TF-converted 1x1 layer) shows as an output map larger than the input -- its extra row / column holds the
+// requantised bias, which only the tap-addressed form computes.
+inline bool conv_is_pointwise(const ConvArgs& a)
+{
+    return a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0 && a.OH == a.H && a.OW == a.W;
+}
+
 struct DwArgs {
     const int8_t* x;       // NHWC
     const int8_t* w;       // [3 rows][cw] dwords {w[r][0],w[r][1],w[r][2],0}, cw = roundup(C,16)

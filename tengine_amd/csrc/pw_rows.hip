@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void pw_rows_i8_kernel(ConvArgs a)
 
 bool pw_rows_applicable(const ConvArgs& a)
 {
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0);
+    const bool is1x1 = conv_is_pointwise(a);
     const int S = a.kpad / 32;
     if (a.elt.res && ((a.elt.res_ldc | a.elt.res_c_off) & 3)) return false;        // dword reads of the residual operand
     return is1x1 && S <= 4 && a.M >= 2048 && ((a.c_limit | a.c_off | a.ldc) & 3) == 0;

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void pw_stream_i8_kernel(ConvArgs a)
 // (k steps, cout tiles per block) combinations instantiated; weights padded to 128 couts by the planner
 bool pw_stream_applicable(const ConvArgs& a)
 {
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0);
+    const bool is1x1 = conv_is_pointwise(a);
     const int S = a.kpad / 32;
     // 16-B stores need 16-channel granularity of the destination (always true for non-view outputs)
     if (a.elt.res && ((a.elt.res_ldc | a.elt.res_c_off) & 15)) return false;      // 16-B reads of the residual operand

@@ -6,13 +6,16 @@ NHWC device tensor, not the raw graph input), then
 and the variations the fusion must refuse."""
 import numpy as np
 
-from helpers import _scales
+from helpers import _scales, conv_geom, geom_params
 from tengine_amd import tm2
 from tengine_amd.tm2 import DT_INT8, DT_INT32, Graph
 
 
-def _conv(g, rng, name, x, cin, cout, k, out_dims, act, bias, s=1, pad=0, dil=1, bias_range=(-2000, 2000)):
-    """one group-1 convolution node behind tensor x; returns its output tensor.  Output scale as helpers.conv_graph sizes it."""
+def _conv(g, rng, name, x, cin, cout, k, out_dims, act, bias, s=1, pad=0, dil=1, bias_range=(-2000, 2000), geom=None):
+    """one group-1 convolution node behind tensor x; returns its output tensor.  Output scale as helpers.conv_graph sizes it.
+    `geom`: per-axis overrides of the k x k / s / pad / dil geometry (helpers.conv_geom; the kernel stays k x k)"""
+    G = conv_geom(geom, k, s, pad, dil)
+    assert (G["kh"], G["kw"]) == (k, k)
     wq = rng.integers(-127, 128, size=(cout, cin, k, k)).astype(np.int8)
     ws = _scales(rng, cout)
     ins = [x, g.add_const(name + "_w", wq, DT_INT8, ws, [0] * cout)]
@@ -21,17 +24,17 @@ def _conv(g, rng, name, x, cin, cout, k, out_dims, act, bias, s=1, pad=0, dil=1,
     xs = g.tensors[x].scales[0]
     os_ = float(np.float32(xs * np.mean(ws) * 73.0 * np.sqrt(cin * k * k) * 73.0 / 60.0))
     y = g.add_tensor(name, out_dims, DT_INT8, tm2.TT_VAR, None, [os_], [0])
-    g.add_node(name, "Convolution", ins, [y], kernel_h=k, kernel_w=k, stride_h=s, stride_w=s, dilation_h=dil, dilation_w=dil,
-               input_channel=cin, output_channel=cout, group=1, activation=act, pad_h0=pad, pad_w0=pad, pad_h1=pad, pad_w1=pad)
+    g.add_node(name, "Convolution", ins, [y], input_channel=cin, output_channel=cout, group=1, activation=act, **geom_params(G))
     return y
 
 
 def block_graph(seed, n, c, h, w, mid, act_lead=0, act_a=0, act_b=0, bias=True, relu=True, conv_first=False, relu_scale=1.0,
-                stride_a=1, dil_b=1, projection=False, a_twice=False, b_is_output=False, bias_a_range=(-2000, 2000), cin0=16):
+                stride_a=1, dil_b=1, projection=False, a_twice=False, b_is_output=False, bias_a_range=(-2000, 2000), cin0=16, geom_b=None):
     """returns (graph, input).  Tensor names: "x" the block input, "mid1" / "mid2" the two intermediate maps, "sum" the eltwise output,
     "out" the ReLU's.  conv_first: the Eltwise reads (branch2c, x) instead of (x, branch2c); relu_scale != 1: the ReLU re-quantises;
     stride_a 2 (with a stride-2 projection as the residual), dil_b 2, projection, a_twice (mid1 also feeds a ReLU that is a graph
-    output), b_is_output (mid2 is a graph output): the shapes the fusion refuses."""
+    output), b_is_output (mid2 is a graph output): the shapes the fusion refuses.  geom_b: per-axis geometry of the 3x3 (it must
+    keep the map size)."""
     rng = np.random.default_rng(seed)
     g = Graph(name="block_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
@@ -39,7 +42,7 @@ def block_graph(seed, n, c, h, w, mid, act_lead=0, act_a=0, act_b=0, bias=True, 
     x = _conv(g, rng, "x", data, cin0, c, 1, [n, c, h, w], act_lead, bias)
     oh, ow = (h - 1) // stride_a + 1, (w - 1) // stride_a + 1
     m1 = _conv(g, rng, "mid1", x, c, mid, 1, [n, mid, oh, ow], act_a, bias, s=stride_a, bias_range=bias_a_range)
-    m2 = _conv(g, rng, "mid2", m1, mid, mid, 3, [n, mid, oh, ow], act_b, bias, pad=dil_b, dil=dil_b)
+    m2 = _conv(g, rng, "mid2", m1, mid, mid, 3, [n, mid, oh, ow], act_b, bias, pad=dil_b, dil=dil_b, geom=geom_b)
     y = _conv(g, rng, "branch2c", m2, mid, c, 1, [n, c, oh, ow], -1, bias)
     outs = []
     res = x

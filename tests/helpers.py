@@ -11,10 +11,45 @@ def _scales(rng, n, lo=0.002, hi=0.02):
     return [float(np.float32(v)) for v in rng.uniform(lo, hi, size=n)]
 
 
-def conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True, dil=1, kw=None, pw=None):
+GEOM_KEYS = ("kh", "kw", "sh", "sw", "ph0", "ph1", "pw0", "pw1", "dh", "dw")
+
+
+def conv_geom(geom=None, k=1, s=1, p=0, dil=1, kw=None, pw=None):
+    """the ten per-axis quantities of a Convolution node as a dict (GEOM_KEYS): the isotropic arguments, overridden key by key by `geom`.
+    ph0 / pw0 may be the reference's SAME codes (-1: smaller half first, -2: larger half first)."""
+    pw = p if pw is None else pw
+    G = dict(kh=k, kw=k if kw is None else kw, sh=s, sw=s, ph0=p, ph1=p, pw0=pw, pw1=pw, dh=dil, dw=dil)
+    if geom:
+        assert set(geom) <= set(GEOM_KEYS), sorted(set(geom) - set(GEOM_KEYS))
+        G.update(geom)
+    return G
+
+
+def geom_params(G):
+    """the node parameters of a geometry dict"""
+    return dict(kernel_h=G["kh"], kernel_w=G["kw"], stride_h=G["sh"], stride_w=G["sw"], dilation_h=G["dh"], dilation_w=G["dw"],
+                pad_h0=G["ph0"], pad_w0=G["pw0"], pad_h1=G["ph1"], pad_w1=G["pw1"])
+
+
+def geom_out(h, w, G):
+    """(out_h, out_w) by the reference's infer_shape (convolution.c:76-125): all four pads; a SAME code fixes its axis at
+    (in - 1) / stride + 1 -- oracle.conv_out_dims restates it"""
+    from oracle import oracle
+    return tuple(oracle.conv_out_dims([1, 1, h, w], [1], geom_params(G))[2:])
+
+
+def swap_pads(geom):
+    """the same geometry with pad_*0 and pad_*1 exchanged (the output shape is unchanged)"""
+    G = conv_geom(geom)
+    G.update(ph0=G["ph1"], ph1=G["ph0"], pw0=G["pw1"], pw1=G["pw0"])
+    return G
+
+
+def conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True, dil=1, kw=None, pw=None, geom=None):
+    """`geom`: per-axis geometry (conv_geom) in place of k / s / p / dil / kw / pw; the rng draw order does not depend on it"""
     rng = np.random.default_rng(seed)
-    kh, kw = k, (k if kw is None else kw)
-    ph, pw = p, (p if pw is None else pw)
+    G = conv_geom(geom, k, s, p, dil, kw, pw)
+    kh, kw = G["kh"], G["kw"]
     g = Graph(name="conv_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
     x = g.add_input("data", [n, cin, h, w], DT_INT8, [xs], [0])
@@ -24,15 +59,13 @@ def conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True,
     if bias:
         bq = rng.integers(-2000, 2000, size=(cout,)).astype(np.int32)
         ins.append(g.add_const("b", bq, DT_INT32, [1.0], [0]))
-    oh = (h - dil * (kh - 1) - 1 + 2 * ph) // s + 1
-    ow = (w - dil * (kw - 1) - 1 + 2 * pw) // s + 1
+    oh, ow = geom_out(h, w, G)
     # output scale sized so results spread over the int8 range without saturating everywhere
     fan = (cin // group) * kh * kw
     os_ = float(np.float32(xs * np.mean(ws) * 73.0 * np.sqrt(fan) * 73.0 / 60.0))
     y = g.add_tensor("out", [n, cout, oh, ow], DT_INT8, tm2.TT_VAR, None, [os_], [0])
-    ni = g.add_node("conv", "Convolution", ins, [y], kernel_h=kh, kernel_w=kw, stride_h=s, stride_w=s,
-                    dilation_h=dil, dilation_w=dil, input_channel=cin, output_channel=cout, group=group,
-                    activation=act, pad_h0=ph, pad_w0=pw, pad_h1=ph, pad_w1=pw)
+    ni = g.add_node("conv", "Convolution", ins, [y], input_channel=cin, output_channel=cout, group=group, activation=act,
+                    **geom_params(G))
     g.output_nodes = [ni]
     xin = rng.integers(-127, 128, size=(n, cin, h, w)).astype(np.int8)
     return g, xin
@@ -56,21 +89,41 @@ def fc_graph(seed, n, hidden_dims, nout, bias=True):
     return g, rng.integers(-127, 128, size=[n] + list(hidden_dims)).astype(np.int8)
 
 
-def pool_graph(seed, n, c, h, w, alg, k, s, p=0, glob=0, caffe=0, same_scale=False):
+POOL_GEOM_KEYS = ("kh", "kw", "sh", "sw", "ph0", "ph1", "pw0", "pw1")
+
+
+def pool_geom(geom=None, k=1, s=1, p=0):
+    """the per-axis quantities of a Pooling node (POOL_GEOM_KEYS): k / s / p, overridden key by key by `geom`"""
+    G = dict(kh=k, kw=k, sh=s, sw=s, ph0=p, ph1=p, pw0=p, pw1=p)
+    if geom:
+        assert set(geom) <= set(POOL_GEOM_KEYS), sorted(set(geom) - set(POOL_GEOM_KEYS))
+        G.update(geom)
+    return G
+
+
+def pool_geom_params(G):
+    return dict(kernel_h=G["kh"], kernel_w=G["kw"], stride_h=G["sh"], stride_w=G["sw"], pad_h0=G["ph0"], pad_w0=G["pw0"],
+                pad_h1=G["ph1"], pad_w1=G["pw1"])
+
+
+def pool_geom_out(h, w, G, glob, caffe):
+    """(out_h, out_w) by the reference's infer_shape (pooling.c:47-79): each axis from its own kernel, stride and pad_*0"""
     from tengine_amd.models import pool_out
+    if glob:
+        return 1, 1
+    return pool_out(h, G["kh"], G["sh"], G["ph0"], caffe)[0], pool_out(w, G["kw"], G["sw"], G["pw0"], caffe)[0]
+
+
+def pool_graph(seed, n, c, h, w, alg, k, s, p=0, glob=0, caffe=0, same_scale=False, geom=None):
     rng = np.random.default_rng(seed)
+    G = pool_geom(geom, k, s, p)
     g = Graph(name="pool_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
     x = g.add_input("data", [n, c, h, w], DT_INT8, [xs], [0])
-    if glob:
-        oh = ow = 1
-    else:
-        oh, _, _ = pool_out(h, k, s, p, caffe)
-        ow, _, _ = pool_out(w, k, s, p, caffe)
+    oh, ow = pool_geom_out(h, w, G, glob, caffe)
     os_ = xs if same_scale else float(np.float32(xs * rng.uniform(0.4, 1.3)))
     y = g.add_tensor("out", [n, c, oh, ow], DT_INT8, tm2.TT_VAR, None, [os_], [0])
-    ni = g.add_node("pool", "Pooling", [x], [y], alg=alg, kernel_h=k, kernel_w=k, stride_h=s, stride_w=s,
-                    **{"global": glob}, caffe_flavor=caffe, pad_h0=p, pad_w0=p, pad_h1=p, pad_w1=p)
+    ni = g.add_node("pool", "Pooling", [x], [y], alg=alg, **{"global": glob}, caffe_flavor=caffe, **pool_geom_params(G))
     g.output_nodes = [ni]
     return g, rng.integers(-127, 128, size=(n, c, h, w)).astype(np.int8)
 
@@ -124,14 +177,15 @@ def _u8q(rng, lo=0.01, hi=0.05):
 
 
 def u8_conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True, dil=1, in_zp=None, w_zp=None,
-                  out_zp=None):
+                  out_zp=None, geom=None):
     rng = np.random.default_rng(seed)
+    G = conv_geom(geom, k, s, p, dil)
     g = Graph(name="u8conv_case")
     xs, xz = _u8q(rng)
     if in_zp is not None:
         xz = in_zp
     x = g.add_input("data", [n, cin, h, w], DT_UINT8, [xs], [xz])
-    wq = rng.integers(0, 256, size=(cout, cin // group, k, k)).astype(np.uint8)
+    wq = rng.integers(0, 256, size=(cout, cin // group, G["kh"], G["kw"])).astype(np.uint8)
     ws, wz = _u8q(rng, 0.002, 0.02)
     if w_zp is not None:
         wz = w_zp
@@ -139,9 +193,8 @@ def u8_conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=Tr
     if bias:
         bq = rng.integers(-4000, 4000, size=(cout,)).astype(np.int32)
         ins.append(g.add_const("b", bq, DT_INT32, [float(np.float32(xs) * np.float32(ws))], [0]))
-    oh = (h - dil * (k - 1) - 1 + 2 * p) // s + 1
-    ow = (w - dil * (k - 1) - 1 + 2 * p) // s + 1
-    fan = (cin // group) * k * k
+    oh, ow = geom_out(h, w, G)
+    fan = (cin // group) * G["kh"] * G["kw"]
     os_ = float(np.float32(xs * ws * 73.0 * np.sqrt(fan) * 73.0 / 40.0))
     oz = int(rng.integers(0, 256)) if out_zp is None else out_zp
     if act >= 0 and out_zp is None:
@@ -149,9 +202,8 @@ def u8_conv_graph(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=Tr
     if act > 0:
         os_ = min(os_, float(np.float32(6.3 / (255 - oz))))
     y = g.add_tensor("out", [n, cout, oh, ow], DT_UINT8, tm2.TT_VAR, None, [os_], [oz])
-    ni = g.add_node("conv", "Convolution", ins, [y], kernel_h=k, kernel_w=k, stride_h=s, stride_w=s,
-                    dilation_h=dil, dilation_w=dil, input_channel=cin, output_channel=cout, group=group,
-                    activation=act, pad_h0=p, pad_w0=p, pad_h1=p, pad_w1=p)
+    ni = g.add_node("conv", "Convolution", ins, [y], input_channel=cin, output_channel=cout, group=group, activation=act,
+                    **geom_params(G))
     g.output_nodes = [ni]
     return g, rng.integers(0, 256, size=(n, cin, h, w)).astype(np.uint8)
 
@@ -171,16 +223,11 @@ def u8_unary_graph(seed, op, dims, out_dims=None, same_q=False, **params):
     return g, rng.integers(0, 256, size=dims).astype(np.uint8)
 
 
-def u8_pool_graph(seed, n, c, h, w, alg, k, s, p=0, glob=0, caffe=0, same_q=False):
-    from tengine_amd.models import pool_out
-    if glob:
-        oh = ow = 1
-    else:
-        oh, _, _ = pool_out(h, k, s, p, caffe)
-        ow, _, _ = pool_out(w, k, s, p, caffe)
-    return u8_unary_graph(seed, "Pooling", [n, c, h, w], [n, c, oh, ow], same_q, alg=alg, kernel_h=k, kernel_w=k,
-                          stride_h=s, stride_w=s, **{"global": glob}, caffe_flavor=caffe, pad_h0=p, pad_w0=p,
-                          pad_h1=p, pad_w1=p)
+def u8_pool_graph(seed, n, c, h, w, alg, k, s, p=0, glob=0, caffe=0, same_q=False, geom=None):
+    G = pool_geom(geom, k, s, p)
+    oh, ow = pool_geom_out(h, w, G, glob, caffe)
+    return u8_unary_graph(seed, "Pooling", [n, c, h, w], [n, c, oh, ow], same_q, alg=alg, **{"global": glob}, caffe_flavor=caffe,
+                          **pool_geom_params(G))
 
 
 def u8_fc_graph(seed, n, hidden_dims, nout, bias=True):
@@ -291,45 +338,43 @@ def i8_concat_graph(seed, n, c, h, w, axis=1, shrink=False):
     return g, rng.integers(-127, 128, size=(n, c, h, w)).astype(np.int8)
 
 
-def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", pool_alg=1, bias=True, first=None, mid_output=False, sum_tail=False):
+def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", pool_alg=1, bias=True, first=None, mid_output=False, sum_tail=False,
+               first_geom=None, dw_geom=None):
     """int8: pointwise 1x1 conv (cin -> c) -> depthwise 3x3 (stride s, pad p) | global pooling: the pair pwdw.hip fuses.
     `first` = (k, stride, pad[, dilation]): the producer is a k x k conv on the graph input instead (network's first layer);
     `mid_output`: the pointwise output is a graph output as well; `sum_tail`: an eltwise SUM (depthwise output, pointwise output) behind
-    the pair (stride 1, pad 1), so the pointwise output has a second reader that takes it as its SECOND input"""
+    the pair (stride 1, pad 1), so the pointwise output has a second reader that takes it as its SECOND input;
+    `first_geom` / `dw_geom`: per-axis geometry (conv_geom) of the producer / of the depthwise, over `first` / (3, s, p)"""
     rng = np.random.default_rng(seed)
     fk, fs, fp, fd = (list(first) + [1])[:4] if first else (1, 1, 0, 1)
+    F, D = conv_geom(first_geom, fk, fs, fp, fd), conv_geom(dw_geom, 3, s, p)
     g = Graph(name="pwdw_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
     x = g.add_input("data", [n, cin, h, w], DT_INT8, [xs], [0])
-    wq = rng.integers(-127, 128, size=(c, cin, fk, fk)).astype(np.int8)
+    wq = rng.integers(-127, 128, size=(c, cin, F["kh"], F["kw"])).astype(np.int8)
     ws = _scales(rng, c)
     ins = [x, g.add_const("w_pw", wq, DT_INT8, ws, [0] * c)]
     if bias:
         ins.append(g.add_const("b_pw", rng.integers(-2000, 2000, size=(c,)).astype(np.int32), DT_INT32, [1.0], [0]))
-    ms = float(np.float32(xs * np.mean(ws) * 73.0 * np.sqrt(cin * fk * fk) * 73.0 / 60.0))
-    h = (h - fd * (fk - 1) - 1 + 2 * fp) // fs + 1          # from here on: the producer's output map
-    w = (w - fd * (fk - 1) - 1 + 2 * fp) // fs + 1
+    ms = float(np.float32(xs * np.mean(ws) * 73.0 * np.sqrt(cin * F["kh"] * F["kw"]) * 73.0 / 60.0))
+    h, w = geom_out(h, w, F)          # from here on: the producer's output map
     mid = g.add_tensor("mid", [n, c, h, w], DT_INT8, tm2.TT_VAR, None, [ms], [0])
-    pw = g.add_node("pw", "Convolution", ins, [mid], kernel_h=fk, kernel_w=fk, stride_h=fs, stride_w=fs, dilation_h=fd, dilation_w=fd,
-               input_channel=cin, output_channel=c, group=1, activation=act_pw, pad_h0=fp, pad_w0=fp, pad_h1=fp, pad_w1=fp)
+    pw = g.add_node("pw", "Convolution", ins, [mid], input_channel=cin, output_channel=c, group=1, activation=act_pw, **geom_params(F))
     if tail == "pool":
         os_ = float(np.float32(ms * rng.uniform(0.3, 0.9)))
         y = g.add_tensor("out", [n, c, 1, 1], DT_INT8, tm2.TT_VAR, None, [os_], [0])
         ni = g.add_node("pool", "Pooling", [mid], [y], alg=pool_alg, kernel_h=h, kernel_w=w, stride_h=1, stride_w=1,
                         **{"global": 1}, caffe_flavor=0, pad_h0=0, pad_w0=0, pad_h1=0, pad_w1=0)
     else:
-        dq = rng.integers(-127, 128, size=(c, 1, 3, 3)).astype(np.int8)
+        dq = rng.integers(-127, 128, size=(c, 1, D["kh"], D["kw"])).astype(np.int8)
         dsc = _scales(rng, c)
         dins = [mid, g.add_const("w_dw", dq, DT_INT8, dsc, [0] * c)]
         if bias:
             dins.append(g.add_const("b_dw", rng.integers(-2000, 2000, size=(c,)).astype(np.int32), DT_INT32, [1.0], [0]))
-        oh = (h - 3 + 2 * p) // s + 1
-        ow = (w - 3 + 2 * p) // s + 1
+        oh, ow = geom_out(h, w, D)
         os_ = float(np.float32(ms * np.mean(dsc) * 73.0 * 3.0 * 73.0 / 60.0))
         y = g.add_tensor("out", [n, c, oh, ow], DT_INT8, tm2.TT_VAR, None, [os_], [0])
-        ni = g.add_node("dw", "Convolution", dins, [y], kernel_h=3, kernel_w=3, stride_h=s, stride_w=s, dilation_h=1,
-                        dilation_w=1, input_channel=c, output_channel=c, group=c, activation=act_dw, pad_h0=p, pad_w0=p,
-                        pad_h1=p, pad_w1=p)
+        ni = g.add_node("dw", "Convolution", dins, [y], input_channel=c, output_channel=c, group=c, activation=act_dw, **geom_params(D))
     if sum_tail:
         e = g.add_tensor("sum", g.tensors[y].dims, DT_INT8, tm2.TT_VAR, None, [float(np.float32(max(ms, g.tensors[y].scales[0]) * 1.5))], [0])
         ni = g.add_node("sum", "Eltwise", [y, mid], [e], type=tm2.ELT_SUM, caffe_flavor=1)
@@ -338,10 +383,9 @@ def pwdw_graph(seed, n, cin, h, w, c, s=1, p=1, act_pw=0, act_dw=0, tail="dw", p
 
 
 
-def stem_graph(seed, n, h, w, c, kw=7, pad=3, act=0, caffe=1, pool_k=3, pool_s=2, same_scale=True, cin=3, tail_conv=False):
+def stem_graph(seed, n, h, w, c, kw=7, pad=3, act=0, caffe=1, pool_k=3, pool_s=2, same_scale=True, cin=3, tail_conv=False, pool_g=None):
     """int8 ResNet-style stem: 7 x kw / stride-2 conv on the NCHW graph input -> MAX pool (3x3 / 2 / pad 0 by default): the pair
     conv_first_pool.hip runs as one launch.  `tail_conv`: a 1x1 conv behind the pool, so that the pooled map is an inner tensor."""
-    from tengine_amd.models import pool_out
     rng = np.random.default_rng(seed)
     g = Graph(name="stem_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
@@ -355,12 +399,11 @@ def stem_graph(seed, n, h, w, c, kw=7, pad=3, act=0, caffe=1, pool_k=3, pool_s=2
     mid = g.add_tensor("mid", [n, c, ch, cw], DT_INT8, tm2.TT_VAR, None, [ms], [0])
     g.add_node("conv1", "Convolution", ins, [mid], kernel_h=7, kernel_w=kw, stride_h=2, stride_w=2, dilation_h=1, dilation_w=1,
                input_channel=cin, output_channel=c, group=1, activation=act, pad_h0=pad, pad_w0=pad, pad_h1=pad, pad_w1=pad)
-    oh, _, _ = pool_out(ch, pool_k, pool_s, 0, caffe)
-    ow, _, _ = pool_out(cw, pool_k, pool_s, 0, caffe)
+    P = pool_geom(pool_g, pool_k, pool_s, 0)            # `pool_g`: per-axis geometry of the pool over (pool_k, pool_s, pad 0)
+    oh, ow = pool_geom_out(ch, cw, P, 0, caffe)
     ps = ms if same_scale else float(np.float32(ms * rng.uniform(0.5, 1.2)))
     y = g.add_tensor("pooled", [n, c, oh, ow], DT_INT8, tm2.TT_VAR, None, [ps], [0])
-    ni = g.add_node("pool1", "Pooling", [mid], [y], alg=tm2.POOL_MAX, kernel_h=pool_k, kernel_w=pool_k, stride_h=pool_s, stride_w=pool_s,
-                    **{"global": 0}, caffe_flavor=caffe, pad_h0=0, pad_w0=0, pad_h1=0, pad_w1=0)
+    ni = g.add_node("pool1", "Pooling", [mid], [y], alg=tm2.POOL_MAX, **{"global": 0}, caffe_flavor=caffe, **pool_geom_params(P))
     if tail_conv:
         w2 = rng.integers(-127, 128, size=(32, c, 1, 1)).astype(np.int8)
         s2 = _scales(rng, 32)
@@ -373,22 +416,23 @@ def stem_graph(seed, n, h, w, c, kw=7, pad=3, act=0, caffe=1, pool_k=3, pool_s=2
     return g, rng.integers(-127, 128, size=(n, cin, h, w)).astype(np.int8)
 
 
-def dwpw_graph(seed, n, c, h, w, cout, p=1, act_dw=0, act_pw=0, bias=True):
-    """int8: depthwise 3x3 stride 1 (pad p) -> pointwise 1x1 (c -> cout): the pair dwpw.hip runs as one launch"""
+def dwpw_graph(seed, n, c, h, w, cout, p=1, act_dw=0, act_pw=0, bias=True, dw_geom=None):
+    """int8: depthwise 3x3 stride 1 (pad p) -> pointwise 1x1 (c -> cout): the pair dwpw.hip runs as one launch.
+    `dw_geom`: per-axis geometry (conv_geom) of the depthwise over (3, 1, p)"""
     rng = np.random.default_rng(seed)
+    D = conv_geom(dw_geom, 3, 1, p)
     g = Graph(name="dwpw_case")
     xs = float(np.float32(rng.uniform(0.01, 0.05)))
     x = g.add_input("data", [n, c, h, w], DT_INT8, [xs], [0])
-    dq = rng.integers(-127, 128, size=(c, 1, 3, 3)).astype(np.int8)
+    dq = rng.integers(-127, 128, size=(c, 1, D["kh"], D["kw"])).astype(np.int8)
     dsc = _scales(rng, c)
     dins = [x, g.add_const("w_dw", dq, DT_INT8, dsc, [0] * c)]
     if bias:
         dins.append(g.add_const("b_dw", rng.integers(-2000, 2000, size=(c,)).astype(np.int32), DT_INT32, [1.0], [0]))
-    oh, ow = h - 3 + 2 * p + 1, w - 3 + 2 * p + 1
+    oh, ow = geom_out(h, w, D)
     ms = float(np.float32(xs * np.mean(dsc) * 73.0 * 3.0 * 73.0 / 60.0))
     mid = g.add_tensor("mid", [n, c, oh, ow], DT_INT8, tm2.TT_VAR, None, [ms], [0])
-    g.add_node("dw", "Convolution", dins, [mid], kernel_h=3, kernel_w=3, stride_h=1, stride_w=1, dilation_h=1, dilation_w=1,
-               input_channel=c, output_channel=c, group=c, activation=act_dw, pad_h0=p, pad_w0=p, pad_h1=p, pad_w1=p)
+    g.add_node("dw", "Convolution", dins, [mid], input_channel=c, output_channel=c, group=c, activation=act_dw, **geom_params(D))
     wq = rng.integers(-127, 128, size=(cout, c, 1, 1)).astype(np.int8)
     ws = _scales(rng, cout)
     pins = [mid, g.add_const("w_pw", wq, DT_INT8, ws, [0] * cout)]
@@ -526,14 +570,16 @@ def u8_conv_int_model(g, x):
     xv = x.astype(np.int64) - int(xt.zero_points[0])
     n, cin, h, wd = x.shape
     cout, _, kh, kw = w.shape
-    s, dil, pad = p["stride_h"], p["dilation_h"], p["pad_h0"]
+    sh, sw, dh, dw_, ph0, pw0 = p["stride_h"], p["stride_w"], p["dilation_h"], p["dilation_w"], p["pad_h0"], p["pad_w0"]
+    assert ph0 >= 0 and pw0 >= 0
     oh, ow = yt.dims[2], yt.dims[3]
-    xp = np.zeros((n, cin, h + 2 * pad, wd + 2 * pad), np.int64)       # out-of-image taps contribute (zx - zx) = 0
-    xp[:, :, pad:pad + h, pad:pad + wd] = xv
+    # out-of-image taps contribute (zx - zx) = 0; the low pads place the image, the canvas covers every tap of the last output
+    xp = np.zeros((n, cin, max(ph0 + h, (oh - 1) * sh + (kh - 1) * dh + 1), max(pw0 + wd, (ow - 1) * sw + (kw - 1) * dw_ + 1)), np.int64)
+    xp[:, :, ph0:ph0 + h, pw0:pw0 + wd] = xv
     acc = np.zeros((n, cout, oh, ow), np.int64)
     for ky in range(kh):
         for kx in range(kw):
-            patch = xp[:, :, ky * dil:ky * dil + (oh - 1) * s + 1:s, kx * dil:kx * dil + (ow - 1) * s + 1:s]
+            patch = xp[:, :, ky * dh:ky * dh + (oh - 1) * sh + 1:sh, kx * dw_:kx * dw_ + (ow - 1) * sw + 1:sw]
             acc += np.einsum("nchw,oc->nohw", patch, w[:, :, ky, kx])
     if len(node.inputs) > 2:
         acc += np.asarray(g.tensors[node.inputs[2]].data).astype(np.int64).reshape(1, cout, 1, 1)

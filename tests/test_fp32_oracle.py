@@ -10,6 +10,38 @@ TOL = dict(rtol=1e-4, atol=1e-4)
 needs_ref = pytest.mark.skipif(not ref_capi.available(), reason="reference library not built (oracle/build_ref.py)")
 
 
+# anisotropic / asymmetric geometry (tests/geometry_cases.py): the tables the device runs in test_gpu_geometry.py, and the two 3x3 / s1
+# shapes it forces through Winograd (the second is one the reference runs ITS Winograd F(4,3) on: its pads go through that code too)
+from geometry_cases import ALL_CONV, F32_WINO, POOLS, seed_of  # noqa: E402
+from test_gpu_parity_fp32 import conv_graph_f32, pool_graph_f32  # noqa: E402
+
+
+def geometry_f32_conv(name):
+    n, cin, h, w, cout, group, act, geom = (ALL_CONV.get(name) or F32_WINO[name])
+    return conv_graph_f32(seed_of(name), n, cin, h, w, cout, 1, group=group, act=act, geom=geom)
+
+
+@needs_ref
+@pytest.mark.parametrize("name", sorted(ALL_CONV) + sorted(F32_WINO))
+def test_conv_fp32_geometry_oracle_matches_reference(name):
+    g, x = geometry_f32_conv(name)
+    want = ref_capi.run_model(tm2.write_tm2(g), x, ref_capi.MODE_FP32, 2)[0]
+    got = oracle.run_graph(g, x)[0]
+    assert list(want.shape) == list(got.shape)
+    assert np.allclose(want, got, **TOL), np.abs(want - got).max()
+    assert np.abs(want).max() > 1e-3
+
+
+@needs_ref
+@pytest.mark.parametrize("name", sorted(POOLS))
+def test_pool_fp32_geometry_oracle_matches_reference(name):
+    n, c, h, w, alg, caffe, geom = POOLS[name]
+    g, x = pool_graph_f32(seed_of(name), n, c, h, w, alg, caffe, geom)
+    want = ref_capi.run_model(tm2.write_tm2(g), x, ref_capi.MODE_FP32, 2)[0]
+    got = oracle.run_graph(g, x)[0]
+    assert want.shape == got.shape and np.allclose(want, got, **TOL) and np.abs(want).max() > 1e-3
+
+
 @needs_ref
 @pytest.mark.parametrize("name", ["squeezenet_v1.1", "mobilenet_v1"])
 def test_fp32_models_oracle_matches_reference(name):

@@ -17,12 +17,14 @@ pytestmark = pytest.mark.gpu
 NONE, RELU, RELU6 = -1, 0, 6
 
 
-def chain_graph(seed, n, cin, h, w, c1, c2, s2, first=None, pad=1, acts=(RELU, RELU, RELU, RELU), c1_pad=None, mid_output=False):
+def chain_graph(seed, n, cin, h, w, c1, c2, s2, first=None, pad=1, acts=(RELU, RELU, RELU, RELU), c1_pad=None, mid_output=False, geoms=None):
     """producer (first = (k, stride, pad): a k x k conv on the NCHW graph input; None: a pointwise conv) -> dw1 (stride 1) -> pw2 ->
     dw2 (stride s2), biases on all four.  Every node's output scale follows helpers.pwdw_graph's rule, applied per layer:
     out = in * mean(weight scales) * 73 * sqrt(fan_in) * 73 / 60, weight scales uniform in [0.002, 0.02], bias in [-2000, 2000),
     input scale uniform in [0.01, 0.05], input bytes dense in [-127, 127].  `c1_pad`: pad of dw1 where it differs from dw2's;
-    `mid_output`: dw1's output is a graph output as well."""
+    `mid_output`: dw1's output is a graph output as well; `geoms`: {"prod" | "dw1" | "dw2": per-axis geometry (helpers.conv_geom)} over
+    the node's k / stride / pad."""
+    from helpers import conv_geom, geom_out, geom_params
     rng = np.random.default_rng(seed)
     g = Graph(name="chain4_case")
     scale = float(np.float32(rng.uniform(0.01, 0.05)))
@@ -33,14 +35,15 @@ def chain_graph(seed, n, cin, h, w, c1, c2, s2, first=None, pad=1, acts=(RELU, R
     def conv(name, out_name, cout, k, s, p, group, act):
         nonlocal t, scale, cin, h, w
         cg = cin // group
+        G = conv_geom((geoms or {}).get(name), k, s, p)
         ws = [float(np.float32(v)) for v in rng.uniform(0.002, 0.02, size=cout)]
-        ins = [t, g.add_const("w_" + name, rng.integers(-127, 128, size=(cout, cg, k, k)).astype(np.int8), DT_INT8, ws, [0] * cout),
+        ins = [t, g.add_const("w_" + name, rng.integers(-127, 128, size=(cout, cg, G["kh"], G["kw"])).astype(np.int8), DT_INT8, ws, [0] * cout),
                g.add_const("b_" + name, rng.integers(-2000, 2000, size=(cout,)).astype(np.int32), DT_INT32, [1.0], [0])]
-        scale = float(np.float32(scale * np.mean(ws) * 73.0 * np.sqrt(cg * k * k) * 73.0 / 60.0))
-        h, w = (h - k + 2 * p) // s + 1, (w - k + 2 * p) // s + 1
+        scale = float(np.float32(scale * np.mean(ws) * 73.0 * np.sqrt(cg * G["kh"] * G["kw"]) * 73.0 / 60.0))
+        h, w = geom_out(h, w, G)
         t = g.add_tensor(out_name, [n, cout, h, w], DT_INT8, tm2.TT_VAR, None, [scale], [0])
-        nodes.append(g.add_node(name, "Convolution", ins, [t], kernel_h=k, kernel_w=k, stride_h=s, stride_w=s, dilation_h=1, dilation_w=1,
-                                input_channel=cin, output_channel=cout, group=group, activation=act, pad_h0=p, pad_w0=p, pad_h1=p, pad_w1=p))
+        nodes.append(g.add_node(name, "Convolution", ins, [t], input_channel=cin, output_channel=cout, group=group, activation=act,
+                                **geom_params(G)))
         cin = cout
 
     fk, fs, fp = first if first else (1, 1, 0)

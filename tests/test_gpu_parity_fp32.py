@@ -28,22 +28,35 @@ def run_hip(g, x):
     return out
 
 
-def conv_graph_f32(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True, dil=1):
+def conv_graph_f32(seed, n, cin, h, w, cout, k, s=1, p=0, group=1, act=0, bias=True, dil=1, geom=None):
+    """`geom`: per-axis geometry (helpers.conv_geom) in place of k / s / p / dil"""
+    from helpers import conv_geom, geom_out, geom_params
     rng = np.random.default_rng(seed)
+    G = conv_geom(geom, k, s, p, dil)
     g = Graph(name="conv_f32_case")
     x = g.add_input("data", [n, cin, h, w], DT_FP32, None, None)
-    fan = (cin // group) * k * k
-    ins = [x, g.add_const("w", rng.normal(0, np.sqrt(2.0 / fan), size=(cout, cin // group, k, k)).astype(np.float32), DT_FP32, None, None)]
+    fan = (cin // group) * G["kh"] * G["kw"]
+    ins = [x, g.add_const("w", rng.normal(0, np.sqrt(2.0 / fan), size=(cout, cin // group, G["kh"], G["kw"])).astype(np.float32), DT_FP32, None, None)]
     if bias:
         ins.append(g.add_const("b", rng.uniform(-0.1, 0.1, size=(cout,)).astype(np.float32), DT_FP32, None, None))
-    oh = (h - dil * (k - 1) - 1 + 2 * p) // s + 1
-    ow = (w - dil * (k - 1) - 1 + 2 * p) // s + 1
+    oh, ow = geom_out(h, w, G)
     y = g.add_tensor("out", [n, cout, oh, ow], DT_FP32, tm2.TT_VAR, None, None, None)
-    ni = g.add_node("conv", "Convolution", ins, [y], kernel_h=k, kernel_w=k, stride_h=s, stride_w=s, dilation_h=dil,
-                    dilation_w=dil, input_channel=cin, output_channel=cout, group=group, activation=act, pad_h0=p,
-                    pad_w0=p, pad_h1=p, pad_w1=p)
+    ni = g.add_node("conv", "Convolution", ins, [y], input_channel=cin, output_channel=cout, group=group, activation=act, **geom_params(G))
     g.output_nodes = [ni]
     return g, rng.normal(0, 1, size=(n, cin, h, w)).astype(np.float32)
+
+
+def pool_graph_f32(seed, n, c, h, w, alg, caffe, geom):
+    """one fp32 Pooling node of per-axis geometry `geom` (helpers.pool_geom)"""
+    from helpers import pool_geom, pool_geom_out, pool_geom_params
+    rng = np.random.default_rng(seed)
+    G = pool_geom(geom)
+    g = Graph(name="pool_f32_case")
+    x = g.add_input("data", [n, c, h, w], DT_FP32, None, None)
+    oh, ow = pool_geom_out(h, w, G, 0, caffe)
+    y = g.add_tensor("out", [n, c, oh, ow], DT_FP32, tm2.TT_VAR, None, None, None)
+    g.output_nodes = [g.add_node("pool", "Pooling", [x], [y], alg=alg, **{"global": 0}, caffe_flavor=caffe, **pool_geom_params(G))]
+    return g, rng.normal(0, 1, size=(n, c, h, w)).astype(np.float32)
 
 
 F32_CONV = [

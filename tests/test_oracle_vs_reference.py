@@ -170,3 +170,66 @@ def test_mssd_full_tail_oracle_equals_reference(ref):
     assert [tuple(o.shape) for o in got] == [(1, 7668), (1, 40257), (1, 2, 7668, 1)]
     for w, o in zip(want, got):
         assert np.array_equal(np.asarray(w).reshape(o.shape), o)
+
+
+# ---- anisotropic / asymmetric geometry (tests/geometry_cases.py): stride, pads, dilation and kernel differ between the axes, pad_*0 !=
+# pad_*1, SAME pad codes -- every case the device tests of test_gpu_geometry.py run, pinned here to the real reference first
+from geometry_cases import ALL_CONV, FUSED, POOLS, asymmetric, fused_graph, not_degenerate, seed_of  # noqa: E402
+from helpers import swap_pads  # noqa: E402
+
+
+def geometry_conv(name, geom=None):
+    n, cin, h, w, cout, group, act, case_geom = ALL_CONV[name]
+    return conv_graph(seed_of(name), n, cin, h, w, cout, 1, group=group, act=act, geom=geom or case_geom)
+
+
+@pytest.mark.parametrize("name", sorted(ALL_CONV))
+def test_conv_int8_geometry_oracle_equals_reference(ref, name):
+    g, x = geometry_conv(name)
+    want = ref.run_model(tm2.write_tm2(g), x, ref.MODE_INT8, 2)[0]
+    got = oracle.run_graph(g, x)[0]
+    assert list(want.shape) == list(got.shape) == g.tensors[g.nodes[-1].outputs[0]].dims
+    assert np.array_equal(want, got), "mismatches: %d / %d" % (np.count_nonzero(want != got), want.size)
+    assert not_degenerate(got)
+
+
+@pytest.mark.parametrize("name", sorted(POOLS))
+def test_pool_int8_geometry_oracle_equals_reference(ref, name):
+    n, c, h, w, alg, caffe, geom = POOLS[name]
+    g, x = pool_graph(seed_of(name), n, c, h, w, alg, 0, 0, caffe=caffe, geom=geom)
+    want = ref.run_model(tm2.write_tm2(g), x, ref.MODE_INT8, 1)[0]
+    got = oracle.run_graph(g, x)[0]
+    assert want.shape == got.shape and want.shape[2] != want.shape[3]
+    assert np.array_equal(want, got) and not_degenerate(got)
+
+
+FUSED_AT = [(name, n) for name in sorted(FUSED) for n in FUSED[name]]
+
+
+@pytest.mark.parametrize("name,n", FUSED_AT, ids=["%s-b%d" % c for c in FUSED_AT])
+def test_fused_geometry_graphs_oracle_equals_reference(ref, name, n):
+    """the multi-node graphs of the fused-launch cases, both depthwise formulas (batch 1 / batch > 1)"""
+    g, x = fused_graph(name, n)
+    want = ref.run_model(tm2.write_tm2(g), x, ref.MODE_INT8, 2)[0]
+    got = oracle.run_graph(g, x)[0]
+    assert want.shape == got.shape
+    assert np.array_equal(want, got), "mismatches: %d / %d" % (np.count_nonzero(want != got), want.size)
+    assert not_degenerate(got)
+
+
+def test_geometry_cases_discriminate():
+    """a kernel that confused pad_*0 with pad_*1 could not pass: with the two exchanged (same weights, same input, same output
+    shape) the oracle's output differs from the case's expected output"""
+    checked = 0
+    for name in sorted(ALL_CONV):
+        geom = ALL_CONV[name][7]
+        if not asymmetric(geom):
+            continue
+        g, x = geometry_conv(name)
+        g2, x2 = geometry_conv(name, swap_pads(geom))
+        assert np.array_equal(x, x2) and g.tensors[g.nodes[-1].outputs[0]].dims == g2.tensors[g2.nodes[-1].outputs[0]].dims, name
+        want, swapped = oracle.run_graph(g, x)[0], oracle.run_graph(g2, x2)[0]
+        assert want.shape == swapped.shape, name
+        assert np.count_nonzero(want != swapped) > want.size // 50, name
+        checked += 1
+    assert checked >= 12, checked

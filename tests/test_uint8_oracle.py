@@ -46,6 +46,32 @@ def test_conv_uint8_oracle_is_the_reference(case):
     both(*u8_conv_graph(31 + cin + cout, n, cin, h, w, cout, k, s, p, group, act, bias, dil))
 
 
+# anisotropic / asymmetric geometry (tests/geometry_cases.py): the tables the device runs in test_gpu_geometry.py.  The builder's zero
+# points are never 0, so a padded tap (the reference pads with the zero point, i.e. real 0) is visible in the bytes
+from geometry_cases import ALL_CONV, POOLS, not_degenerate, seed_of  # noqa: E402
+
+
+def geometry_u8_conv(name, geom=None):
+    n, cin, h, w, cout, group, act, case_geom = ALL_CONV[name]
+    return u8_conv_graph(seed_of(name), n, cin, h, w, cout, 1, group=group, act=act, geom=geom or case_geom)
+
+
+@needs_ref
+@pytest.mark.parametrize("name", sorted(ALL_CONV))
+def test_conv_uint8_geometry_oracle_is_the_reference(name):
+    g, x = geometry_u8_conv(name)
+    assert g.tensors[g.nodes[-1].inputs[0]].zero_points[0] != 0 and g.tensors[g.nodes[-1].inputs[1]].zero_points[0] != 0
+    both(g, x)
+    assert not_degenerate(oracle.run_graph(g, x)[0])
+
+
+@needs_ref
+@pytest.mark.parametrize("name", sorted(POOLS))
+def test_pool_uint8_geometry_oracle_is_the_reference(name):
+    n, c, h, w, alg, caffe, geom = POOLS[name]
+    both(*u8_pool_graph(seed_of(name), n, c, h, w, alg, 0, 0, caffe=caffe, geom=geom))
+
+
 @needs_ref
 @pytest.mark.parametrize("zps", [(0, 0, 0), (255, 255, 255), (0, 255, 128), (255, 0, 7)])
 def test_conv_uint8_extreme_zero_points(zps):

@@ -85,24 +85,22 @@ RELU_POOL_SCALES = {
 }
 
 
-def relu_pool_graph(seed, dims, k, s, p, caffe, slope, s_in, s_relu, s_pool, alg=0, glob=0, second_consumer=False):
-    """data -> ReLU(slope) -> Pooling; `second_consumer`: the ReLU's output is a graph output as well"""
-    from tengine_amd.models import pool_out
+def relu_pool_graph(seed, dims, k, s, p, caffe, slope, s_in, s_relu, s_pool, alg=0, glob=0, second_consumer=False, geom=None):
+    """data -> ReLU(slope) -> Pooling; `second_consumer`: the ReLU's output is a graph output as well; `geom`: per-axis geometry of the
+    pool (helpers.pool_geom) over k / s / p"""
+    from helpers import pool_geom, pool_geom_out, pool_geom_params
     rng = np.random.default_rng(seed)
+    G = pool_geom(geom, k, s, p)
     n, c, h, w = dims
     g = Graph(name="i8_relu_pool_case")
     x = g.add_input("data", list(dims), DT_INT8, [float(np.float32(s_in))], [0])
     r = g.add_tensor("act", list(dims), DT_INT8, tm2.TT_VAR, None, [float(np.float32(s_relu))], [0])
     ri = g.add_node("act", "ReLU", [x], [r], negative_slope=float(slope))
     if glob:
-        oh = ow = 1
-        k_h, k_w = h, w
-    else:
-        oh, ow = pool_out(h, k, s, p, caffe)[0], pool_out(w, k, s, p, caffe)[0]
-        k_h = k_w = k
+        G.update(kh=h, kw=w)
+    oh, ow = pool_geom_out(h, w, G, glob, caffe)
     y = g.add_tensor("pooled", [n, c, oh, ow], DT_INT8, tm2.TT_VAR, None, [float(np.float32(s_pool))], [0])
-    pi = g.add_node("pool", "Pooling", [r], [y], alg=alg, kernel_h=k_h, kernel_w=k_w, stride_h=s, stride_w=s, **{"global": glob},
-                    caffe_flavor=caffe, pad_h0=p, pad_w0=p, pad_h1=p, pad_w1=p)
+    pi = g.add_node("pool", "Pooling", [r], [y], alg=alg, **{"global": glob}, caffe_flavor=caffe, **pool_geom_params(G))
     g.output_nodes = [pi, ri] if second_consumer else [pi]
     xin = rng.integers(-128, 128, size=dims).astype(np.int8)
     xin.flat[:min(256, xin.size)] = rng.permutation(np.arange(-128, 128))[:min(256, xin.size)]
