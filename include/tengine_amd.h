@@ -67,6 +67,13 @@ enum {
                            * Permute / Flatten / Reshape / PriorBox / flat Concat produces is dense on the device)                  */
     TAMD_OP_PRIORBOX = 15,/* param: tamd_priorbox_param; uint8 / fp32 and (round 6) int8 graphs, batch 1.  Depends on shapes only:
                            * evaluated ONCE at prerun (priorbox_ref.c:53-213 re-computes the same numbers at every run), no launch   */
+    /* the byte-to-byte activations of quantised graphs: each is, in the reference, a function of ONE input byte and the two tensors'
+     * quantisation parameters, so the device maps bytes through a 256-entry table built at prerun (tamd_lut_table, csrc/lut_tables.cc)
+     * with one kernel, lut_u8.  int8 / uint8 graphs only; fp32 graphs keep these four on the CPU device */
+    TAMD_OP_SIGMOID = 16,  /* int8 / uint8 (sigmoid_ref.c:84-170)                                                                  */
+    TAMD_OP_CLIP = 17,     /* param: tamd_clip_param; int8 / uint8 (clip_kernel_ref_int8.c / _uint8.c:41-80); ReLU6 of an ONNX export */
+    TAMD_OP_HARDSWISH = 18,/* param: tamd_hardswish_param; uint8 only (hardswish_kernel_ref_uint8.c:41-83; no int8 kernel in the reference) */
+    TAMD_OP_MISH = 19,     /* uint8 only, a 4-D tensor (mish_kernel_ref_uint8.c:41-95 reads dims[0..3]; no int8 kernel in the reference)  */
     TAMD_OP_NUM
 };
 
@@ -98,6 +105,9 @@ typedef struct tamd_softmax_param { int axis; } tamd_softmax_param;          /* 
 /* the RESOLVED output shape of a Reshape node (what reshape.c:37-160 infers from re_shape / is_mxnet / is_onnx); the batch
  * dimension follows tamd_graph_set_batch */
 typedef struct tamd_reshape_param { int dim_num; int dims[8]; } tamd_reshape_param;
+typedef struct tamd_clip_param { float max, min; } tamd_clip_param;           /* clip_param.h */
+/* hardswish_param.h; carried, not used: the reference's uint8 kernel computes x * clamp(x + 3, 0, 6) / 6 whatever they hold */
+typedef struct tamd_hardswish_param { float alpha, beta; } tamd_hardswish_param;
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */
@@ -161,7 +171,7 @@ typedef struct tamd_options {
                            * MobileNet-SSD's outputs differ from the reference's by up to 4-5 steps in 33-36 % of the bytes
                            * (profiles/r04_u8int_pytest.txt).  0 (default): the byte-exact fp32 chains.  TAMD_U8_INT=0|1 overrides. */
     int split_batch;      /* A batched graph whose operators treat the images of a batch independently (Convolution, FullyConnected,
-                           * Pooling, ReLU, Eltwise, Dropout, Concat / Softmax on an axis >= 1) and whose activation tensors all carry
+                           * Pooling, ReLU, Eltwise, Dropout, Sigmoid, Clip, HardSwish, Mish, Concat / Softmax on an axis >= 1) and whose activation tensors all carry
                            * the same even batch B as dimension 0 can be compiled as TWO device graphs of B / 2 images each, run side by
                            * side on their own HSA queues behind this one tamd_graph: launch boundaries and tile tails of one half
                            * overlap the other half's work (ResNet-50 b32 +8 %, MobileNet-v1 b64 +6 %, outputs identical:
@@ -191,6 +201,12 @@ TAMD_API int tamd_op_supported(int op, int dtype);
  * subgraph (source/device/cuda/cuda_executor.cc:72-134 fails Build() instead; tensorrt: trt_limit.hpp) */
 TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_desc* inputs, int input_num,
                                  const tamd_tensor_desc* outputs, int output_num);
+/* the byte map the device applies for a Sigmoid / Clip / HardSwish / Mish node between tensors of these quantisation parameters:
+ * table[b] = the output byte for input byte b (int8: b is the byte's bit pattern).  param: the operator's struct above (NULL where it
+ * has none).  Built on the host with the reference's own float / double arithmetic; needs no GPU.  0, or -1 for an (op, dtype) pair
+ * the device does not run */
+TAMD_API int tamd_lut_table(int op, int dtype, const void* param, float in_scale, int in_zp, float out_scale, int out_zp,
+                            unsigned char table[256]);
 
 /* ---- graph construction: the plugin's pre_run walks `struct subgraph` (source/graph/subgraph.h, node.h:46-70,
  * tensor.h:43-102) and mirrors it through these calls, like CUDAEngine::Build does for its own IR

@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -84,8 +84,22 @@ def lib():
         }.items():
             getattr(L, name).argtypes = args
         L.tamd_graph_destroy.restype = None
+        L.tamd_lut_table.argtypes = [ci, ci, vp, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         _lib = L
     return _lib
+
+
+OP_SIGMOID, OP_CLIP, OP_HARDSWISH, OP_MISH = 16, 17, 18, 19      # TAMD_OP_* of the byte-map operators
+
+
+def lut_table(op, dtype, in_scale, in_zp, out_scale, out_zp, params=None):
+    """tamd_lut_table(): the 256 output bytes (uint8 array, indexed by the input byte's bit pattern) the device applies for a Sigmoid /
+    Clip / HardSwish / Mish node between tensors of these quantisation parameters; None for a pair the device does not run.  `params`:
+    the node's two floats (Clip: max, min; HardSwish: alpha, beta).  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    p = (C.c_float * 2)(*params) if params is not None else None
+    rc = lib().tamd_lut_table(op, dtype, C.cast(p, C.c_void_p) if p is not None else None, in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 
 
 def _check(rc, what):

@@ -47,6 +47,8 @@ union NodeParam {
     tamd_softmax_param softmax;
     tamd_reshape_param reshape;
     tamd_priorbox_param priorbox;
+    tamd_clip_param clip;
+    tamd_hardswish_param hardswish;
 };
 
 struct HNode {
@@ -240,6 +242,8 @@ int count_consumers(const tamd_graph* g, int tensor);
 // inputs and tensors, views for Dropout / Flatten / Reshape and for channel-concat inputs that `in_place` allows; graph outputs
 int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place);
 int plan_nchw_outputs(tamd_graph* g, size_t esz);
+// a Sigmoid / Clip / HardSwish / Mish node of an int8 or uint8 graph as ONE launch (graph_plan.hip): table upload + lut_u8
+int plan_lut(tamd_graph* g, HNode& n, Step* out);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
 inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
 // .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of

@@ -78,6 +78,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_SOFTMAX) return 1;                           // (which axes: tamd_node_supported)
     if (op == TAMD_OP_RESHAPE || op == TAMD_OP_PRIORBOX) return 1; // dense device tensors: uint8 / fp32 graphs; int8 since round 6 (graph_plan.hip)
     if (op == TAMD_OP_PERMUTE) return dtype != TAMD_DT_FP32;       // SSD heads (Permute -> Flatten -> Concat): uint8, and int8 since round 6
+    if (is_lut_op(op)) return lut_op_on_device(op, dtype);         // byte maps by table: the quantised forms the reference has (which ranks: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
     case TAMD_OP_ELTWISE: case TAMD_OP_CONCAT: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
@@ -175,6 +176,12 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         const int m = ((const tamd_pool_param*)n->param)->pool_method;
         return m == 0 || m == 1;
     }
+    case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: {
+        if (n_in != 1 || in[0].ttype == TAMD_TT_CONST || in[0].dim_num < 1 || in[0].dim_num != out[0].dim_num) return 0;
+        for (int i = 0; i < in[0].dim_num; i++) if (in[0].dims[i] != out[0].dims[i]) return 0;
+        if (n->op == TAMD_OP_CLIP && !n->param) return 0;
+        return lut_rank_on_device(n->op, in[0].dim_num);
+    }
     default:
         return 1;
     }
@@ -231,6 +238,8 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_SOFTMAX: n.p.softmax = *(const tamd_softmax_param*)d->param; break;
         case TAMD_OP_RESHAPE: n.p.reshape = *(const tamd_reshape_param*)d->param; break;
         case TAMD_OP_PRIORBOX: n.p.priorbox = *(const tamd_priorbox_param*)d->param; break;
+        case TAMD_OP_CLIP: n.p.clip = *(const tamd_clip_param*)d->param; break;
+        case TAMD_OP_HARDSWISH: n.p.hardswish = *(const tamd_hardswish_param*)d->param; break;
         default: break;
         }
     }

@@ -209,6 +209,7 @@ int infer_shapes(tamd_graph* g)
             break;
         }
         case TAMD_OP_RELU: case TAMD_OP_RELU6: case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT: case TAMD_OP_SOFTMAX:
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
             y.dims = x.dims;
             break;
         case TAMD_OP_CONCAT: {
@@ -280,6 +281,12 @@ int validate_graph(tamd_graph* g)
         if (n.op == TAMD_OP_PRIORBOX && g->tensors[n.out[0]].dims[0] != 1) return bad(n, "PriorBox is defined for batch 1 only");
         // the uint8 / fp32 planners and infer_shapes take the factor as an int: 1.5 would run as 1, 0.5 would give an empty tensor
         if (n.op == TAMD_OP_UPSAMPLE && !upsample_factor_on_device(n.p.ups.scale)) return bad(n, "Upsample takes an integer factor >= 1");
+        if (is_lut_op(n.op)) {
+            const HTensor& x = g->tensors[n.in[0]];
+            if (!lut_op_on_device(n.op, x.dtype)) return bad(n, "Sigmoid / Clip run on the device in int8 and uint8 graphs, HardSwish / Mish in uint8 graphs only");
+            if (!lut_rank_on_device(n.op, (int)x.dims.size())) return bad(n, "Mish is defined for a 4-D tensor only");
+            if (x.scales.empty() || g->tensors[n.out[0]].scales.empty()) return bad(n, "missing quant params");
+        }
         if (n.op != TAMD_OP_CONV && n.op != TAMD_OP_FC) continue;
         const HTensor& x = g->tensors[n.in[0]];
         HTensor& w = g->tensors[n.in[1]];

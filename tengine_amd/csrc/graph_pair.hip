@@ -41,7 +41,7 @@ static bool ops_allow_split(const tamd_graph* g)
     for (auto& n : g->nodes)
         switch (n.op) {
         case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
-        case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT:
+        case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT: case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
             break;
         case TAMD_OP_CONCAT: if (n.p.concat.axis < 1) return false; break;
         case TAMD_OP_SOFTMAX: if (n.p.softmax.axis < 1) return false; break;

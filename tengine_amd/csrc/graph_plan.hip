@@ -211,6 +211,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
             }
             break;
         case TAMD_OP_SOFTMAX: if (L.dense[n.in[0]]) L.dense[yo] = 1; break;
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: if (L.dense[n.in[0]]) L.dense[yo] = 1; break;       // a byte map keeps the element order it finds
         case TAMD_OP_CONCAT: {
             HTensor& y = g->tensors[yo];
             const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
@@ -839,6 +840,44 @@ static int plan_relu(tamd_graph* g, I8Layout& L, size_t ni)
     return 0;
 }
 
+// Sigmoid / Clip / HardSwish / Mish, int8 and uint8 graphs alike (graph_u8.hip calls this too): the node's 256-entry byte map is built
+// on the host with the reference's arithmetic (lut_tables.cc), uploaded once here, and applied by one lut_u8 launch (misc_kernels.hip).
+// An NHWC int8 tensor with padding lanes (cs > c) is mapped channel by channel and its padding is written as zero; everything else --
+// uint8 tensors, dense int8 tensors, NHWC tensors without padding -- is a run of bytes.  A concat view is refused by name, as plan_relu
+// does: neither planner makes one of these nodes' tensors a view (plan_concat_views: slice_capable; plan_u8: in_place), so the error
+// guards a change to those lists.
+int plan_lut(tamd_graph* g, HNode& n, Step* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const char* what = n.op == TAMD_OP_SIGMOID ? "sigmoid" : n.op == TAMD_OP_CLIP ? "clip" : n.op == TAMD_OP_HARDSWISH ? "hardswish" : "mish";
+    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
+    if (x.scales.empty() || y.scales.empty()) { set_error("%s %s: missing quant params", what, n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("%s %s: output shape / type mismatch", what, n.name.c_str()); return -1; }
+    if (!lut_rank_on_device(n.op, (int)x.dims.size())) { set_error("%s %s: only a 4-D tensor runs on the device", what, n.name.c_str()); return -1; }
+    const void* param = n.op == TAMD_OP_CLIP ? (const void*)&n.p.clip : n.op == TAMD_OP_HARDSWISH ? (const void*)&n.p.hardswish : nullptr;
+    std::vector<unsigned> table(64);
+    if (tamd_lut_table(n.op, x.dtype, param, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
+        set_error("%s %s: not supported on the device for data type %d", what, n.name.c_str(), x.dtype);
+        return -1;
+    }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    LutArgs a{};
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
+    const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
+    if (x_nhwc != y_nhwc || (x_nhwc && (x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off))) { set_error("%s %s: input and output layouts differ", what, n.name.c_str()); return -1; }
+    if (x_nhwc) {
+        a.count = (size_t)x.n * x.h * x.w * x.cs;
+        if (x.cs != x.c) { a.C = x.c; a.cs = x.cs; }
+    } else {
+        a.count = x.elems();
+    }
+    *out = make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); });
+    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
+    return 0;
+}
+
 // upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
 static int plan_upsample(tamd_graph* g, HNode& n)
 {
@@ -950,6 +989,9 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_RELU: r = plan_relu(g, L, ni); break;
         case TAMD_OP_UPSAMPLE: r = plan_upsample(g, n); break;
         case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n); break;
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
+            if (!(r = plan_lut(g, n, &one.step))) g->steps.push_back(one.step);
+            break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

@@ -885,6 +885,11 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_FC: rc = plan_fc_u8(g, n, &out); break;
         case TAMD_OP_POOL: rc = plan_pool_u8(n, x, y, &out); break;
         case TAMD_OP_RELU: case TAMD_OP_UPSAMPLE: rc = plan_map_u8(n, x, y, &out); break;
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: {     // byte maps by table: the planner both graphs share
+            Step st;
+            if (!(rc = plan_lut(g, n, &st))) out.push_back(st);
+            break;
+        }
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;

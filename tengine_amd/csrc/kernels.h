@@ -283,6 +283,13 @@ struct ReluArgs {
     const int8_t* x; int8_t* y; size_t count; float slope, in_scale, out_scale;
 };
 
+struct LutArgs {           // y[i] = table[x[i]] over `count` bytes, x and y 16-byte aligned (Sigmoid / Clip / HardSwish / Mish, int8 and uint8)
+    const uint8_t* x; uint8_t* y;
+    size_t count;          // cs == 0: the bytes of a dense tensor, any number.  cs > 0: an NHWC int8 buffer, N * H * W * cs bytes
+    int C, cs;             // cs > 0 (a multiple of 16): only channels [0, C) of every pixel are mapped, the padding lanes [C, cs) are written 0
+    const unsigned* table; // [64]: entries 4i .. 4i + 3 in the bytes of dword i, lowest first (tamd_lut_table's 256 bytes as they lie)
+};
+
 struct SoftmaxI8Args {     // softmax over ONE axis of an int8 tensor: the channels of an NHWC tensor (a view's channel slice included), or --
                            // round 6 -- any axis of a dense (reference-order) or NHWC tensor
     const int8_t* x; int8_t* y;
@@ -399,6 +406,7 @@ hipError_t launch_relu_pool(const ReluPoolArgs& a, hipStream_t s);   // (never t
 hipError_t launch_upsample_i8(const UpsampleI8Args& a, hipStream_t s);
 hipError_t launch_eltwise(const EltArgs& a, hipStream_t s);
 hipError_t launch_relu(const ReluArgs& a, hipStream_t s);
+hipError_t launch_lut(const LutArgs& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);
 hipError_t launch_concat_copy_i8(const CatCopyArgs& a, hipStream_t s);
 hipError_t launch_flatcat_i8(const FlatCatI8Args& a, hipStream_t s);

@@ -399,6 +399,70 @@ hipError_t launch_relu(const ReluArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---- byte map through a 256-entry table: Sigmoid / Clip / HardSwish / Mish of int8 and uint8 graphs (lut_tables.cc builds the table) ----
+// 16 bytes per thread like relu_i8.  WHERE THE TABLE LIVES: in registers -- 256 bytes are 64 dwords, exactly one dword per lane of a
+// wave, so every wave stages the table once with ONE coalesced 256-byte load (lane l keeps entries 4l .. 4l + 3) and a lookup is a
+// ds_bpermute_b32 of that register from lane b >> 2 plus a shift by b & 3.  The alternative, a byte table in LDS read with
+// ds_read_u8, costs a barrier per block and banks by dword address ((a / 4) % 32 for the narrow reads): 256 bytes cover each bank
+// twice, so which lanes collide depends on the activation bytes, up to 2-way per 32-lane half for every lookup.  The bpermute crosses
+// lanes through the same LDS data path without touching the LDS array: no allocation, no barrier, no bank, the same cost for every
+// input.  It needs every lane of the wave active (a disabled lane supplies 0), so no thread leaves early: a thread past the end
+// loads nothing, looks up zeros and stores nothing.
+// Two forms of tensor.  cs > 0: an int8 NHWC buffer whose pixels are cs bytes, C of them channels -- cs is a multiple of 16, so a
+// thread's 16 bytes lie inside one pixel; the padding lanes [C, cs) are WRITTEN AS ZERO whatever table[0] is (Sigmoid: 0 maps to one
+// half), the invariant the next convolution's K loop relies on (graph_plan.hip: plan_buffers).  cs == 0: dense bytes, any count; the
+// last thread moves the count % 16 bytes behind the last whole vector one by one and touches nothing past them.
+__global__ __launch_bounds__(256) void lut_u8_kernel(LutArgs a)
+{
+    const unsigned tab = a.table[threadIdx.x & 63];
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    int valid = 0;                                    // bytes of this thread's 16 that are mapped
+    if (i < a.count) {
+        if (a.cs > 0) { const int left = a.C - (int)(i % (size_t)a.cs); valid = left < 0 ? 0 : (left > 16 ? 16 : left); }
+        else valid = a.count - i >= 16 ? 16 : (int)(a.count - i);
+    }
+    const bool inside = i < a.count, whole = inside && (a.cs > 0 || valid == 16);   // whole: one 16-byte load, one 16-byte store
+    unsigned pv[4] = {0u, 0u, 0u, 0u};
+    if (whole) {
+        const uint4 v = *reinterpret_cast<const uint4*>(a.x + i);
+        pv[0] = v.x; pv[1] = v.y; pv[2] = v.z; pv[3] = v.w;
+    } else if (inside) {
+#pragma unroll
+        for (int j = 0; j < 16; j++)                  // (unrolled: registers indexed by constants, no scratch memory)
+            if (j < valid) pv[j >> 2] |= (unsigned)a.x[i + j] << (8 * (j & 3));
+    }
+    unsigned out[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        unsigned o = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const unsigned q = (pv[d] >> (8 * b)) & 0xffu;
+            const unsigned t = (unsigned)__builtin_amdgcn_ds_bpermute((int)(q & 0xfcu), (int)tab);      // byte address of lane q >> 2
+            const unsigned r = (t >> (8 * (q & 3u))) & 0xffu;
+            o |= (d * 4 + b < valid ? r : 0u) << (8 * b);
+        }
+        out[d] = o;
+    }
+    if (whole) {
+        *reinterpret_cast<uint4*>(a.y + i) = make_uint4(out[0], out[1], out[2], out[3]);
+    } else if (inside) {
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            if (j < valid) a.y[i + j] = (uint8_t)(out[j >> 2] >> (8 * (j & 3)));
+    }
+}
+
+hipError_t launch_lut(const LutArgs& a, hipStream_t s)
+{
+    if (a.cs < 0 || a.cs % 16 || (a.cs > 0 && (a.C < 1 || a.C > a.cs || a.count % (size_t)a.cs))) return hipErrorInvalidValue;
+    if (((uintptr_t)a.x | (uintptr_t)a.y) & 15) return hipErrorInvalidValue;
+    const size_t n16 = (a.count + 15) / 16;
+    if (n16 == 0) return hipSuccess;
+    hipLaunchKernelGGL(lut_u8_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---- softmax over the channel axis: softmax/softmax_kernel_ref_int8.c:41-117 over softmax_kernel_ref.h:35-85 ------------------
 // f = (float)q * in_scale; per position: max over the axis; o = (float)exp((double)(f - max)) -- the reference calls C `exp` on a
 // float argument, i.e. the DOUBLE routine, and rounds to float on the store (:67); the sum is accumulated in fp32 IN AXIS ORDER

@@ -3,6 +3,7 @@
 // planner alone decides stays in that planner.
 #pragma once
 #include "kernels.h"
+#include "lut_tables.h"
 
 namespace tamd {
 
@@ -27,5 +28,12 @@ inline bool softmax_i8_axis_fits(int len) { return len >= 1 && len <= kSoftmaxI8
 // Upsample: nearest neighbour by a whole factor >= 1 (upsample_ref.c indexes with 1 / scale; the device kernels take an int, and
 // shape inference multiplies by it)
 inline bool upsample_factor_on_device(float scale) { return scale >= 1.f && scale == (float)(int)scale; }
+
+// Sigmoid / Clip / HardSwish / Mish: byte maps through a 256-entry table (lut_tables.cc builds it, misc_kernels.hip: lut_u8 applies it).
+// Which (operator, type) pairs run there is lut_op_on_device (lut_tables.h: the list of table builders itself)
+inline bool is_lut_op(int op) { return op == TAMD_OP_SIGMOID || op == TAMD_OP_CLIP || op == TAMD_OP_HARDSWISH || op == TAMD_OP_MISH; }
+// Mish: mish_kernel_ref_uint8.c:43-51 sizes its loops from dims[0..3] -- on a tensor of another rank the reference reads dimensions that
+// are not there, and there are no bytes to equal; the other three kernels run over elem_num
+inline bool lut_rank_on_device(int op, int dim_num) { return op != TAMD_OP_MISH || dim_num == 4; }
 
 }  // namespace tamd

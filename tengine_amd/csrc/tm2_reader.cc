@@ -75,7 +75,11 @@ int map_op(uint32_t t)
     case 21: return TAMD_OP_RELU6;
     case 23: return TAMD_OP_RESHAPE;
     case 28: return TAMD_OP_SOFTMAX;
+    case 37: return TAMD_OP_SIGMOID;
     case 51: return TAMD_OP_UPSAMPLE;
+    case 70: return TAMD_OP_HARDSWISH;
+    case 87: return TAMD_OP_CLIP;
+    case 97: return TAMD_OP_MISH;
     default: return -1;
     }
 }
@@ -178,6 +182,8 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
             case TAMD_OP_CONCAT: p.concat.axis = r.i32(po); break;
             case TAMD_OP_SOFTMAX: p.softmax.axis = r.i32(po); break;   // TM2_SoftmaxParam {axis}
             case TAMD_OP_UPSAMPLE: p.ups.scale = r.f32(po); break;
+            case TAMD_OP_CLIP: p.clip.max = r.f32(po); p.clip.min = r.f32(po + 4); break;                 // TM2_ClipParam {max, min}
+            case TAMD_OP_HARDSWISH: p.hardswish.alpha = r.f32(po); p.hardswish.beta = r.f32(po + 4); break;   // TM2_HardSwishParam {alpha, beta}
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)
                 tamd_priorbox_param& q = p.priorbox;
                 auto floats = [&](uint32_t vo_, float* dst, int cap, int* num) {      // TM2_Vector_floats {v_num, data[]}

@@ -42,11 +42,13 @@ extern "C" {
 #include "utility/sys_port.h"
 #include "utility/vector.h"
 // operator parameter structs (source/operator/prototype/)
+#include "clip_param.h"
 #include "concat_param.h"
 #include "convolution_param.h"
 #include "eltwise_param.h"
 #include "fc_param.h"
 #include "flatten_param.h"
+#include "hardswish_param.h"
 #include "permute_param.h"
 #include "pooling_param.h"
 #include "priorbox_param.h"
@@ -79,6 +81,9 @@ const OpRow kOps[] = {
     {OP_UPSAMPLE, TAMD_OP_UPSAMPLE, false}, {OP_SOFTMAX, TAMD_OP_SOFTMAX, false}, {OP_RELU6, TAMD_OP_RELU6, false},
     {OP_PERMUTE, TAMD_OP_PERMUTE, true},    {OP_FLATTEN, TAMD_OP_FLATTEN, true},  {OP_RESHAPE, TAMD_OP_RESHAPE, true},
     {OP_PRIORBOX, TAMD_OP_PRIORBOX, true},
+    // byte maps by table (csrc/lut_tables.cc): the quantised kernels of the reference alone; which of int8 / uint8: tamd_op_supported
+    {OP_SIGMOID, TAMD_OP_SIGMOID, true},    {OP_CLIP, TAMD_OP_CLIP, true},        {OP_HARDSWISH, TAMD_OP_HARDSWISH, true},
+    {OP_MISH, TAMD_OP_MISH, true},
 };
 
 const OpRow* find_op(int op)
@@ -140,6 +145,7 @@ tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
+    tamd_clip_param clip; tamd_hardswish_param hardswish;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -179,6 +185,16 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
     }
     case TAMD_OP_CONCAT: s->concat.axis = ((const struct concat_param*)n->op.param_mem)->axis; break;
     case TAMD_OP_UPSAMPLE: s->ups.scale = ((const struct upsample_param*)n->op.param_mem)->scale; break;
+    case TAMD_OP_CLIP: {
+        const struct clip_param* p = (const struct clip_param*)n->op.param_mem;
+        s->clip = {p->max, p->min};
+        break;
+    }
+    case TAMD_OP_HARDSWISH: {
+        const struct hardswish_param* p = (const struct hardswish_param*)n->op.param_mem;
+        s->hardswish = {p->alpha, p->beta};
+        break;
+    }
     case TAMD_OP_PERMUTE: {
         const struct permute_param* p = (const struct permute_param*)n->op.param_mem;
         s->perm = {{p->order0, p->order1, p->order2, p->order3}};

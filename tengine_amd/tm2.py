@@ -29,6 +29,7 @@ OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Softmax": 28, "Upsample": 51,
+    "Sigmoid": 37, "HardSwish": 70, "Clip": 87, "Mish": 97,
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
 
@@ -127,7 +128,11 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<5i", p.get("flag", 0), o[0], o[1], o[2], o[3])
     if op == "DetectionOutput":  # TM2_DetectionOutputParam tm2_format.h:455-463
         return struct.pack("<3i2f", p["num_classes"], p["keep_top_k"], p["nms_top_k"], p["confidence_threshold"], p["nms_threshold"])
-    if op in ("Const", "InputOp", "Dropout", "ReLU6"):
+    if op == "Clip":             # TM2_ClipParam {max, min}
+        return struct.pack("<2f", p["max"], p["min"])
+    if op == "HardSwish":        # TM2_HardSwishParam {alpha, beta}; the loader reads the blob (tm2_hardswish.c:48-51), the uint8 kernel neither value
+        return struct.pack("<2f", p.get("alpha", 1.0), p.get("beta", 3.0))
+    if op in ("Const", "InputOp", "Dropout", "ReLU6", "Sigmoid", "Mish"):
         return None
     raise NotImplementedError("tm2 writer: op %s" % op)
 
@@ -154,6 +159,10 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         return dict(zip(["axis", "end_axis"], struct.unpack_from("<2i", b, off)))
     if op == "Upsample":
         return {"scale": struct.unpack_from("<f", b, off)[0]}
+    if op == "Clip":
+        return dict(zip(["max", "min"], struct.unpack_from("<2f", b, off)))
+    if op == "HardSwish":
+        return dict(zip(["alpha", "beta"], struct.unpack_from("<2f", b, off)))
     if op == "Permute":
         v = struct.unpack_from("<5i", b, off)
         return {"flag": v[0], "order": list(v[1:])}
