@@ -221,6 +221,8 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     if (tmode == 1 && pinned_tile("pwdw_cfg", a.OH, a.OW, &pth, &ptw, &pthreads, &psl)) {
         if ((psl != 2 && psl != 4) || slices % psl != 0 || nsteps > steps) psl = 1;
         if (pwdw_config_ok(with_tiles(a, pth, ptw, psl), pthreads)) { cfgs.clear(); cfgs.push_back({pth, ptw, pthreads, 0.0, psl}); }
+    } else if (tmode == 0 && pinned_tile("pwdw_cfg", a.OH, a.OW, &pth, &ptw, &pthreads, &psl) && pwdw_config_ok(a, pthreads)) {
+        cfgs.clear(); cfgs.push_back({1, 1, pthreads, 0.0, 1});      // a pooling tail has no tile: the pin picks the block width (tests)
     }
     if (cfgs.empty()) return 0;
     const Step& sa = pa.step;

@@ -388,12 +388,82 @@ static bool pwdw_windows(const PwDwArgs& a, int mode)
 static_assert(sizeof(PwDwArgs) == 304, "PwDwArgs must not grow: see the note at PwDwArgs::sl (kernels.h)");
 #endif
 
+// The whole argument segment in ONE trip.  Left to itself the compiler fetches the fields of a by-value PwDwArgs in three dependent
+// groups of s_load, a wait behind each (it loads over-wide tuples and reuses a dead lane of one as the destination of a later load;
+// scalar loads return out of order, so it must wait), and the second group misses in three 64-byte lines the first did not touch --
+// all of it before the first vector load of a launch whose whole life is 3-5 us.  Here every 64-byte line of the segment the block
+// reads is requested back to back, with a single wait, and the struct is rebuilt from those registers; the hidden group size
+// (blockDim.x) lies in the last of these lines, so its own s_load hits.  Pointer fields come back as GLOBAL pointers: rebuilt from
+// integers they would be generic and every weight / bias / multiplier load a flat_load.
+// TAIL false (MODE 0 / 4, no depthwise behind the conv, never a first-layer producer): the block reads nothing between `taps` and `y`,
+// so the third and fourth line stay where they are -- 48 scalar registers instead of 80, which keeps these small instances at their
+// eight waves per SIMD.  The fields not fetched are zero.
+typedef unsigned v16u __attribute__((ext_vector_type(16)));
+template <typename T> __device__ __forceinline__ T* as_global(T* p) { return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p; }
+__device__ __forceinline__ unsigned long long line_word(const v16u& l, int i) { return (unsigned long long)l[2 * i] | (unsigned long long)l[2 * i + 1] << 32; }
+
+template <bool TAIL>
+__device__ __forceinline__ PwDwArgs pwdw_fetch_args()
+{
+    constexpr int kLines = (sizeof(PwDwArgs) + 63) / 64;
+    static_assert(kLines == 5, "pwdw_fetch_args requests five lines");
+    const auto seg = __builtin_amdgcn_kernarg_segment_ptr();
+    // (rebuilt through 64-bit words, not the vectors: a pointer field written back into one wide vector loses its address space again)
+    unsigned long long w[kLines * 8];
+    PwDwArgs a = {};
+    if constexpr (TAIL) {
+        v16u l0, l1, l2, l3, l4;
+        asm volatile("s_load_dwordx16 %0, %5, 0x0\n\t"
+                     "s_load_dwordx16 %1, %5, 0x40\n\t"
+                     "s_load_dwordx16 %2, %5, 0x80\n\t"
+                     "s_load_dwordx16 %3, %5, 0xc0\n\t"
+                     "s_load_dwordx16 %4, %5, 0x100\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&s"(l0), "=&s"(l1), "=&s"(l2), "=&s"(l3), "=&s"(l4) : "s"(seg));
+        const v16u lines[kLines] = {l0, l1, l2, l3, l4};
+#pragma unroll
+        for (int i = 0; i < kLines * 8; i++) w[i] = line_word(lines[i >> 3], i & 7);
+        __builtin_memcpy(&a, w, sizeof(PwDwArgs));
+        a.taps = as_global(a.taps); a.dw_w = as_global(a.dw_w); a.dw_bias = as_global(a.dw_bias); a.dw_wscale = as_global(a.dw_wscale);
+    } else {
+        // [0, 128) holds everything up to `taps`; the 64 bytes from `y` on hold the rest and end in the line of the group size
+        constexpr size_t kHead = 128, kBack = offsetof(PwDwArgs, y);
+        static_assert(offsetof(PwDwArgs, taps) <= kHead && kBack >= kHead && kBack % 8 == 0 && sizeof(PwDwArgs) - kBack <= 64, "PwDwArgs: the tail-less fetch");
+        v16u l0, l1, lb;
+        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\t"
+                     "s_load_dwordx16 %1, %3, 0x40\n\t"
+                     "s_load_dwordx16 %2, %3, %4\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&s"(l0), "=&s"(l1), "=&s"(lb) : "s"(seg), "i"((int)kBack));
+        const v16u lines[3] = {l0, l1, lb};
+#pragma unroll
+        for (int i = 0; i < 24; i++) w[i] = line_word(lines[i >> 3], i & 7);
+        __builtin_memcpy(&a, w, kHead);
+        __builtin_memcpy(reinterpret_cast<char*>(&a) + kBack, w + 16, sizeof(PwDwArgs) - kBack);
+        a.taps = nullptr;
+    }
+    a.x = as_global(a.x); a.wf = as_global(a.wf); a.bias = as_global(a.bias); a.wscale = as_global(a.wscale); a.y = as_global(a.y);
+#ifdef TAMD_PWDW_STAMPS
+    a.stamps = as_global(a.stamps);
+#endif
+    return a;
+}
+
+// Several slices of 16 register-resident steps sit at the 256-VGPR ceiling and spill already: the scalars this fetch keeps alive
+// would cost them one more spilled vector register, so they keep the compiler's own argument loads (batch > 1 only, deep in a
+// long-running grid, where the entry does not show).
+template <int STEPS, int SL> constexpr bool kPwdwFetch = !(SL > 1 && STEPS >= 16);
+
 template <int STEPS, int MODE, bool CHUNKED, int PROD, int WIN, int SL>
-__global__ __launch_bounds__(512) void pwdw_i8_kernel(PwDwArgs a)
+__global__ __launch_bounds__(512) void pwdw_i8_kernel(PwDwArgs arg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned inter[];       // [slice][region pixel][4 dwords = 16 channels]
     const ChainDep none = {nullptr, 0, nullptr, nullptr};
-    pwdw_block<STEPS, MODE, CHUNKED, PROD, false, WIN, SL>(a, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
+    if constexpr (kPwdwFetch<STEPS, SL>) {
+        const PwDwArgs a = pwdw_fetch_args<MODE != 0 && MODE != 4>();
+        pwdw_block<STEPS, MODE, CHUNKED, PROD, false, WIN, SL>(a, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
+    } else
+        pwdw_block<STEPS, MODE, CHUNKED, PROD, false, WIN, SL>(arg, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
 }
 
 // The COHERENT form of the same launch (PwDwArgs::coherent, used under direct dispatch -- direct.cc): every tensor the launch
@@ -404,11 +474,15 @@ __global__ __launch_bounds__(512) void pwdw_i8_kernel(PwDwArgs a)
 // multiplier vectors, which nobody ever writes, stay valid in the L2s from one pass to the next.  The first convolution's
 // graph input (PROD 1) is read with ordinary loads: it changes only between bursts, behind a system-scope acquire.
 template <int STEPS, int MODE, bool CHUNKED, int PROD, int WIN, int SL>
-__global__ __launch_bounds__(512) void pwdw_i8_coh_kernel(PwDwArgs a)
+__global__ __launch_bounds__(512) void pwdw_i8_coh_kernel(PwDwArgs arg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned inter[];
     const ChainDep none = {nullptr, 0, nullptr, nullptr};
-    pwdw_block<STEPS, MODE, CHUNKED, PROD, true, WIN, SL>(a, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
+    if constexpr (kPwdwFetch<STEPS, SL>) {
+        const PwDwArgs a = pwdw_fetch_args<MODE != 0 && MODE != 4>();
+        pwdw_block<STEPS, MODE, CHUNKED, PROD, true, WIN, SL>(a, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
+    } else
+        pwdw_block<STEPS, MODE, CHUNKED, PROD, true, WIN, SL>(arg, inter, blockIdx.x, blockIdx.y, blockIdx.z, blockDim.x, none);
 }
 
 #ifdef TAMD_PWDW_CHAIN_EXPERIMENT
