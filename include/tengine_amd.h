@@ -74,6 +74,10 @@ enum {
     TAMD_OP_CLIP = 17,     /* param: tamd_clip_param; int8 / uint8 (clip_kernel_ref_int8.c / _uint8.c:41-80); ReLU6 of an ONNX export */
     TAMD_OP_HARDSWISH = 18,/* param: tamd_hardswish_param; uint8 only (hardswish_kernel_ref_uint8.c:41-83; no int8 kernel in the reference) */
     TAMD_OP_MISH = 19,     /* uint8 only, a 4-D tensor (mish_kernel_ref_uint8.c:41-95 reads dims[0..3]; no int8 kernel in the reference)  */
+    /* every ONNX Resize: param tamd_interp_param.  Nearest (resize_type 1) of a 4-D tensor in int8 / uint8 graphs: any batch, scales
+     * below 1, non-integer and per-axis scales (interp_ref.c:275-301 / :384-410).  The source indices (tamd_interp_indices) and the byte
+     * map (tamd_interp_table) are built on the host at prerun.  Bilinear and fp32 graphs stay on the CPU device */
+    TAMD_OP_INTERP = 20,
     TAMD_OP_NUM
 };
 
@@ -108,6 +112,9 @@ typedef struct tamd_reshape_param { int dim_num; int dims[8]; } tamd_reshape_par
 typedef struct tamd_clip_param { float max, min; } tamd_clip_param;           /* clip_param.h */
 /* hardswish_param.h; carried, not used: the reference's uint8 kernel computes x * clamp(x + 3, 0, 6) / 6 whatever they hold */
 typedef struct tamd_hardswish_param { float alpha, beta; } tamd_hardswish_param;
+/* TM2_InterpParam order (tm2_format.h:898-905).  Both scales non-zero: the output is (int)(in * scale) per axis and the sizes are not
+ * read; otherwise the sizes are, and the scales become (float)out / (float)in (interp.c:51-60) */
+typedef struct tamd_interp_param { int resize_type; float width_scale, height_scale; int output_width, output_height; } tamd_interp_param;
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */
@@ -207,6 +214,15 @@ TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_d
  * the device does not run */
 TAMD_API int tamd_lut_table(int op, int dtype, const void* param, float in_scale, int in_zp, float out_scale, int out_zp,
                             unsigned char table[256]);
+/* the two host-built operands of a nearest Interp node (csrc/interp_tables.cc; no GPU needed).
+ * tamd_interp_table: table[b] = the output byte for input byte b between tensors of these quantisation parameters (interp_ref.c:269-272,
+ * 346-354: int8 saturates at +-127, so -128 comes out as -127 even between equal scales; :378-381, 455-463: uint8 at 0 .. 255).  0, or
+ * -1 for a dtype other than int8 / uint8.
+ * tamd_interp_indices: idx[o] = (int)((float)o / scale) for o in [0, out_extent), the source row / column of output row / column o
+ * (interp_ref.c:292-293).  0, or -1 when an index leaves [0, in_extent) -- the reference would read out of bounds there -- or an
+ * extent is not positive */
+TAMD_API int tamd_interp_table(int dtype, float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
+TAMD_API int tamd_interp_indices(int in_extent, int out_extent, float scale, int* idx);
 
 /* ---- graph construction: the plugin's pre_run walks `struct subgraph` (source/graph/subgraph.h, node.h:46-70,
  * tensor.h:43-102) and mirrors it through these calls, like CUDAEngine::Build does for its own IR

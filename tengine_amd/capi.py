@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -85,11 +85,30 @@ def lib():
             getattr(L, name).argtypes = args
         L.tamd_graph_destroy.restype = None
         L.tamd_lut_table.argtypes = [ci, ci, vp, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        L.tamd_interp_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
         _lib = L
     return _lib
 
 
 OP_SIGMOID, OP_CLIP, OP_HARDSWISH, OP_MISH = 16, 17, 18, 19      # TAMD_OP_* of the byte-map operators
+OP_INTERP = 20
+
+
+def interp_table(dtype, in_scale, in_zp, out_scale, out_zp):
+    """tamd_interp_table(): the 256 output bytes (uint8 array, indexed by the input byte's bit pattern) of a nearest Interp node between
+    tensors of these quantisation parameters; None for a type the device does not run.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_interp_table(dtype, in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
+
+
+def interp_indices(in_extent, out_extent, scale):
+    """tamd_interp_indices(): the source row (column) of every output row (column) of a nearest Interp node, (int)((float)o / scale);
+    None when one of them leaves the input.  Needs no GPU."""
+    idx = (C.c_int * max(out_extent, 1))()
+    rc = lib().tamd_interp_indices(in_extent, out_extent, scale, idx)
+    return None if rc != 0 else np.array(idx[:out_extent], dtype=np.int32)
 
 
 def lut_table(op, dtype, in_scale, in_zp, out_scale, out_zp, params=None):

@@ -49,6 +49,7 @@ union NodeParam {
     tamd_priorbox_param priorbox;
     tamd_clip_param clip;
     tamd_hardswish_param hardswish;
+    tamd_interp_param interp;
 };
 
 struct HNode {
@@ -244,6 +245,9 @@ int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const 
 int plan_nchw_outputs(tamd_graph* g, size_t esz);
 // a Sigmoid / Clip / HardSwish / Mish node of an int8 or uint8 graph as ONE launch (graph_plan.hip): table upload + lut_u8
 int plan_lut(tamd_graph* g, HNode& n, Step* out);
+// a nearest Interp node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch (graph_plan.hip): index vectors and byte map uploaded,
+// interp_nearest_i8 / interp_nearest_u8; reads and writes channel slices (concat views)
+int plan_interp(tamd_graph* g, HNode& n, Step* out);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
 inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
 // .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of

@@ -79,6 +79,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_RESHAPE || op == TAMD_OP_PRIORBOX) return 1; // dense device tensors: uint8 / fp32 graphs; int8 since round 6 (graph_plan.hip)
     if (op == TAMD_OP_PERMUTE) return dtype != TAMD_DT_FP32;       // SSD heads (Permute -> Flatten -> Concat): uint8, and int8 since round 6
     if (is_lut_op(op)) return lut_op_on_device(op, dtype);         // byte maps by table: the quantised forms the reference has (which ranks: tamd_node_supported)
+    if (op == TAMD_OP_INTERP) return interp_on_device(dtype);      // nearest, int8 / uint8 (which modes, sizes and ranks: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
     case TAMD_OP_ELTWISE: case TAMD_OP_CONCAT: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
@@ -182,6 +183,16 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         if (n->op == TAMD_OP_CLIP && !n->param) return 0;
         return lut_rank_on_device(n->op, in[0].dim_num);
     }
+    case TAMD_OP_INTERP: {
+        if (n_in < 1 || !in) return 0;
+        InterpGeom geom;
+        std::vector<int> iy, ix;
+        if (interp_refusal((const tamd_interp_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                           (size_t)out[0].quant_num, &geom, &iy, &ix))
+            return 0;
+        return out[0].dim_num == 4 && out[0].dims[0] == in[0].dims[0] && out[0].dims[1] == in[0].dims[1] && out[0].dims[2] == geom.out_h
+               && out[0].dims[3] == geom.out_w;
+    }
     default:
         return 1;
     }
@@ -240,6 +251,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_PRIORBOX: n.p.priorbox = *(const tamd_priorbox_param*)d->param; break;
         case TAMD_OP_CLIP: n.p.clip = *(const tamd_clip_param*)d->param; break;
         case TAMD_OP_HARDSWISH: n.p.hardswish = *(const tamd_hardswish_param*)d->param; break;
+        case TAMD_OP_INTERP: n.p.interp = *(const tamd_interp_param*)d->param; break;
         default: break;
         }
     }

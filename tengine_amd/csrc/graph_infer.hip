@@ -225,6 +225,13 @@ int infer_shapes(tamd_graph* g)
             y.dims = {x.dims[0], x.dims[1], x.dims[2] * sc, x.dims[3] * sc};
             break;
         }
+        case TAMD_OP_INTERP: {            // interp.c:51-67: by the scales when both are set, else the sizes (interp_tables.cc)
+            InterpGeom geom;
+            if (x.dims.size() != 4) { set_error("interp %s: input is not 4-D", n.name.c_str()); return -1; }
+            if (!interp_resolve(n.p.interp, x.dims[2], x.dims[3], &geom)) { set_error("interp %s: the reference does not keep this output size when it infers the shape again", n.name.c_str()); return -1; }
+            y.dims = {x.dims[0], x.dims[1], geom.out_h, geom.out_w};
+            break;
+        }
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
             y.dims.resize(4);
@@ -286,6 +293,14 @@ int validate_graph(tamd_graph* g)
             if (!lut_op_on_device(n.op, x.dtype)) return bad(n, "Sigmoid / Clip run on the device in int8 and uint8 graphs, HardSwish / Mish in uint8 graphs only");
             if (!lut_rank_on_device(n.op, (int)x.dims.size())) return bad(n, "Mish is defined for a 4-D tensor only");
             if (x.scales.empty() || g->tensors[n.out[0]].scales.empty()) return bad(n, "missing quant params");
+        }
+        if (n.op == TAMD_OP_INTERP) {
+            const HTensor& x = g->tensors[n.in[0]];
+            InterpGeom geom;
+            std::vector<int> iy, ix;
+            const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(),
+                                             g->tensors[n.out[0]].scales.size(), &geom, &iy, &ix);
+            if (why) return bad(n, why);
         }
         if (n.op != TAMD_OP_CONV && n.op != TAMD_OP_FC) continue;
         const HTensor& x = g->tensors[n.in[0]];

@@ -265,7 +265,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 static int plan_concat_views(tamd_graph* g, I8Layout& L)
 {
     auto producer_op = [&](int t) { for (auto& n : g->nodes) if (!n.out.empty() && n.out[0] == t) return n.op; return -1; };
-    auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE; };
+    auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP; };
     for (auto& n : g->nodes) {
         if (n.op != TAMD_OP_CONCAT || L.flat_concat[&n - g->nodes.data()]) continue;
         HTensor& y = g->tensors[n.out[0]];
@@ -878,6 +878,56 @@ int plan_lut(tamd_graph* g, HNode& n, Step* out)
     return 0;
 }
 
+// Nearest Interp, int8 and uint8 graphs alike (graph_u8.hip calls this too).  Everything the reference computes for the node is done
+// HERE, once: the scales and the output size (interp_resolve), the source row of every output row and the source column of every
+// output column (tamd_interp_indices), the byte map between the two tensors' quantisation parameters (tamd_interp_table) -- uploaded,
+// and one launch of interp.hip looks them up.  int8: NHWC with padded channel stride, reads a channel slice, writes one (a concat
+// view), like plan_upsample.  uint8: dense NCHW; writes a channel range of a concat buffer (out_img / out_c0), like plan_map_u8.
+int plan_interp(tamd_graph* g, HNode& n, Step* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    InterpGeom geom;
+    std::vector<int> iy, ix;
+    const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), &geom, &iy, &ix);
+    if (why) { set_error("interp %s: %s", n.name.c_str(), why); return -1; }
+    if (y.dtype != x.dtype || y.n != x.n || y.c != x.c || y.h != geom.out_h || y.w != geom.out_w) { set_error("interp %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    std::vector<unsigned> table(64);
+    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
+        set_error("interp %s: not supported on the device for data type %d", n.name.c_str(), x.dtype);
+        return -1;
+    }
+    int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, iy, &diy) || upload(g, ix, &dix) || upload(g, table, &dtable)) return -1;
+    const double bytes = 2.0 * (double)y.elems();
+    if (x.dtype == TAMD_DT_INT8) {
+        // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
+        const int cv = rup(x.c, 16);
+        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || y.cs <= 0 || x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + cv > x.cs || y.c_off + cv > y.cs) {
+            set_error("interp %s: channel slice not 16-byte aligned", n.name.c_str());
+            return -1;
+        }
+        InterpI8Args a{};
+        a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+        a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs;
+        a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
+        a.iy = diy; a.ix = dix; a.table = dtable;
+        *out = make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); });
+    } else {
+        if (x.is_view) { set_error("interp %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
+        InterpU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+        a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w;
+        a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+        a.iy = diy; a.ix = dix; a.table = dtable;
+        a.identity = 1;
+        for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
+        *out = make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); });
+    }
+    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
+    return 0;
+}
+
 // upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
 static int plan_upsample(tamd_graph* g, HNode& n)
 {
@@ -992,6 +1042,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
             if (!(r = plan_lut(g, n, &one.step))) g->steps.push_back(one.step);
             break;
+        case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &one.step))) g->steps.push_back(one.step); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

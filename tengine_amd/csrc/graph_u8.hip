@@ -861,10 +861,10 @@ static int plan_conv_node_u8(tamd_graph* g, size_t ni, std::vector<char>* fused,
 int plan_u8(tamd_graph* g)
 {
     // concat-by-offset: when an input carries the concat output's (scale, zero point) the reference's per-element rescale
-    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample whose only
+    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample / interp whose only
     // consumer is that concat writes in place
     if (plan_nchw_buffers(g, 1, [](const HNode& pn, const HTensor& xi, const HTensor& y) {
-            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE) && !xi.scales.empty() && !y.scales.empty()
+            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE || pn.op == TAMD_OP_INTERP) && !xi.scales.empty() && !y.scales.empty()
                    && xi.scales[0] == y.scales[0] && (xi.zps.empty() ? 0 : xi.zps[0]) == (y.zps.empty() ? 0 : y.zps[0]);
         }))
         return -1;
@@ -888,6 +888,11 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: {     // byte maps by table: the planner both graphs share
             Step st;
             if (!(rc = plan_lut(g, n, &st))) out.push_back(st);
+            break;
+        }
+        case TAMD_OP_INTERP: {                  // nearest: index vectors + byte map at prerun, one launch (graph_plan.hip: plan_interp)
+            Step st;
+            if (!(rc = plan_interp(g, n, &st))) out.push_back(st);
             break;
         }
         case TAMD_OP_PERMUTE:

@@ -290,6 +290,25 @@ struct LutArgs {           // y[i] = table[x[i]] over `count` bytes, x and y 16-
     const unsigned* table; // [64]: entries 4i .. 4i + 3 in the bytes of dword i, lowest first (tamd_lut_table's 256 bytes as they lie)
 };
 
+struct InterpI8Args {      // nearest Interp, NHWC int8 (interp.hip): y[n][oy][ox][c] = table[x[n][iy[oy]][ix[ox]][c]], padding lanes written 0
+    const int8_t* x;       // first channel of the input (a view's channel offset applied)
+    int8_t* y;             // base of the output buffer
+    int N, H, W, C, cs_in; // input map and its pixel stride
+    int OH, OW, ldc, c_off;// output map, its pixel stride and channel offset (a concat view)
+    const int* iy;         // [OH] source row of every output row, [OW] source column of every output column (tamd_interp_indices)
+    const int* ix;
+    const unsigned* table; // [64]: tamd_interp_table's 256 bytes as they lie
+};
+
+struct InterpU8Args {      // nearest Interp, dense NCHW uint8 (interp.hip)
+    const uint8_t* x; uint8_t* y;
+    int N, C, H, W, OH, OW;
+    int out_img, out_c0;   // output image stride (bytes) / channel offset (concat), as in U8MapArgs
+    const int* iy; const int* ix;
+    const unsigned* table;
+    int identity;          // the table maps every byte to itself: no lookups
+};
+
 struct SoftmaxI8Args {     // softmax over ONE axis of an int8 tensor: the channels of an NHWC tensor (a view's channel slice included), or --
                            // round 6 -- any axis of a dense (reference-order) or NHWC tensor
     const int8_t* x; int8_t* y;
@@ -407,6 +426,8 @@ hipError_t launch_upsample_i8(const UpsampleI8Args& a, hipStream_t s);
 hipError_t launch_eltwise(const EltArgs& a, hipStream_t s);
 hipError_t launch_relu(const ReluArgs& a, hipStream_t s);
 hipError_t launch_lut(const LutArgs& a, hipStream_t s);
+hipError_t launch_interp_i8(const InterpI8Args& a, hipStream_t s);
+hipError_t launch_interp_u8(const InterpU8Args& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);
 hipError_t launch_concat_copy_i8(const CatCopyArgs& a, hipStream_t s);
 hipError_t launch_flatcat_i8(const FlatCatI8Args& a, hipStream_t s);

@@ -2,7 +2,10 @@
 // stated here once, with the reason for its number.  Only rules that are written at more than one site live here; what a single
 // planner alone decides stays in that planner.
 #pragma once
+#include <vector>
+
 #include "kernels.h"
+#include "interp_tables.h"
 #include "lut_tables.h"
 
 namespace tamd {
@@ -35,5 +38,27 @@ inline bool is_lut_op(int op) { return op == TAMD_OP_SIGMOID || op == TAMD_OP_CL
 // Mish: mish_kernel_ref_uint8.c:43-51 sizes its loops from dims[0..3] -- on a tensor of another rank the reference reads dimensions that
 // are not there, and there are no bytes to equal; the other three kernels run over elem_num
 inline bool lut_rank_on_device(int op, int dim_num) { return op != TAMD_OP_MISH || dim_num == 4; }
+
+// Interp: the nearest mode of the two quantised kernels (interp_ref.c; interp.hip).  fp32 graphs keep the node on the CPU device
+inline bool interp_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// .. and one node of it: nullptr when the device runs it (*geom: the scales and the output size, interp_tables.h; *iy / *ix: the source
+// row of every output row, the source column of every output column), else the reason.  in_dims: the input's shape; in_quant /
+// out_quant: how many (scale, zero point) pairs the two tensors carry.  interp_ref.c reads dims[2] and dims[3] and nothing else, so the
+// tensor is 4-D; bilinear (resize_type 2 | 4) is undefined at batch > 1 there and is not built; an index outside the input is a read
+// out of bounds in the reference: no bytes to equal
+inline const char* interp_refusal(const tamd_interp_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant,
+                                  size_t out_quant, InterpGeom* geom, std::vector<int>* iy, std::vector<int>* ix)
+{
+    if (!p) return "Interp needs its parameter";
+    if (!interp_on_device(dtype)) return "Interp runs on the device in int8 and uint8 graphs only";
+    if (p->resize_type != 1) return "only nearest Interp (resize_type 1) runs on the device";
+    if (in_dim_num != 4 || in_const) return "Interp takes a 4-D tensor that is not a constant";
+    if (in_quant != 1 || out_quant != 1) return "Interp needs per-tensor quant params on both sides";
+    if (!interp_resolve(*p, in_dims[2], in_dims[3], geom)) return "Interp: the reference does not keep this output size when it infers the shape again";
+    iy->resize((size_t)geom->out_h); ix->resize((size_t)geom->out_w);
+    if (tamd_interp_indices(in_dims[2], geom->out_h, geom->height_scale, iy->data()) || tamd_interp_indices(in_dims[3], geom->out_w, geom->width_scale, ix->data()))
+        return "Interp: a source index leaves the input";
+    return nullptr;
+}
 
 }  // namespace tamd

@@ -78,6 +78,7 @@ int map_op(uint32_t t)
     case 37: return TAMD_OP_SIGMOID;
     case 51: return TAMD_OP_UPSAMPLE;
     case 70: return TAMD_OP_HARDSWISH;
+    case 71: return TAMD_OP_INTERP;
     case 87: return TAMD_OP_CLIP;
     case 97: return TAMD_OP_MISH;
     default: return -1;
@@ -184,6 +185,10 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
             case TAMD_OP_UPSAMPLE: p.ups.scale = r.f32(po); break;
             case TAMD_OP_CLIP: p.clip.max = r.f32(po); p.clip.min = r.f32(po + 4); break;                 // TM2_ClipParam {max, min}
             case TAMD_OP_HARDSWISH: p.hardswish.alpha = r.f32(po); p.hardswish.beta = r.f32(po + 4); break;   // TM2_HardSwishParam {alpha, beta}
+            case TAMD_OP_INTERP:                               // TM2_InterpParam {resize_type, width_scale, height_scale, output_width, output_height}
+                p.interp.resize_type = r.i32(po); p.interp.width_scale = r.f32(po + 4); p.interp.height_scale = r.f32(po + 8);
+                p.interp.output_width = r.i32(po + 12); p.interp.output_height = r.i32(po + 16);
+                break;
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)
                 tamd_priorbox_param& q = p.priorbox;
                 auto floats = [&](uint32_t vo_, float* dst, int cap, int* num) {      // TM2_Vector_floats {v_num, data[]}

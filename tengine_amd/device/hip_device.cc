@@ -49,6 +49,7 @@ extern "C" {
 #include "fc_param.h"
 #include "flatten_param.h"
 #include "hardswish_param.h"
+#include "interp_param.h"
 #include "permute_param.h"
 #include "pooling_param.h"
 #include "priorbox_param.h"
@@ -84,6 +85,8 @@ const OpRow kOps[] = {
     // byte maps by table (csrc/lut_tables.cc): the quantised kernels of the reference alone; which of int8 / uint8: tamd_op_supported
     {OP_SIGMOID, TAMD_OP_SIGMOID, true},    {OP_CLIP, TAMD_OP_CLIP, true},        {OP_HARDSWISH, TAMD_OP_HARDSWISH, true},
     {OP_MISH, TAMD_OP_MISH, true},
+    // every ONNX Resize; the device runs the nearest mode of the two quantised kernels (which nodes: tamd_node_supported)
+    {OP_INTERP, TAMD_OP_INTERP, true},
 };
 
 const OpRow* find_op(int op)
@@ -145,7 +148,7 @@ tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
-    tamd_clip_param clip; tamd_hardswish_param hardswish;
+    tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -193,6 +196,11 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
     case TAMD_OP_HARDSWISH: {
         const struct hardswish_param* p = (const struct hardswish_param*)n->op.param_mem;
         s->hardswish = {p->alpha, p->beta};
+        break;
+    }
+    case TAMD_OP_INTERP: {           // all five fields (interp.c infer_shape already ran: both scales are set, the sizes are its result)
+        const struct interp_param* p = (const struct interp_param*)n->op.param_mem;
+        s->interp = {p->resize_type, p->width_scale, p->height_scale, p->output_width, p->output_height};
         break;
     }
     case TAMD_OP_PERMUTE: {

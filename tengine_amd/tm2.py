@@ -29,7 +29,7 @@ OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Softmax": 28, "Upsample": 51,
-    "Sigmoid": 37, "HardSwish": 70, "Clip": 87, "Mish": 97,
+    "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Clip": 87, "Mish": 97,
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
 
@@ -132,6 +132,8 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<2f", p["max"], p["min"])
     if op == "HardSwish":        # TM2_HardSwishParam {alpha, beta}; the loader reads the blob (tm2_hardswish.c:48-51), the uint8 kernel neither value
         return struct.pack("<2f", p.get("alpha", 1.0), p.get("beta", 3.0))
+    if op == "Interp":           # TM2_InterpParam tm2_format.h:898-905; scales 0: the sizes decide (interp.c:51-60)
+        return struct.pack("<i2f2i", p["resize_type"], p.get("width_scale", 0.0), p.get("height_scale", 0.0), p.get("output_width", 0), p.get("output_height", 0))
     if op in ("Const", "InputOp", "Dropout", "ReLU6", "Sigmoid", "Mish"):
         return None
     raise NotImplementedError("tm2 writer: op %s" % op)
@@ -163,6 +165,8 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         return dict(zip(["max", "min"], struct.unpack_from("<2f", b, off)))
     if op == "HardSwish":
         return dict(zip(["alpha", "beta"], struct.unpack_from("<2f", b, off)))
+    if op == "Interp":
+        return dict(zip(["resize_type", "width_scale", "height_scale", "output_width", "output_height"], struct.unpack_from("<i2f2i", b, off)))
     if op == "Permute":
         v = struct.unpack_from("<5i", b, off)
         return {"flag": v[0], "order": list(v[1:])}
