@@ -78,6 +78,11 @@ enum {
      * below 1, non-integer and per-axis scales (interp_ref.c:275-301 / :384-410).  The source indices (tamd_interp_indices) and the byte
      * map (tamd_interp_table) are built on the host at prerun.  Bilinear and fp32 graphs stay on the CPU device */
     TAMD_OP_INTERP = 20,
+    /* 21: reserved, never supported */
+    /* the channel-moving operators of a ShuffleNet unit, int8 / uint8 graphs: in the reference both are byte copies (split_ref.c:109-135,
+     * shuffle_channel_ref.c), only the uint8 Split requantises byte to byte (tamd_split_table).  fp32 graphs keep them on the CPU device */
+    TAMD_OP_SPLIT = 22,          /* param: tamd_split_param; the split_sizes form along the channel axis of a 4-D tensor */
+    TAMD_OP_SHUFFLECHANNEL = 23, /* param: tamd_shufflechannel_param; a 4-D tensor, channels % group == 0, any batch */
     TAMD_OP_NUM
 };
 
@@ -115,6 +120,12 @@ typedef struct tamd_hardswish_param { float alpha, beta; } tamd_hardswish_param;
 /* TM2_InterpParam order (tm2_format.h:898-905).  Both scales non-zero: the output is (int)(in * scale) per axis and the sizes are not
  * read; otherwise the sizes are, and the scales become (float)out / (float)in (interp.c:51-60) */
 typedef struct tamd_interp_param { int resize_type; float width_scale, height_scale; int output_width, output_height; } tamd_interp_param;
+/* split_param.h with the split_sizes vector inline.  axis: as the reference's loader leaves it (the file's value when is_onnx is set,
+ * else 0).  num: the number of split_sizes; 0: the node carries none (split.c:80-117 then gives every output the input's shape);
+ * -1: the is_caffe form (every output is a full copy).  The device runs num == output_num in 1 .. TAMD_SPLIT_MAX only */
+#define TAMD_SPLIT_MAX 8
+typedef struct tamd_split_param { int axis; int num; int sizes[TAMD_SPLIT_MAX]; } tamd_split_param;
+typedef struct tamd_shufflechannel_param { int group; } tamd_shufflechannel_param;   /* shuffle_channel_param.h */
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */
@@ -223,6 +234,15 @@ TAMD_API int tamd_lut_table(int op, int dtype, const void* param, float in_scale
  * extent is not positive */
 TAMD_API int tamd_interp_table(int dtype, float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
 TAMD_API int tamd_interp_indices(int in_extent, int out_extent, float scale, int* idx);
+/* the two host-built operands of the channel-moving operators (csrc/chanmap_tables.cc; no GPU needed).
+ * tamd_shuffle_sources: src[o] = the input channel that output channel o of a ShuffleChannel node takes: src[group * j + i] =
+ * (channels / group) * i + j (shuffle_channel_ref.c).  0, or -1 for group < 1 or channels % group != 0 -- the reference never writes the
+ * last channels then.
+ * tamd_split_table: table[b] = the output byte of a uint8 Split for input byte b (split_ref.c:94-99, as the compiler contracts it:
+ * roundf(fmaf((float)(b - in_zp), in_scale / out_scale, (float)out_zp)) clamped to 0 .. 255).  An int8 Split copies bytes and has no
+ * table.  0, or -1 without a table */
+TAMD_API int tamd_shuffle_sources(int channels, int group, int* src);
+TAMD_API int tamd_split_table(float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
 
 /* ---- graph construction: the plugin's pre_run walks `struct subgraph` (source/graph/subgraph.h, node.h:46-70,
  * tensor.h:43-102) and mirrors it through these calls, like CUDAEngine::Build does for its own IR

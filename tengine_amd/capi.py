@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -87,12 +87,39 @@ def lib():
         L.tamd_lut_table.argtypes = [ci, ci, vp, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
+        L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
+        L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         _lib = L
     return _lib
 
 
 OP_SIGMOID, OP_CLIP, OP_HARDSWISH, OP_MISH = 16, 17, 18, 19      # TAMD_OP_* of the byte-map operators
 OP_INTERP = 20
+OP_SPLIT, OP_SHUFFLECHANNEL = 22, 23
+SPLIT_MAX = 8
+
+
+class SplitParam(C.Structure):        # tamd_split_param
+    _fields_ = [("axis", C.c_int), ("num", C.c_int), ("sizes", C.c_int * SPLIT_MAX)]
+
+
+class ShuffleChannelParam(C.Structure):   # tamd_shufflechannel_param
+    _fields_ = [("group", C.c_int)]
+
+
+def shuffle_sources(channels, group):
+    """tamd_shuffle_sources(): the input channel every output channel of a ShuffleChannel node takes; None when the group count does not
+    divide the channels.  Needs no GPU."""
+    src = (C.c_int * max(channels, 1))()
+    rc = lib().tamd_shuffle_sources(channels, group, src)
+    return None if rc != 0 else np.array(src[:channels], dtype=np.int32)
+
+
+def split_table(in_scale, in_zp, out_scale, out_zp):
+    """tamd_split_table(): the 256 output bytes of a uint8 Split between tensors of these quantisation parameters.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_split_table(in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 
 
 def interp_table(dtype, in_scale, in_zp, out_scale, out_zp):

@@ -50,6 +50,8 @@ union NodeParam {
     tamd_clip_param clip;
     tamd_hardswish_param hardswish;
     tamd_interp_param interp;
+    tamd_split_param split;
+    tamd_shufflechannel_param shuffle;
 };
 
 struct HNode {
@@ -248,6 +250,10 @@ int plan_lut(tamd_graph* g, HNode& n, Step* out);
 // a nearest Interp node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch (graph_plan.hip): index vectors and byte map uploaded,
 // interp_nearest_i8 / interp_nearest_u8; reads and writes channel slices (concat views)
 int plan_interp(tamd_graph* g, HNode& n, Step* out);
+// Split / ShuffleChannel of a uint8 (NCHW) graph (graph_plan.hip): one chan_map_u8 launch per output tensor, the plane map and the
+// Split's byte map uploaded.  The int8 forms are planned inside graph_plan.hip
+int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
+int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
 inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
 // .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of

@@ -80,6 +80,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_PERMUTE) return dtype != TAMD_DT_FP32;       // SSD heads (Permute -> Flatten -> Concat): uint8, and int8 since round 6
     if (is_lut_op(op)) return lut_op_on_device(op, dtype);         // byte maps by table: the quantised forms the reference has (which ranks: tamd_node_supported)
     if (op == TAMD_OP_INTERP) return interp_on_device(dtype);      // nearest, int8 / uint8 (which modes, sizes and ranks: tamd_node_supported)
+    if (op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL) return chanmap_on_device(dtype);      // byte movers, int8 / uint8 (which forms: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
     case TAMD_OP_ELTWISE: case TAMD_OP_CONCAT: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
@@ -193,6 +194,26 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         return out[0].dim_num == 4 && out[0].dims[0] == in[0].dims[0] && out[0].dims[1] == in[0].dims[1] && out[0].dims[2] == geom.out_h
                && out[0].dims[3] == geom.out_w;
     }
+    case TAMD_OP_SPLIT: {
+        if (n_in < 1 || !in) return 0;
+        const tamd_split_param* p = (const tamd_split_param*)n->param;
+        std::vector<size_t> oq;
+        for (int i = 0; i < n_out; i++) oq.push_back((size_t)out[i].quant_num);
+        if (split_refusal(p, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, n_out, oq.data())) return 0;
+        for (int i = 0; i < n_out; i++)
+            if (out[i].dim_num != 4 || out[i].dims[0] != in[0].dims[0] || out[i].dims[1] != p->sizes[i] || out[i].dims[2] != in[0].dims[2] || out[i].dims[3] != in[0].dims[3])
+                return 0;
+        return 1;
+    }
+    case TAMD_OP_SHUFFLECHANNEL: {
+        if (n_in < 1 || !in) return 0;
+        if (shuffle_refusal((const tamd_shufflechannel_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                            (size_t)out[0].quant_num))
+            return 0;
+        if (out[0].dim_num != 4) return 0;
+        for (int i = 0; i < 4; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
+        return 1;
+    }
     default:
         return 1;
     }
@@ -252,6 +273,8 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_CLIP: n.p.clip = *(const tamd_clip_param*)d->param; break;
         case TAMD_OP_HARDSWISH: n.p.hardswish = *(const tamd_hardswish_param*)d->param; break;
         case TAMD_OP_INTERP: n.p.interp = *(const tamd_interp_param*)d->param; break;
+        case TAMD_OP_SPLIT: n.p.split = *(const tamd_split_param*)d->param; break;
+        case TAMD_OP_SHUFFLECHANNEL: n.p.shuffle = *(const tamd_shufflechannel_param*)d->param; break;
         default: break;
         }
     }

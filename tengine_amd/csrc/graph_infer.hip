@@ -232,6 +232,16 @@ int infer_shapes(tamd_graph* g)
             y.dims = {x.dims[0], x.dims[1], geom.out_h, geom.out_w};
             break;
         }
+        case TAMD_OP_SPLIT: {             // split.c:57-78, the split_sizes form: output i takes sizes[i] of the axis.  Every other form is
+            const tamd_split_param& sp = n.p.split;                    // refused HERE, by name (split_refusal), before a shape is made up for it
+            std::vector<size_t> oq;
+            for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+            const char* why = split_refusal(&sp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+            if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
+            for (int i = 0; i < sp.num; i++) g->tensors[n.out[i]].dims = {x.dims[0], sp.sizes[i], x.dims[2], x.dims[3]};
+            break;
+        }
+        case TAMD_OP_SHUFFLECHANNEL: y.dims = x.dims; break;
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
             y.dims.resize(4);
@@ -300,6 +310,19 @@ int validate_graph(tamd_graph* g)
             std::vector<int> iy, ix;
             const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(),
                                              g->tensors[n.out[0]].scales.size(), &geom, &iy, &ix);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_SPLIT) {
+            const HTensor& x = g->tensors[n.in[0]];
+            std::vector<size_t> oq;
+            for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+            const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_SHUFFLECHANNEL) {
+            const HTensor& x = g->tensors[n.in[0]];
+            const char* why = shuffle_refusal(&n.p.shuffle, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(),
+                                              g->tensors[n.out[0]].scales.size());
             if (why) return bad(n, why);
         }
         if (n.op != TAMD_OP_CONV && n.op != TAMD_OP_FC) continue;

@@ -164,10 +164,13 @@ struct I8Layout {
     std::vector<char> dense, flat_concat;
     // fused[node]: planned inside another node's launch (skipped at its own position); has_fuse / fuse_at[node]: the convolution
     // that takes an eltwise (+ReLU) into its epilogue
+    // cat_shuffle[node]: a channel Concat that runs together with the ShuffleChannel behind it, node index cat_shuffle[node] - 1
     std::vector<char> fused, has_fuse;
     std::vector<FusedElt> fuse_at;
+    std::vector<int> cat_shuffle;
     I8Layout(size_t nt, size_t nn)
-        : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn) {}
+        : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn),
+          cat_shuffle(nn, 0) {}
 };
 
 // ---- DENSE tensors (the SSD head plumbing of an int8 graph).  The convolution stack lives in NHWC buffers
@@ -262,12 +265,19 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 // An input that cannot be written in place (its scale differs -> the reference rescales, concat_kernel_ref_int8.c:70-80;
 // channel count / offset not a multiple of 16; produced or also consumed by a kernel that does not address channel
 // slices; a graph input) keeps its own buffer and is copied by concat_copy_i8 at the concat's position.
+// the operators whose launches address a channel slice of a wider buffer, on the side they read and on the side they write
+static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP; }
+// .. and on the side they read alone.  Split and ShuffleChannel are NOT written in place into a Concat's buffer: they hand on the byte
+// -128 where their input holds it, and the reference's Concat of several inputs turns that byte into 127 even between equal scales
+// (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not
+static bool reads_slices(int op) { return slice_capable(op) || op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL; }
+
 static int plan_concat_views(tamd_graph* g, I8Layout& L)
 {
-    auto producer_op = [&](int t) { for (auto& n : g->nodes) if (!n.out.empty() && n.out[0] == t) return n.op; return -1; };
-    auto slice_capable = [](int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP; };
+    auto producer_op = [&](int t) { for (auto& n : g->nodes) for (int o : n.out) if (o == t) return n.op; return -1; };     // (a Split has several outputs)
     for (auto& n : g->nodes) {
-        if (n.op != TAMD_OP_CONCAT || L.flat_concat[&n - g->nodes.data()]) continue;
+        // (a Concat that runs inside its ShuffleChannel's launch writes no buffer: its inputs must not become slices of one)
+        if (n.op != TAMD_OP_CONCAT || L.flat_concat[&n - g->nodes.data()] || L.cat_shuffle[&n - g->nodes.data()]) continue;
         HTensor& y = g->tensors[n.out[0]];
         int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
         if (ax != 1 || y.dims.size() < 2) { set_error("concat %s: only the channel axis is supported on the device", n.name.c_str()); return -1; }
@@ -280,7 +290,7 @@ static int plan_concat_views(tamd_graph* g, I8Layout& L)
                       && L.view_of[i] < 0 && slice_capable(producer_op(i));
             for (auto& c : g->nodes)            // every other reader must cope with a channel slice too
                 for (int ci : c.in)
-                    if (ci == i && &c != &n && !(slice_capable(c.op) || c.op == TAMD_OP_CONCAT)) ok = false;
+                    if (ci == i && &c != &n && !(reads_slices(c.op) || c.op == TAMD_OP_CONCAT)) ok = false;
             int readers = 0;
             for (int ci : n.in) readers += (ci == i);
             if (readers > 1) ok = false;        // the same tensor twice: one copy per position
@@ -289,6 +299,59 @@ static int plan_concat_views(tamd_graph* g, I8Layout& L)
         }
     }
     return 0;
+}
+
+// Concat -> ShuffleChannel as ONE launch (ShuffleNet-v2: every unit ends in this pair).  A channel Concat whose every input carries the
+// Concat's scale is a copy in the reference but for one byte (concat_kernel_ref_int8.c:70-84 rescales otherwise; -128 comes out as 127
+// from a Concat of several inputs: ChanMapI8Args::fix128), the ShuffleChannel behind it is a copy always: together they are one
+// channel map from the Concat's inputs to the ShuffleChannel's output, and the Concat's own tensor is never written.  Matched BEFORE plan_concat_views, so that the inputs are not turned into slices of a buffer nobody writes.
+// TAMD_PIN=cat_shuffle=0: two steps (A/B runs and the fused == unfused tests)
+static void match_cat_shuffle(tamd_graph* g, I8Layout& L)
+{
+    if (!tamd_pin_int("cat_shuffle", 1)) return;
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        const HNode& n = g->nodes[ni];
+        if (n.op != TAMD_OP_CONCAT || L.flat_concat[ni] || n.in.empty() || n.in.size() > (size_t)kChanMapMaxSrc) continue;
+        const HTensor& y = g->tensors[n.out[0]];
+        const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
+        if (ax != 1 || y.dims.size() != 4 || y.dtype != TAMD_DT_INT8 || y.scales.size() != 1) continue;
+        bool copy = true;
+        for (int i : n.in) {
+            const HTensor& x = g->tensors[i];
+            copy &= x.ttype != TAMD_TT_CONST && x.dtype == y.dtype && x.dims.size() == 4 && x.scales.size() == 1 && (x.scales[0] == y.scales[0] || n.in.size() == 1);
+        }
+        const int sj = copy ? sole_reader(g, n.out[0]) : -1;            // (a graph output counts as a consumer)
+        if (sj < 0 || g->nodes[sj].op != TAMD_OP_SHUFFLECHANNEL || sj < (int)ni) continue;
+        L.cat_shuffle[ni] = sj + 1;
+    }
+}
+
+// Split outputs as VIEWS of the Split's input: an output whose first channel and width are multiples of 16 is a channel slice of the
+// input's pixels as they lie, so it needs no launch where every reader addresses channel slices.  Neither tensor may be a graph input
+// or output (those keep their own staging).  view_of / view_off carry it like a concat view: root_of (plan_buffers) keeps the input's
+// buffer alive until the last reader of the view.  At ShuffleNet's own widths (58, 116, 232) nothing aligns and plan_split copies
+static void plan_split_views(tamd_graph* g, I8Layout& L)
+{
+    auto is_io = [&](int t) {
+        for (auto& io : g->inputs) if (io.tensor == t) return true;
+        for (auto& io : g->outputs) if (io.tensor == t) return true;
+        return false;
+    };
+    for (auto& n : g->nodes) {
+        if (n.op != TAMD_OP_SPLIT || n.in.empty()) continue;
+        const HTensor& x = g->tensors[n.in[0]];
+        if (x.ttype != TAMD_TT_VAR || x.dims.size() != 4 || L.dense[n.in[0]] || is_io(n.in[0])) continue;
+        int first = 0;
+        for (int t : n.out) {
+            const int width = g->tensors[t].c;
+            bool ok = first % 16 == 0 && width % 16 == 0 && width > 0 && !is_io(t) && L.view_of[t] < 0;
+            for (size_t ci = 0; ci < g->nodes.size(); ci++)
+                for (int i : g->nodes[ci].in)
+                    if (i == t && !(reads_slices(g->nodes[ci].op) || (g->nodes[ci].op == TAMD_OP_CONCAT && !L.flat_concat[ci]))) ok = false;
+            if (ok) { L.view_of[t] = n.in[0]; L.view_off[t] = first; }
+            first += width;
+        }
+    }
 }
 
 // graph inputs: NCHW staging; first conv with <=4 channels reads NCHW directly
@@ -336,7 +399,7 @@ static int plan_buffers(tamd_graph* g, I8Layout& L)
             bool is_out = false, dword_producer = false;
             for (auto& o : g->outputs) is_out |= (o.tensor == (int)i);
             for (auto& n : g->nodes)
-                if (!n.out.empty() && n.out[0] == (int)i)
+                if (n.out.size() == 1 && n.out[0] == (int)i)      // (a node with several outputs -- Split -- stores bytes)
                     dword_producer = (n.op == TAMD_OP_CONV || n.op == TAMD_OP_FC || n.op == TAMD_OP_POOL || n.op == TAMD_OP_SOFTMAX);   // (softmax: byte stores, any stride)
             if (is_out && dword_producer) t.cs = t.c;
         }
@@ -441,7 +504,7 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
 {
     g->fused_away.assign(g->tensors.size(), 0);
     const char* fuse_env = getenv("TAMD_FUSE_ELTWISE");
-    auto producer = [&](int t) { for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].out.empty() && g->nodes[i].out[0] == t) return (int)i; return -1; };
+    auto producer = [&](int t) { for (size_t i = 0; i < g->nodes.size(); i++) for (int o : g->nodes[i].out) if (o == t) return (int)i; return -1; };
     for (size_t ei = 0; ei < g->nodes.size() && !(fuse_env && atoi(fuse_env) == 0); ei++) {
         HNode& e = g->nodes[ei];
         if (e.op != TAMD_OP_ELTWISE || e.in.size() != 2) continue;
@@ -928,6 +991,209 @@ int plan_interp(tamd_graph* g, HNode& n, Step* out)
     return 0;
 }
 
+// ---- Split, ShuffleChannel and Concat + ShuffleChannel of an int8 graph: chan_map_i8 (chanmap.hip).  ONE launch writes tensor y from
+// up to kChanMapMaxSrc source tensors; sel[o] = {source, channel of that source} for output channel o.  The table is built and checked
+// here -- every entry inside its source's pixel -- and uploaded once; sources and output are addressed where they lie (whole tensors,
+// concat views, Split views), the output's padding lanes are written as zero
+static int plan_chan_map_i8(tamd_graph* g, const std::string& node, const std::vector<const HTensor*>& srcs, const std::vector<std::pair<int, int>>& sel, HTensor& y,
+                            bool through_concat, Step* out)
+{
+    if (srcs.empty() || srcs.size() > (size_t)kChanMapMaxSrc || sel.size() != (size_t)y.c) { set_error("%s: at most %d sources, one entry per output channel", node.c_str(), kChanMapMaxSrc); return -1; }
+    const int cv = rup(y.c, 16);
+    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + cv > y.cs) { set_error("%s: output channel slice not 16-byte aligned", node.c_str()); return -1; }
+    ChanMapI8Args a{};
+    a.nsrc = (int)srcs.size();
+    for (size_t i = 0; i < srcs.size(); i++) {
+        const HTensor& x = *srcs[i];
+        if (x.dtype != TAMD_DT_INT8 || x.nchw_raw || x.cs <= 0 || !x.dptr || x.n != y.n || x.h != y.h || x.w != y.w || x.c_off + x.c > x.cs) {
+            set_error("%s: source %s is not an NHWC int8 tensor of the output's map", node.c_str(), x.name.c_str());
+            return -1;
+        }
+        a.src[i] = ChanMapI8Src{(const int8_t*)x.dptr, x.cs};
+    }
+    std::vector<unsigned> table((size_t)cv, kChanMapZero);
+    for (int o = 0; o < y.c; o++) {
+        const int s = sel[o].first, c = sel[o].second;
+        if (s < 0 || s >= a.nsrc || c < 0 || c >= srcs[s]->c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
+        table[o] = (unsigned)s << 28 | (unsigned)(srcs[s]->c_off + c);
+    }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    a.y = (int8_t*)y.dptr; a.pixels = (long)y.n * y.h * y.w; a.C = y.c; a.ldc = y.cs; a.c_off = y.c_off; a.table = dtable;
+    a.fix128 = through_concat ? 1 : 0;                      // a Concat of several inputs: -128 -> 127 (chanmap.hip)
+    *out = make_step(node, "chan_map_i8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_i8(a, s); });
+    for (const HTensor* x : srcs) out->rd.push_back(access_of(*x));
+    out->wr.push_back(access_of(y));                                         // (complete lists; the step stays ordered: no deps)
+    return 0;
+}
+
+// group 2 over two halves of equal width `half` -- channels [a0, a0 + half) of tensor a and [b0, b0 + half) of tensor b -- as the
+// interleave launch (chanmap.hip: chan_map_i8_g2) where both halves can be read in aligned 8-byte words inside their own pixels.
+// 1: *out is that launch, 0: the table form has to do it.  TAMD_PIN=chan_map_g2=0: always the table form (A/B runs, and the test that
+// demands the same bytes of both)
+static int try_chan_map_g2(tamd_graph* g, const std::string& node, const HTensor& a, int a0, const HTensor& b, int b0, int half, HTensor& y, bool through_concat,
+                           Step* out)
+{
+    if (!tamd_pin_int("chan_map_g2", 1) || y.c != 2 * half || half < 1) return 0;
+    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + rup(y.c, 16) > y.cs) return 0;
+    const int ra = a.c_off + a0, rb = b.c_off + b0, rv = rup(half, 8);
+    for (const HTensor* x : {&a, &b})
+        if (x->dtype != TAMD_DT_INT8 || x->nchw_raw || x->cs <= 0 || x->cs % 8 || !x->dptr || x->n != y.n || x->h != y.h || x->w != y.w) return 0;
+    if (a0 < 0 || b0 < 0 || a0 + half > a.c || b0 + half > b.c || ra % 8 || rb % 8 || ra + rv > a.cs || rb + rv > b.cs) return 0;
+    ChanMapG2Args k{};
+    k.a = (const int8_t*)a.dptr + ra; k.b = (const int8_t*)b.dptr + rb; k.cs_a = a.cs; k.cs_b = b.cs;
+    k.y = (int8_t*)y.dptr; k.pixels = (long)y.n * y.h * y.w; k.half = half; k.ldc = y.cs; k.c_off = y.c_off; k.fix128 = through_concat ? 1 : 0;
+    *out = make_step(node, "chan_map_i8_g2", 0, 2.0 * (double)y.elems(), [k](hipStream_t s) { return launch_chan_map_g2(k, s); });
+    out->rd.push_back(access_of(a));
+    if (&a != &b) out->rd.push_back(access_of(b));
+    out->wr.push_back(access_of(y));
+    return 1;
+}
+
+// split_ref.c:109-135: output i is channels [first_i, first_i + sizes[i]) of the input, bytes as they are.  An output that
+// plan_split_views made a view of the input has no launch; every other one is one chan_map_i8 launch with one source
+static int plan_split(tamd_graph* g, I8Layout& L, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    std::vector<size_t> oq;
+    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
+    int first = 0;
+    for (size_t i = 0; i < n.out.size(); i++) {
+        HTensor& y = g->tensors[n.out[i]];
+        if (y.dtype != x.dtype || y.dims.size() != 4 || y.n != x.n || y.c != n.p.split.sizes[i] || y.h != x.h || y.w != x.w) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
+        if (!(L.view_of[n.out[i]] == n.in[0] && L.view_off[n.out[i]] == first)) {
+            std::vector<std::pair<int, int>> sel((size_t)y.c);
+            for (int c = 0; c < y.c; c++) sel[c] = {0, first + c};
+            Step st;
+            if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
+            g->steps.push_back(st);
+        }
+        first += y.c;
+    }
+    return 0;
+}
+
+// shuffle_channel_ref.c: output channel group * j + i takes input channel (C / group) * i + j (tamd_shuffle_sources), bytes as they are
+static int shuffle_sources(const HNode& n, const HTensor& x, const HTensor& y, std::vector<int>* src)
+{
+    const char* why = shuffle_refusal(&n.p.shuffle, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size());
+    if (why) { set_error("shufflechannel %s: %s", n.name.c_str(), why); return -1; }
+    if (y.dtype != x.dtype || y.dims != x.dims) { set_error("shufflechannel %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    src->resize((size_t)x.dims[1]);
+    if (tamd_shuffle_sources(x.dims[1], n.p.shuffle.group, src->data())) { set_error("shufflechannel %s: the group count must divide the channels", n.name.c_str()); return -1; }
+    return 0;
+}
+
+static int plan_shuffle(tamd_graph* g, HNode& n)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(n, x, y, &src)) return -1;
+    std::vector<std::pair<int, int>> sel((size_t)y.c);
+    for (int o = 0; o < y.c; o++) sel[o] = {0, src[o]};
+    Step st;
+    if (n.p.shuffle.group == 2 && try_chan_map_g2(g, n.name, x, 0, x, x.c / 2, x.c / 2, y, false, &st)) { g->steps.push_back(st); return 0; }
+    if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
+    g->steps.push_back(st);
+    return 0;
+}
+
+// The pair match_cat_shuffle found, planned at the CONCAT's position: the launch reads the Concat's inputs and writes the
+// ShuffleChannel's output.  That output's lifetime starts at the earliest producer within two hops above the ShuffleChannel
+// (plan_buffers: shuffle <- concat <- the inputs' producers), so it never shares memory with an input; planned at the
+// ShuffleChannel's position an input's buffer could have been reused before it is read.  plan_i8 checks it (writes_what_it_reads)
+static int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj)
+{
+    HNode& sh = g->nodes[sj];
+    HTensor& mid = g->tensors[cat.out[0]];
+    HTensor& y = g->tensors[sh.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(sh, mid, y, &src)) return -1;
+    std::vector<const HTensor*> srcs;
+    std::vector<int> begin;                                  // first Concat channel of every input
+    int total = 0;
+    for (int i : cat.in) { srcs.push_back(&g->tensors[i]); begin.push_back(total); total += g->tensors[i].c; }
+    if (total != mid.c) { set_error("concat %s: the inputs do not add up to the output", cat.name.c_str()); return -1; }
+    std::vector<std::pair<int, int>> sel((size_t)y.c);
+    for (int o = 0; o < y.c; o++) {
+        int k = (int)cat.in.size() - 1;
+        while (k > 0 && begin[k] > src[o]) k--;
+        sel[o] = {k, src[o] - begin[k]};
+    }
+    Step st;
+    const bool two_halves = sh.p.shuffle.group == 2 && srcs.size() == 2 && srcs[0]->c == srcs[1]->c;
+    if (!(two_halves && try_chan_map_g2(g, cat.name + "+" + sh.name, *srcs[0], 0, *srcs[1], 0, srcs[0]->c, y, true, &st))
+        && plan_chan_map_i8(g, cat.name + "+" + sh.name, srcs, sel, y, cat.in.size() > 1, &st))
+        return -1;
+    g->steps.push_back(st);
+    L.fused[sj] = 1;
+    g->fused_away[cat.out[0]] = 1;
+    return 0;
+}
+
+// The uint8 forms (graph_u8.hip calls these): dense NCHW, one chan_map_u8 launch per output tensor.  Neither planner makes these
+// nodes' tensors concat views (plan_u8: in_place), which the errors below guard
+static int plan_chan_map_u8(tamd_graph* g, const std::string& node, const HTensor& x, const HTensor& y, const std::vector<int>& planes, const unsigned char* map,
+                            Step* out)
+{
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("%s on a concat view is not supported in a uint8 graph", node.c_str()); return -1; }
+    if (planes.size() != (size_t)y.c || y.n != x.n || y.h != x.h || y.w != x.w) { set_error("%s: output shape mismatch", node.c_str()); return -1; }
+    for (int p : planes)
+        if (p < 0 || p >= x.c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
+    ChanMapU8Args a{};
+    a.identity = 1;
+    std::vector<unsigned> table(64, 0u);
+    if (map) {
+        memcpy(table.data(), map, 256);
+        for (int b = 0; b < 256; b++) a.identity &= map[b] == b;
+    }
+    int* dplanes = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, planes, &dplanes) || upload(g, table, &dtable)) return -1;
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+    a.N = y.n; a.C = y.c; a.HW = y.h * y.w; a.in_img = x.c * x.h * x.w; a.in_planes = x.c;
+    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.src_plane = dplanes; a.table = dtable;
+    *out = make_step(node, "chan_map_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_u8(a, s); });
+    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));
+    return 0;
+}
+
+// split_ref.c:68-107: output i is channels [first_i, ..) of the input, every byte through tamd_split_table between the two tensors'
+// parameters (the identity between equal ones: no lookups)
+int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    std::vector<size_t> oq;
+    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
+    int first = 0;
+    for (size_t i = 0; i < n.out.size(); i++) {
+        HTensor& y = g->tensors[n.out[i]];
+        if (y.dtype != x.dtype || y.dims.size() != 4 || y.c != n.p.split.sizes[i]) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
+        std::vector<int> planes((size_t)y.c);
+        for (int c = 0; c < y.c; c++) planes[c] = first + c;
+        unsigned char map[256];
+        if (tamd_split_table(x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], map)) { set_error("split %s: no byte map", n.name.c_str()); return -1; }
+        Step st;
+        if (plan_chan_map_u8(g, n.name, x, y, planes, map, &st)) return -1;
+        out->push_back(st);
+        first += y.c;
+    }
+    return 0;
+}
+
+int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(n, x, y, &src)) return -1;
+    return plan_chan_map_u8(g, n.name, x, y, src, nullptr, out);
+}
+
 // upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
 static int plan_upsample(tamd_graph* g, HNode& n)
 {
@@ -1019,7 +1285,10 @@ int plan_i8(tamd_graph* g)
 {
     for (auto& t : g->tensors) if (t.ttype != TAMD_TT_CONST) nhwc_geom(t);
     I8Layout L(g->tensors.size(), g->nodes.size());
-    if (plan_dense(g, L) || plan_concat_views(g, L) || plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
+    if (plan_dense(g, L)) return -1;
+    match_cat_shuffle(g, L);
+    plan_split_views(g, L);
+    if (plan_concat_views(g, L) || plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
     scan_eltwise_fusion(g, L);
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
@@ -1031,7 +1300,9 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_PERMUTE: r = plan_permute(g, L, n); break;
         case TAMD_OP_RESHAPE: r = plan_reshape(g, L, n); break;
         case TAMD_OP_PRIORBOX: r = plan_priorbox(g, n); break;
-        case TAMD_OP_CONCAT: r = L.flat_concat[ni] ? plan_flat_concat(g, L, n) : plan_channel_concat(g, L, n); break;
+        case TAMD_OP_CONCAT:
+            r = L.flat_concat[ni] ? plan_flat_concat(g, L, n) : L.cat_shuffle[ni] ? plan_cat_shuffle(g, L, n, (size_t)L.cat_shuffle[ni] - 1) : plan_channel_concat(g, L, n);
+            break;
         case TAMD_OP_CONV: r = plan_conv_node(g, L, ni); break;
         case TAMD_OP_FC: if (!(r = plan_conv(g, n, true, nullptr, &one))) g->steps.push_back(one.step); break;
         case TAMD_OP_POOL: if (!(r = plan_pool(g, n, &one))) g->steps.push_back(one.step); break;
@@ -1043,6 +1314,8 @@ int plan_i8(tamd_graph* g)
             if (!(r = plan_lut(g, n, &one.step))) g->steps.push_back(one.step);
             break;
         case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &one.step))) g->steps.push_back(one.step); break;
+        case TAMD_OP_SPLIT: r = plan_split(g, L, n); break;
+        case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

@@ -895,6 +895,12 @@ int plan_u8(tamd_graph* g)
             if (!(rc = plan_interp(g, n, &st))) out.push_back(st);
             break;
         }
+        case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // plane maps at prerun, one chan_map_u8 launch per output (graph_plan.hip)
+        case TAMD_OP_SHUFFLECHANNEL: {
+            Step st;
+            if (!(rc = plan_shuffle_u8(g, n, &st))) out.push_back(st);
+            break;
+        }
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;

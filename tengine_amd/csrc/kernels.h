@@ -309,6 +309,45 @@ struct InterpU8Args {      // nearest Interp, dense NCHW uint8 (interp.hip)
     int identity;          // the table maps every byte to itself: no lookups
 };
 
+// Split / ShuffleChannel / Concat + ShuffleChannel of an int8 graph (chanmap.hip): y[pixel][c_off + o] = src[s][pixel][off] for every
+// output channel o, where table[o] = s << 28 | off names the source and the byte offset inside ITS pixel (a view's channel offset
+// included), or kChanMapZero: written as zero.  The table has one entry per channel of the whole 16-byte vectors, rup(C, 16)
+constexpr int kChanMapMaxSrc = 4;
+constexpr unsigned kChanMapZero = 0xffffffffu;
+struct ChanMapI8Src { const int8_t* x; int cs; };      // base of the source's buffer, its bytes per pixel
+struct ChanMapI8Args {
+    ChanMapI8Src src[kChanMapMaxSrc];
+    int nsrc;
+    int8_t* y;             // base of the output buffer
+    long pixels;           // N * H * W, the same in every source
+    int C, ldc, c_off;     // output channels, pixel stride and channel offset (a concat view)
+    const unsigned* table; // [rup(C, 16)]
+    int fix128;            // 1: the byte -128 is written as 127 (the reference's Concat between equal scales, see chanmap.hip)
+};
+
+// group 2 over two sources of equal width `half` (ShuffleNet-v2's own pair: Concat of two halves -> ShuffleChannel(2), or a
+// ShuffleChannel(2) of one tensor): output channel 2j is a[j], 2j + 1 is b[j] -- output vector v is the byte interleave of 8 bytes of each
+struct ChanMapG2Args {
+    const int8_t* a; const int8_t* b;   // first channel of either half (a view's channel offset applied), 8-byte aligned
+    int cs_a, cs_b;        // their bytes per pixel
+    int8_t* y; long pixels;
+    int half, ldc, c_off;
+    int fix128;
+};
+
+// the same operators in a uint8 graph (dense NCHW): output plane o of image n = plane src_plane[o] of image n of x, every byte through
+// `table` unless it is the identity (a uint8 Split's requantisation: tamd_split_table)
+struct ChanMapU8Args {
+    const uint8_t* x; uint8_t* y;
+    int N, C, HW;          // images, OUTPUT planes per image, bytes per plane
+    int in_img;            // bytes per input image
+    int in_planes;         // planes per input image (every src_plane entry is below it: checked where the table is built)
+    int out_img, out_c0;   // output image stride (bytes) / channel offset (concat), as in U8MapArgs
+    const int* src_plane;  // [C]
+    const unsigned* table; // [64]: tamd_split_table's 256 bytes as they lie
+    int identity;
+};
+
 struct SoftmaxI8Args {     // softmax over ONE axis of an int8 tensor: the channels of an NHWC tensor (a view's channel slice included), or --
                            // round 6 -- any axis of a dense (reference-order) or NHWC tensor
     const int8_t* x; int8_t* y;
@@ -428,6 +467,9 @@ hipError_t launch_relu(const ReluArgs& a, hipStream_t s);
 hipError_t launch_lut(const LutArgs& a, hipStream_t s);
 hipError_t launch_interp_i8(const InterpI8Args& a, hipStream_t s);
 hipError_t launch_interp_u8(const InterpU8Args& a, hipStream_t s);
+hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s);
+hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
+hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);
 hipError_t launch_concat_copy_i8(const CatCopyArgs& a, hipStream_t s);
 hipError_t launch_flatcat_i8(const FlatCatI8Args& a, hipStream_t s);

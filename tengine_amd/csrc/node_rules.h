@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "chanmap_tables.h"
 #include "interp_tables.h"
 #include "lut_tables.h"
 
@@ -58,6 +59,48 @@ inline const char* interp_refusal(const tamd_interp_param* p, int dtype, int in_
     iy->resize((size_t)geom->out_h); ix->resize((size_t)geom->out_w);
     if (tamd_interp_indices(in_dims[2], geom->out_h, geom->height_scale, iy->data()) || tamd_interp_indices(in_dims[3], geom->out_w, geom->width_scale, ix->data()))
         return "Interp: a source index leaves the input";
+    return nullptr;
+}
+
+// Split and ShuffleChannel: byte movers of the quantised graphs (split_ref.c, shuffle_channel_ref.c; chanmap.hip).  fp32 graphs keep both
+// on the CPU device
+inline bool chanmap_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// One Split node: nullptr when the device runs it, else the reason.  out_quant: the (scale, zero point) pair count of every output.
+//  - is_caffe (num -1): every output is a full copy of the input -- not a channel mover, it stays on the CPU device
+//  - no split_sizes (num 0): split.c:80-117 gives every output the INPUT's shape, and the kernel then copies past the input's end
+//  - axis 1 only: split.c:60 indexes the shape with the axis as it stands, so -3 reads in front of the array there
+//  - uint8 at batch > 1: ref_split_uint8 ignores out_offset (:99 writes output_data[i]) and leaves images 1.. unwritten
+inline const char* split_refusal(const tamd_split_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, int output_num,
+                                 const size_t* out_quant)
+{
+    if (!p) return "Split needs its parameter";
+    if (!chanmap_on_device(dtype)) return "Split runs on the device in int8 and uint8 graphs only";
+    if (p->num == -1) return "an is_caffe Split (every output a full copy) does not run on the device";
+    if (p->num == 0) return "a Split without split_sizes does not run on the device";
+    if (in_dim_num != 4 || in_const) return "Split takes a 4-D tensor that is not a constant";
+    if (p->axis != 1) return "Split runs on the device along the channel axis (axis 1) only";
+    if (p->num < 1 || p->num > TAMD_SPLIT_MAX || p->num != output_num) return "Split: between 1 and 8 split_sizes, one per output";
+    long sum = 0;
+    for (int i = 0; i < p->num; i++) {
+        if (p->sizes[i] < 1) return "Split: every size must be at least 1";
+        sum += p->sizes[i];
+    }
+    if (sum != in_dims[1]) return "Split: the sizes do not add up to the input's channels";
+    if (in_quant != 1) return "Split needs per-tensor quant params on every tensor";
+    for (int i = 0; i < output_num; i++)
+        if (out_quant[i] != 1) return "Split needs per-tensor quant params on every tensor";
+    if (dtype == TAMD_DT_UINT8 && in_dims[0] != 1) return "a uint8 Split is defined for batch 1 only";
+    return nullptr;
+}
+// One ShuffleChannel node.  channels % group != 0: the reference never writes the last channels, no bytes to equal
+inline const char* shuffle_refusal(const tamd_shufflechannel_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant,
+                                   size_t out_quant)
+{
+    if (!p) return "ShuffleChannel needs its parameter";
+    if (!chanmap_on_device(dtype)) return "ShuffleChannel runs on the device in int8 and uint8 graphs only";
+    if (in_dim_num != 4 || in_const) return "ShuffleChannel takes a 4-D tensor that is not a constant";
+    if (p->group < 1 || in_dims[1] < 1 || in_dims[1] % p->group != 0) return "ShuffleChannel: the group count must divide the channels";
+    if (in_quant != 1 || out_quant != 1) return "ShuffleChannel needs per-tensor quant params on both sides";
     return nullptr;
 }
 

@@ -75,8 +75,10 @@ int map_op(uint32_t t)
     case 21: return TAMD_OP_RELU6;
     case 23: return TAMD_OP_RESHAPE;
     case 28: return TAMD_OP_SOFTMAX;
+    case 29: return TAMD_OP_SPLIT;
     case 37: return TAMD_OP_SIGMOID;
     case 51: return TAMD_OP_UPSAMPLE;
+    case 55: return TAMD_OP_SHUFFLECHANNEL;
     case 70: return TAMD_OP_HARDSWISH;
     case 71: return TAMD_OP_INTERP;
     case 87: return TAMD_OP_CLIP;
@@ -189,6 +191,19 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 p.interp.resize_type = r.i32(po); p.interp.width_scale = r.f32(po + 4); p.interp.height_scale = r.f32(po + 8);
                 p.interp.output_width = r.i32(po + 12); p.interp.output_height = r.i32(po + 16);
                 break;
+            case TAMD_OP_SHUFFLECHANNEL: p.shuffle.group = r.i32(po); break;                              // TM2_ShuffleChannelParam {group}
+            case TAMD_OP_SPLIT: {                              // TM2_SplitParam {axis, split_dim, u8 is_caffe, u8 is_onnx, offset_split_sizes} (tm2_split.c:48-78)
+                const uint32_t flags = r.u32(po + 8), vs = r.u32(po + 12);
+                const bool is_caffe = (flags & 0xffu) != 0, is_onnx = ((flags >> 8) & 0xffu) != 0;
+                p.split.axis = is_onnx ? r.i32(po) : 0;        // the loader takes the file's axis only when is_onnx is set; split.c:134 defaults it to 0
+                if (is_caffe) p.split.num = -1;
+                else if (vs) {                                 // TM2_Vector_dims {v_num, dims[]}
+                    const std::vector<uint32_t> sizes = r.vec(vs);
+                    if (!r.ok || sizes.size() > TAMD_SPLIT_MAX) p.split.num = TAMD_SPLIT_MAX + 1;      // refused by count (split_refusal)
+                    else { p.split.num = (int)sizes.size(); for (size_t i = 0; i < sizes.size(); i++) p.split.sizes[i] = (int)sizes[i]; }
+                }
+                break;
+            }
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)
                 tamd_priorbox_param& q = p.priorbox;
                 auto floats = [&](uint32_t vo_, float* dst, int cap, int* num) {      // TM2_Vector_floats {v_num, data[]}

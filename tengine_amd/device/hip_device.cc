@@ -53,8 +53,10 @@ extern "C" {
 #include "permute_param.h"
 #include "pooling_param.h"
 #include "priorbox_param.h"
+#include "shuffle_channel_param.h"
 #include "relu_param.h"
 #include "softmax_param.h"
+#include "split_param.h"
 #include "upsample_param.h"
 }
 
@@ -87,6 +89,9 @@ const OpRow kOps[] = {
     {OP_MISH, TAMD_OP_MISH, true},
     // every ONNX Resize; the device runs the nearest mode of the two quantised kernels (which nodes: tamd_node_supported)
     {OP_INTERP, TAMD_OP_INTERP, true},
+    // the channel movers of a ShuffleNet unit: byte copies in the quantised kernels of the reference (csrc/chanmap.hip).  An fp32 graph
+    // keeps both on the CPU device (which Split forms: tamd_node_supported; the caffe Slice of the benchmark file is another operator)
+    {OP_SPLIT, TAMD_OP_SPLIT, true},        {OP_SHUFFLECHANNEL, TAMD_OP_SHUFFLECHANNEL, true},
 };
 
 const OpRow* find_op(int op)
@@ -148,7 +153,8 @@ tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
-    tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp;
+    tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
+    tamd_shufflechannel_param shuffle;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -201,6 +207,20 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
     case TAMD_OP_INTERP: {           // all five fields (interp.c infer_shape already ran: both scales are set, the sizes are its result)
         const struct interp_param* p = (const struct interp_param*)n->op.param_mem;
         s->interp = {p->resize_type, p->width_scale, p->height_scale, p->output_width, p->output_height};
+        break;
+    }
+    case TAMD_OP_SHUFFLECHANNEL: s->shuffle.group = ((const struct shuffle_channel_param*)n->op.param_mem)->group; break;
+    case TAMD_OP_SPLIT: {            // the split_sizes vector inline; num -1: is_caffe, 0: no sizes, above TAMD_SPLIT_MAX: too many (all refused by name)
+        const struct split_param* p = (const struct split_param*)n->op.param_mem;
+        s->split = tamd_split_param{};
+        s->split.axis = p->axis;
+        const int num = p->split_sizes_ ? get_vector_num(p->split_sizes_) : 0;
+        if (p->is_caffe) s->split.num = -1;
+        else if (num > TAMD_SPLIT_MAX) s->split.num = TAMD_SPLIT_MAX + 1;
+        else {
+            s->split.num = num;
+            for (int k = 0; k < num; k++) s->split.sizes[k] = *(const int*)get_vector_data(p->split_sizes_, k);
+        }
         break;
     }
     case TAMD_OP_PERMUTE: {

@@ -28,7 +28,7 @@ LAYOUT_NCHW = 0
 OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
-    "Reshape": 23, "Softmax": 28, "Upsample": 51,
+    "Reshape": 23, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Clip": 87, "Mish": 97,
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
@@ -134,6 +134,8 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<2f", p.get("alpha", 1.0), p.get("beta", 3.0))
     if op == "Interp":           # TM2_InterpParam tm2_format.h:898-905; scales 0: the sizes decide (interp.c:51-60)
         return struct.pack("<i2f2i", p["resize_type"], p.get("width_scale", 0.0), p.get("height_scale", 0.0), p.get("output_width", 0), p.get("output_height", 0))
+    if op == "ShuffleChannel":   # TM2_ShuffleChannelParam {group}
+        return struct.pack("<i", p["group"])
     if op in ("Const", "InputOp", "Dropout", "ReLU6", "Sigmoid", "Mish"):
         return None
     raise NotImplementedError("tm2 writer: op %s" % op)
@@ -167,6 +169,13 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         return dict(zip(["alpha", "beta"], struct.unpack_from("<2f", b, off)))
     if op == "Interp":
         return dict(zip(["resize_type", "width_scale", "height_scale", "output_width", "output_height"], struct.unpack_from("<i2f2i", b, off)))
+    if op == "ShuffleChannel":
+        return {"group": struct.unpack_from("<i", b, off)[0]}
+    if op == "Split":           # TM2_SplitParam (tm2_format.h:770-778): {axis, split_dim, u8 is_caffe, u8 is_onnx, offset -> TM2_Vector_dims}
+        axis, split_dim, is_caffe, is_onnx, voff = struct.unpack_from("<iiBBxxI", b, off)
+        n = struct.unpack_from("<I", b, voff)[0] if voff else 0
+        return {"axis": axis, "split_dim": split_dim, "is_caffe": is_caffe, "is_onnx": is_onnx,
+                "split_sizes": list(struct.unpack_from("<%di" % n, b, voff + 4)) if n else []}
     if op == "Permute":
         v = struct.unpack_from("<5i", b, off)
         return {"flag": v[0], "order": list(v[1:])}
@@ -250,6 +259,11 @@ def write_tm2(g: Graph) -> bytes:
         if n.op == "Reshape":    # TM2_ReshapeParam {is_mxnet, reverse, offset_re_shape -> TM2_Vector_dims, is_onnx} (tm2_format.h:565-571)
             pb = struct.pack("<iiIi", n.params.get("is_mxnet", 0), n.params.get("reverse", 0),
                              bl.vec_i32(n.params["re_shape"]), n.params.get("is_onnx", 1))
+        elif n.op == "Split":    # TM2_SplitParam {axis, split_dim, is_caffe, is_onnx, offset_split_sizes -> TM2_Vector_dims}; the vector is written as
+            q = n.params         # Reshape's is, and left out (TM2_NOT_SET) when there are no sizes.  is_onnx defaults to 1: the reference's
+            sizes = q.get("split_sizes", [])     # loader takes `axis` from the file only then (tm2_split.c:61-65)
+            pb = struct.pack("<iiBBxxI", q.get("axis", 1), q.get("split_dim", 1), q.get("is_caffe", 0), q.get("is_onnx", 1),
+                             bl.vec_i32(sizes) if sizes else 0)
         elif n.op == "PriorBox":  # TM2_PriorBoxParam; the loader dereferences all four vector offsets (tm2_priorbox.c:49-52): empty
             q = n.params        # vectors are written as {v_num = 0}
             pb = struct.pack("<4I5i3f2i", bl.vec_f32(q["min_size"]), bl.vec_f32(q.get("max_size", [])),

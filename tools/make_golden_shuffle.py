@@ -1,0 +1,33 @@
+"""Writes tests/golden/shuffle_cases.npz: for every GPU case of tests/shuffle_helpers.py (seeded inputs) the outputs of the real
+reference library -- bytes and shapes; shape and SHA-256 for the one large case -- so that the GPU tests have something to equal on a
+machine where oracle/_ref was never built.  tests/test_shuffle_cpu.py::test_golden_is_the_real_reference checks the file against the
+reference wherever that exists.
+
+    python tools/make_golden_shuffle.py          (needs oracle/_ref/libtengine-lite.so)
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import shuffle_helpers as sh  # noqa: E402
+from oracle import ref_capi as ref  # noqa: E402
+
+
+def main():
+    assert ref.available(), "build the reference library first (oracle/build_ref.py)"
+    z = {}
+    for case, (dtype, build) in sorted(sh.gpu_cases().items()):
+        g, x = build()
+        z.update(sh.golden_entry(case, sh.reference_outputs(ref, g, x, dtype)))
+    np.savez_compressed(sh.GOLDEN, **z)
+    print(sh.GOLDEN, os.path.getsize(sh.GOLDEN), "bytes,", len(z), "arrays")
+
+
+if __name__ == "__main__":
+    main()
