@@ -83,6 +83,12 @@ enum {
      * shuffle_channel_ref.c), only the uint8 Split requantises byte to byte (tamd_split_table).  fp32 graphs keep them on the CPU device */
     TAMD_OP_SPLIT = 22,          /* param: tamd_split_param; the split_sizes form along the channel axis of a 4-D tensor */
     TAMD_OP_SHUFFLECHANNEL = 23, /* param: tamd_shufflechannel_param; a 4-D tensor, channels % group == 0, any batch */
+    /* 24: reserved, never supported */
+    /* the activation of MobileFaceNet and the ArcFace / RetinaFace family, int8 / uint8 graphs: no param; inputs [data, slope].  A 4-D
+     * data tensor; the slope is a constant TAMD_DT_FP16 tensor of one value per channel (uint8: or one value for all), which the
+     * reference widens with its own routine -- not IEEE: every exact power of two (0.25, 1, ...) widens to +0, so such a PReLU is a
+     * ReLU (tamd_prelu_slope).  prelu_ref.c:160-384; int8 saturates at +-127.  fp32 graphs keep the node on the CPU device */
+    TAMD_OP_PRELU = 25,
     TAMD_OP_NUM
 };
 
@@ -214,7 +220,8 @@ TAMD_API const char* tamd_last_error(void);
 TAMD_API const char* tamd_version(void);
 /* 1 if (op, dtype) can run on the device -- what allocator.describe publishes */
 TAMD_API int tamd_op_supported(int op, int dtype);
-/* 1 if this node with these parameters and tensors (descriptors only, const payloads are not read) is one the device
+/* 1 if this node with these parameters and tensors (descriptors only; the one const payload read, where it is given, is a PReLU's
+ * slope: a value that widens to inf or NaN is refused) is one the device
  * compiles; 0 -> leave it to the CPU device.  Replaces the per-op parameter tests a backend makes while it walks a
  * subgraph (source/device/cuda/cuda_executor.cc:72-134 fails Build() instead; tensorrt: trt_limit.hpp) */
 TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_desc* inputs, int input_num,
@@ -243,6 +250,17 @@ TAMD_API int tamd_interp_indices(int in_extent, int out_extent, float scale, int
  * table.  0, or -1 without a table */
 TAMD_API int tamd_shuffle_sources(int channels, int group, int* src);
 TAMD_API int tamd_split_table(float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
+/* the host truth of a quantised PReLU node (csrc/prelu_tables.cc; no GPU needed).
+ * tamd_prelu_slope: the float the reference makes of one fp16 slope (bit pattern), as its fp16_to_fp32 (source/utility/float.c) does
+ * on x86: normal halves with a non-zero fraction and infinities as IEEE; a normal half whose fraction is zero -- every exact power of
+ * two -- gives +0.0f; a sub-normal half gets its fraction in the low bits of the field (0x0003 -> 0x34000200); NaN gets fraction 1.
+ * tamd_prelu_table: table[b] = the output byte of one channel for input byte b (int8: b is the byte's bit pattern) with this slope
+ * between tensors of these quantisation parameters: MAX(x, 0) + slope * MIN(x, 0) in float, round(y / scale [+ zero]) saturated to
+ * +-127 (int8: -128 never comes out) or 0 .. 255 (uint8).  0, or -1 for a dtype other than int8 / uint8 and for a slope that widens
+ * to inf or NaN */
+TAMD_API float tamd_prelu_slope(unsigned short half_bits);
+TAMD_API int tamd_prelu_table(int dtype, unsigned short slope_bits, float in_scale, int in_zp, float out_scale, int out_zp,
+                              unsigned char table[256]);
 
 /* ---- graph construction: the plugin's pre_run walks `struct subgraph` (source/graph/subgraph.h, node.h:46-70,
  * tensor.h:43-102) and mirrors it through these calls, like CUDAEngine::Build does for its own IR

@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -89,6 +89,9 @@ def lib():
         L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
         L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        L.tamd_prelu_slope.argtypes = [C.c_ushort]
+        L.tamd_prelu_slope.restype = C.c_float
+        L.tamd_prelu_table.argtypes = [ci, C.c_ushort, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         _lib = L
     return _lib
 
@@ -96,6 +99,7 @@ def lib():
 OP_SIGMOID, OP_CLIP, OP_HARDSWISH, OP_MISH = 16, 17, 18, 19      # TAMD_OP_* of the byte-map operators
 OP_INTERP = 20
 OP_SPLIT, OP_SHUFFLECHANNEL = 22, 23
+OP_PRELU = 25          # (24: reserved, like 21)
 SPLIT_MAX = 8
 
 
@@ -113,6 +117,21 @@ def shuffle_sources(channels, group):
     src = (C.c_int * max(channels, 1))()
     rc = lib().tamd_shuffle_sources(channels, group, src)
     return None if rc != 0 else np.array(src[:channels], dtype=np.int32)
+
+
+def prelu_slope(half_bits):
+    """tamd_prelu_slope(): the float the reference makes of one fp16 slope (bit pattern) -- not IEEE: an exact power of two gives +0.0.
+    Needs no GPU."""
+    return float(lib().tamd_prelu_slope(int(half_bits) & 0xffff))
+
+
+def prelu_table(dtype, slope_bits, in_scale, in_zp, out_scale, out_zp):
+    """tamd_prelu_table(): the 256 output bytes (uint8 array, indexed by the input byte's bit pattern) of one channel of a PReLU node
+    whose fp16 slope has these bits, between tensors of these quantisation parameters; None for a type other than int8 / uint8 and for
+    a slope that widens to inf or NaN.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_prelu_table(dtype, int(slope_bits) & 0xffff, in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 
 
 def split_table(in_scale, in_zp, out_scale, out_zp):

@@ -254,6 +254,11 @@ int plan_interp(tamd_graph* g, HNode& n, Step* out);
 // Split's byte map uploaded.  The int8 forms are planned inside graph_plan.hip
 int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
 int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out);
+// a PReLU node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch (graph_plan.hip): the slopes widened (int8) or one byte table per
+// channel built (uint8) and uploaded, prelu_i8 / prelu_u8 (prelu.hip)
+int plan_prelu(tamd_graph* g, HNode& n, Step* out);
+// prelu_refusal (node_rules.h) asked of a node of this graph, payload included: validate_graph and plan_prelu
+const char* prelu_refusal_of(const tamd_graph* g, const HNode& n);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
 inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
 // .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of

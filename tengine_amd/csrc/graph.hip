@@ -81,6 +81,7 @@ int tamd_op_supported(int op, int dtype)
     if (is_lut_op(op)) return lut_op_on_device(op, dtype);         // byte maps by table: the quantised forms the reference has (which ranks: tamd_node_supported)
     if (op == TAMD_OP_INTERP) return interp_on_device(dtype);      // nearest, int8 / uint8 (which modes, sizes and ranks: tamd_node_supported)
     if (op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL) return chanmap_on_device(dtype);      // byte movers, int8 / uint8 (which forms: tamd_node_supported)
+    if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
     case TAMD_OP_ELTWISE: case TAMD_OP_CONCAT: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN:
@@ -209,6 +210,15 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         if (n_in < 1 || !in) return 0;
         if (shuffle_refusal((const tamd_shufflechannel_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
                             (size_t)out[0].quant_num))
+            return 0;
+        if (out[0].dim_num != 4) return 0;
+        for (int i = 0; i < 4; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
+        return 1;
+    }
+    case TAMD_OP_PRELU: {
+        if (n_in < 2 || !in) return 0;
+        if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
+                          in[1].ttype == TAMD_TT_CONST, elems(in[1]), in[1].data))
             return 0;
         if (out[0].dim_num != 4) return 0;
         for (int i = 0; i < 4; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;

@@ -941,6 +941,67 @@ int plan_lut(tamd_graph* g, HNode& n, Step* out)
     return 0;
 }
 
+const char* prelu_refusal_of(const tamd_graph* g, const HNode& n)
+{
+    if (n.in.size() != 2 || n.out.empty()) return "PReLU takes two inputs, the data and the slope";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& sl = g->tensors[n.in[1]];
+    const bool payload = sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && sl.data.size() == sl.elems() * 2;
+    if (sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && !payload) return "PReLU: the slope's payload does not match its shape";
+    return prelu_refusal(x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), g->tensors[n.out[0]].scales.size(),
+                         sl.dtype, sl.ttype == TAMD_TT_CONST, sl.elems(), payload ? sl.data.data() : nullptr);
+}
+
+// PReLU, int8 and uint8 graphs alike (graph_u8.hip calls this too).  What the reference computes per channel is prepared HERE, once, on
+// the host (prelu_tables.cc): int8 -- NHWC, 16 channels in a lane's 16 bytes -- gets the slopes widened to fp32 by tamd_prelu_slope and
+// zero-padded to the pixel stride; uint8 -- dense NCHW, one slope per plane -- gets one 256-byte table per channel (one in all for a
+// shared slope) from tamd_prelu_table.  Uploaded once; one launch of prelu.hip.  A concat view on either side is refused by name, as in
+// plan_lut: neither planner makes a PReLU's tensors views (plan_concat_views: slice_capable; plan_u8: in_place)
+int plan_prelu(tamd_graph* g, HNode& n, Step* out)
+{
+    const char* why = prelu_refusal_of(g, n);
+    if (why) { set_error("prelu %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const HTensor& sl = g->tensors[n.in[1]];
+    if (x.is_view || y.is_view) { set_error("prelu %s on a concat view is not supported", n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("prelu %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const unsigned short* half = (const unsigned short*)sl.data.data();
+    const size_t nslope = sl.elems();
+    const int C = x.dims[1];
+    if (x.dtype == TAMD_DT_INT8) {
+        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off || x.c != C || C > x.cs) {
+            set_error("prelu %s: input and output are not NHWC tensors of one pixel stride", n.name.c_str());
+            return -1;
+        }
+        std::vector<float> slope((size_t)x.cs, 0.f);
+        for (int c = 0; c < C; c++) slope[c] = tamd_prelu_slope(half[c]);
+        float* dslope = nullptr;
+        if (upload(g, slope, &dslope)) return -1;
+        PreluI8Args a{};
+        a.x = (const int8_t*)x.dptr; a.y = (int8_t*)y.dptr; a.count = (size_t)x.n * x.h * x.w * x.cs; a.C = C; a.cs = x.cs;
+        a.slope = dslope; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
+        *out = make_step(n.name, "prelu_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_i8(a, s); });
+    } else {
+        if (!x.nchw_raw || !y.nchw_raw) { set_error("prelu %s: input and output are not dense NCHW tensors", n.name.c_str()); return -1; }
+        const size_t ntab = nslope == 1 ? 1 : (size_t)C;
+        std::vector<unsigned> tables(ntab * 64);
+        for (size_t c = 0; c < ntab; c++)
+            if (tamd_prelu_table(x.dtype, half[c], x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)(tables.data() + c * 64))) {
+                set_error("prelu %s: PReLU: a slope widens to inf or NaN", n.name.c_str());
+                return -1;
+            }
+        unsigned* dtables = nullptr;
+        if (upload(g, tables, &dtables)) return -1;
+        PreluU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.planes = (long)x.dims[0] * C; a.C = C; a.HW = x.dims[2] * x.dims[3];
+        a.tables = dtables; a.shared = nslope == 1 ? 1 : 0;
+        *out = make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); });
+    }
+    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
+    return 0;
+}
+
 // Nearest Interp, int8 and uint8 graphs alike (graph_u8.hip calls this too).  Everything the reference computes for the node is done
 // HERE, once: the scales and the output size (interp_resolve), the source row of every output row and the source column of every
 // output column (tamd_interp_indices), the byte map between the two tensors' quantisation parameters (tamd_interp_table) -- uploaded,
@@ -1316,6 +1377,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &one.step))) g->steps.push_back(one.step); break;
         case TAMD_OP_SPLIT: r = plan_split(g, L, n); break;
         case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n); break;
+        case TAMD_OP_PRELU: if (!(r = plan_prelu(g, n, &one.step))) g->steps.push_back(one.step); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

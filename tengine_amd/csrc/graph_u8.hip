@@ -901,6 +901,11 @@ int plan_u8(tamd_graph* g)
             if (!(rc = plan_shuffle_u8(g, n, &st))) out.push_back(st);
             break;
         }
+        case TAMD_OP_PRELU: {                   // one byte table per channel at prerun, one launch (graph_plan.hip: plan_prelu)
+            Step st;
+            if (!(rc = plan_prelu(g, n, &st))) out.push_back(st);
+            break;
+        }
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;

@@ -348,6 +348,23 @@ struct ChanMapU8Args {
     int identity;
 };
 
+// PReLU of a quantised graph (prelu.hip; the host truth: prelu_tables.cc)
+struct PreluI8Args {       // NHWC int8, x and y of one pixel stride: y = requant(x < 0 ? x * slope[c] : x), the chain of relu_i8 per channel
+    const int8_t* x; int8_t* y;
+    size_t count;          // N * H * W * cs bytes
+    int C, cs;             // cs (a multiple of 16) bytes per pixel, C of them channels; the padding lanes [C, cs) are written 0
+    const float* slope;    // [cs]: tamd_prelu_slope of every channel's fp16 slope, zeros behind C; 16-byte aligned
+    float in_scale, out_scale;
+};
+
+struct PreluU8Args {       // dense NCHW uint8: plane p = n * C + c of HW bytes is mapped through the byte table of channel c
+    const uint8_t* x; uint8_t* y;      // both 16-byte aligned, so a plane starts at the same offset in its 16 bytes on either side
+    long planes;           // N * C
+    int C, HW;
+    const unsigned* tables;// [C][64] (shared: [1][64]): tamd_prelu_table's 256 bytes of every channel as they lie
+    int shared;            // one slope, one table, for every channel
+};
+
 struct SoftmaxI8Args {     // softmax over ONE axis of an int8 tensor: the channels of an NHWC tensor (a view's channel slice included), or --
                            // round 6 -- any axis of a dense (reference-order) or NHWC tensor
     const int8_t* x; int8_t* y;
@@ -470,6 +487,8 @@ hipError_t launch_interp_u8(const InterpU8Args& a, hipStream_t s);
 hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s);
 hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
+hipError_t launch_prelu_i8(const PreluI8Args& a, hipStream_t s);
+hipError_t launch_prelu_u8(const PreluU8Args& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);
 hipError_t launch_concat_copy_i8(const CatCopyArgs& a, hipStream_t s);
 hipError_t launch_flatcat_i8(const FlatCatI8Args& a, hipStream_t s);

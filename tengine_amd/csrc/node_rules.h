@@ -8,6 +8,7 @@
 #include "chanmap_tables.h"
 #include "interp_tables.h"
 #include "lut_tables.h"
+#include "prelu_tables.h"
 
 namespace tamd {
 
@@ -101,6 +102,32 @@ inline const char* shuffle_refusal(const tamd_shufflechannel_param* p, int dtype
     if (in_dim_num != 4 || in_const) return "ShuffleChannel takes a 4-D tensor that is not a constant";
     if (p->group < 1 || in_dims[1] < 1 || in_dims[1] % p->group != 0) return "ShuffleChannel: the group count must divide the channels";
     if (in_quant != 1 || out_quant != 1) return "ShuffleChannel needs per-tensor quant params on both sides";
+    return nullptr;
+}
+
+// PReLU: the two quantised kernels of the reference (prelu_ref.c; prelu.hip).  fp32 graphs keep the node on the CPU device
+inline bool prelu_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// One PReLU node: nullptr when the device runs it, else the reason.  input_num: the node's inputs ([data, slope]); slope_data: the
+// slope's payload where the caller has it (a support query may not), slope_elems values.
+//  - 4-D only: ref_prelu_int8 reads dims[0..3] whatever the rank, and the uint8 3-D per-channel loop (`for (j = 0; j < c; c++)`)
+//    never ends; 2-D stays out with them
+//  - int8: the kernel indexes slope[c] unconditionally and reads past a one-element slope; uint8: one element is the shared slope
+//  - the slope is widened by tamd_prelu_slope; a NaN would reach the reference's (int) conversion -- refused, and the kernels are free
+//    of that case
+inline const char* prelu_refusal(int dtype, int input_num, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, size_t out_quant, int slope_dtype,
+                                 bool slope_const, size_t slope_elems, const void* slope_data)
+{
+    if (!prelu_on_device(dtype)) return "PReLU runs on the device in int8 and uint8 graphs only";
+    if (input_num != 2) return "PReLU takes two inputs, the data and the slope";
+    if (in_const) return "PReLU: the data tensor must not be a constant";
+    if (in_dim_num != 4) return "PReLU runs on the device on a 4-D tensor only";
+    if (in_quant != 1) return "PReLU needs per-tensor quant params on its input";
+    if (out_quant != 1) return "PReLU needs per-tensor quant params on its output";
+    if (!slope_const) return "PReLU: the slope must be a constant";
+    if (slope_dtype != TAMD_DT_FP16) return "PReLU: the slope of a quantised graph must be fp16";
+    if (dtype == TAMD_DT_INT8 && slope_elems != (size_t)in_dims[1]) return "an int8 PReLU needs one slope per channel";
+    if (dtype == TAMD_DT_UINT8 && slope_elems != (size_t)in_dims[1] && slope_elems != 1) return "a uint8 PReLU needs one slope per channel, or one for all";
+    if (slope_data && !prelu_slopes_finite((const unsigned short*)slope_data, slope_elems)) return "PReLU: a slope widens to inf or NaN";
     return nullptr;
 }
 

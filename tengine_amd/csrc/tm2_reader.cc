@@ -70,6 +70,7 @@ int map_op(uint32_t t)
     case 12: return TAMD_OP_INPUT;
     case 15: return TAMD_OP_PERMUTE;
     case 16: return TAMD_OP_POOL;
+    case 17: return TAMD_OP_PRELU;                     // TM2_OPTYPE_PRELU: no parameter blob; inputs [data, slope]
     case 18: return TAMD_OP_PRIORBOX;
     case 20: return TAMD_OP_RELU;
     case 21: return TAMD_OP_RELU6;

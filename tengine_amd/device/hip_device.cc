@@ -92,6 +92,9 @@ const OpRow kOps[] = {
     // the channel movers of a ShuffleNet unit: byte copies in the quantised kernels of the reference (csrc/chanmap.hip).  An fp32 graph
     // keeps both on the CPU device (which Split forms: tamd_node_supported; the caffe Slice of the benchmark file is another operator)
     {OP_SPLIT, TAMD_OP_SPLIT, true},        {OP_SHUFFLECHANNEL, TAMD_OP_SHUFFLECHANNEL, true},
+    // the activation of the face models (csrc/prelu.hip): the two quantised kernels of the reference; its fp16 slope constant travels
+    // like any constant.  An fp32 graph keeps the node on the CPU device (which ranks and slopes: tamd_node_supported)
+    {OP_PRELU, TAMD_OP_PRELU, true},
 };
 
 const OpRow* find_op(int op)
@@ -132,7 +135,7 @@ bool translate_priorbox(const struct priorbox_param* p, tamd_priorbox_param* q)
 }
 
 // descriptor of an IR tensor.  with_payload: the constant's bytes and the quantisation values travel too (pre_run); without, shapes
-// and the quantisation form alone (tamd_node_supported looks at nothing else).  The pointers stay the IR tensor's own.
+// and the quantisation form alone (tamd_node_supported looks at nothing else, but for a PReLU's slope).  The pointers stay the IR tensor's own.
 tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 {
     tamd_tensor_desc d;
@@ -504,7 +507,8 @@ static bool node_supported(struct graph* ir, struct node* n)
     if (op < 0) return false;
     if (op == TAMD_OP_INPUT || op == TAMD_OP_CONST) return true;
     std::vector<tamd_tensor_desc> in, out;
-    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), false));
+    // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device)
+    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), op == TAMD_OP_PRELU && k == 1));
     for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), false));
     NodeParams params;
     std::vector<int> ii(in.size()), oi(out.size());

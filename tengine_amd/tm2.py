@@ -30,6 +30,7 @@ OPTYPE = {
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Clip": 87, "Mish": 97,
+    "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
 
@@ -136,7 +137,7 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<i2f2i", p["resize_type"], p.get("width_scale", 0.0), p.get("height_scale", 0.0), p.get("output_width", 0), p.get("output_height", 0))
     if op == "ShuffleChannel":   # TM2_ShuffleChannelParam {group}
         return struct.pack("<i", p["group"])
-    if op in ("Const", "InputOp", "Dropout", "ReLU6", "Sigmoid", "Mish"):
+    if op in ("Const", "InputOp", "Dropout", "ReLU6", "Sigmoid", "Mish", "PReLU"):
         return None
     raise NotImplementedError("tm2 writer: op %s" % op)
 
