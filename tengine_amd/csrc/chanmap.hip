@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "epilogue.h"       // fix128_4
 #include "kernels.h"
 
 namespace tamd {
@@ -61,13 +62,6 @@ hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s)
 // ShuffleChannel(2)).  Output channel 2j is a[j], 2j + 1 is b[j], so output vector v is the byte interleave of a[8v .. 8v + 7] and
 // b[8v .. 8v + 7]: two 8-byte loads, four byte permutes, one 16-byte store -- no table.  Bytes behind channel `half` are zero (the
 // padding lanes).  Its results are chan_map_i8's (tests/test_gpu_shuffle.py runs both forms on the same graphs).
-__device__ __forceinline__ unsigned fix128_4(unsigned x)
-{
-    const unsigned t = x ^ 0x80808080u;                                  // a zero byte where x holds 0x80
-    const unsigned z = ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu);      // 0x80 in exactly those bytes
-    return x - (z >> 7);                                                 // 0x80 -> 0x7f, no borrow out of the byte
-}
-
 __global__ __launch_bounds__(256) void chan_map_i8_g2_kernel(ChanMapG2Args a)
 {
     const unsigned nv = (unsigned)(2 * a.half + 15) / 16;

@@ -107,6 +107,16 @@ __device__ __forceinline__ unsigned pack4(int a, int b, int c, int d)
     return (unsigned)(a & 0xff) | ((unsigned)(b & 0xff) << 8) | ((unsigned)(c & 0xff) << 16) | ((unsigned)(d & 0xff) << 24);
 }
 
+// four bytes at once: 0x80 -> 0x7f, every other byte as it is.  What the reference's int8 Concat of several inputs makes of -128 even
+// between equal scales (concat_kernel_ref_int8.c:83-84 clamps below -127 to PLUS 127): a launch that writes into such a Concat's
+// buffer, or maps channels through one, stores the bytes the Concat's copy would have (chanmap.hip, misc_kernels.hip: upsample_i8)
+__device__ __forceinline__ unsigned fix128_4(unsigned x)
+{
+    const unsigned t = x ^ 0x80808080u;                                  // a zero byte where x holds 0x80
+    const unsigned z = ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu);      // 0x80 in exactly those bytes
+    return x - (z >> 7);                                                 // 0x80 -> 0x7f, no borrow out of the byte
+}
+
 // the hand-over path of requant4 (a wave takes it for ~1.5 % of its groups): the reference chain for the flagged slots.  Kept
 // OUT of line: inlined, its ~60 instructions at each of the 16+ call sites of a GEMM epilogue push the epilogue past the
 // unroller's size budget, the accumulator arrays then get dynamic indices and land in scratch memory.  Everything by value.

@@ -269,7 +269,8 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP; }
 // .. and on the side they read alone.  Split and ShuffleChannel are NOT written in place into a Concat's buffer: they hand on the byte
 // -128 where their input holds it, and the reference's Concat of several inputs turns that byte into 127 even between equal scales
-// (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not
+// (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not.  Upsample holds that byte too and IS written in
+// place: its launch stores 127 for it, where the Concat is its only reader (plan_concat_views, plan_upsample)
 static bool reads_slices(int op) { return slice_capable(op) || op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL; }
 
 static int plan_concat_views(tamd_graph* g, I8Layout& L)
@@ -294,6 +295,12 @@ static int plan_concat_views(tamd_graph* g, I8Layout& L)
             int readers = 0;
             for (int ci : n.in) readers += (ci == i);
             if (readers > 1) ok = false;        // the same tensor twice: one copy per position
+            // an Upsample hands on the byte -128 and can emit it (misc_kernels.hip: upsample_i8 runs the reference's uint8 routine on the
+            // bytes), and a Concat of several inputs stores 127 for it.  In place, the Upsample's launch stores 127 itself
+            // (UpsampleI8Args::fix128) -- which is what the Concat's readers must see and NOT what another reader of the Upsample's own
+            // tensor must see: with a second reader it keeps its buffer and concat_copy_i8 copies.  (Conv, FC, Pool and Interp
+            // saturate at +-127 and never hold the byte.)
+            if (producer_op(i) == TAMD_OP_UPSAMPLE && n.in.size() > 1 && count_consumers(g, i) > 1) ok = false;
             if (ok) { L.view_of[i] = n.out[0]; L.view_off[i] = off; }
             off += x.c;
         }
@@ -1276,6 +1283,13 @@ static int plan_upsample(tamd_graph* g, HNode& n)
     a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
     a.in_zp = x.zps.empty() ? 0 : x.zps[0]; a.out_zp = y.zps.empty() ? 0 : y.zps[0];
     a.copy = a.in_scale == a.out_scale && a.in_zp == a.out_zp;
+    // written in place of a Concat's copy: that copy turns -128 into 127 when the Concat has several inputs (a single input is copied
+    // byte for byte, concat_kernel_ref_int8.c:47-57), so the launch does.  plan_concat_views makes such an output a view only where the
+    // Concat is its one reader: anyone else reads the Upsample's own bytes, -128 included.  (A Concat's output is never a view itself.)
+    if (y.is_view)
+        for (auto& c : g->nodes)
+            if (c.op == TAMD_OP_CONCAT && c.in.size() > 1 && std::find(c.in.begin(), c.in.end(), n.out[0]) != c.in.end() && g->tensors[c.out[0]].dptr == y.dptr)
+                a.fix128 = 1;
     Step st = make_step(n.name, "upsample_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_upsample_i8(a, s); });
     g->steps.push_back(st);
     return 0;

@@ -256,6 +256,7 @@ struct UpsampleI8Args {    // nearest upsample by an integer factor, NHWC int8: 
     float in_scale, out_scale;
     int in_zp, out_zp;
     int copy;              // equal scales and zero points: the byte map is the identity
+    int fix128;            // 1: the output is a view of a Concat of several inputs, whose copy stores 127 for the byte -128 (epilogue.h: fix128_4)
 };
 
 struct FirstPoolArgs {     // the stem in one launch: FirstArgs' convolution (7 x KW, stride 2, C = 3) + MAX pool 3x3 / 2 / pad 0 (conv_first_pool.hip)

@@ -186,6 +186,8 @@ hipError_t launch_relu_pool(const ReluPoolArgs& a, hipStream_t s)
 // clamp 0 .. 255, stored into the int8 tensor (zero points are 0 for int8; a negative input does NOT come out as a signed rescale
 // would give it).  Source pixel = (int)(out / scale).  Byte 0 -> 0: zero channel padding stays zero.  One lane per input pixel and
 // 16-byte channel vector: read once, mapped once, stored to its scale x scale output pixels.  COPY: equal scales and zero points.
+// Both forms can hold the byte 0x80 (COPY hands it on, the map emits it for whatever rounds to 128); fix128: the output lies in the
+// buffer of a Concat of several inputs, which would have stored 0x7f for it.
 template <bool COPY>
 __global__ __launch_bounds__(256) void upsample_i8_kernel(UpsampleI8Args a)
 {
@@ -215,6 +217,7 @@ __global__ __launch_bounds__(256) void upsample_i8_kernel(UpsampleI8Args a)
         }
         d = make_uint4(p[0], p[1], p[2], p[3]);
     }
+    if (a.fix128) { d.x = fix128_4(d.x); d.y = fix128_4(d.y); d.z = fix128_4(d.z); d.w = fix128_4(d.w); }
     const int OW = a.W * a.scale;
     int8_t* y0 = a.y + (((size_t)n * a.H * a.scale + (size_t)iy * a.scale) * OW + (size_t)ix * a.scale) * a.ldc + a.c_off + v * 16;
     for (int dy = 0; dy < a.scale; dy++)
