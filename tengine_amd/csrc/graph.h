@@ -80,8 +80,9 @@ struct Step {                  // one device launch of the compiled plan
     std::function<hipError_t(hipStream_t)> fn;
     bool once = false;         // every input is a prerun constant (PriorBox outputs): launched once at the end of prerun
     // rd / wr list EVERYTHING the step's launch reads / writes in device memory that another step may write (constants left
-    // out) -- only then is deps set, and only a step with deps may run beside its predecessors (graph_exec.hip run_steps).  A step may
-    // list them without deps: the int8 planner refuses a launch whose wr overlaps its rd (graph_plan.hip plan_i8)
+    // out) -- only then is deps set, and only a step with deps may run beside its predecessors (graph_exec.hip run_steps).  Every
+    // compute step of an int8 graph lists them, most without deps (they stay ordered): plan_i8 refuses a step that states nothing
+    // and one whose wr overlaps its rd (graph_plan.hip)
     bool deps = false;
     std::vector<Access> rd, wr;
 };
@@ -91,10 +92,23 @@ inline bool step_conflict(const Step& a, const Step& b)          // RAW, WAR or 
     for (auto& r : a.rd) for (auto& x : b.wr) if (access_overlap(r, x)) return true;
     return false;
 }
-inline Step make_step(const std::string& node, const std::string& kernel, double macs, double bytes, std::function<hipError_t(hipStream_t)> fn)
+inline bool step_states_nothing(const Step& s) { return s.rd.empty() || s.wr.empty(); }
+inline bool step_writes_what_it_reads(const Step& s)             // any write against any read of the SAME launch
+{
+    for (auto& w : s.wr)
+        for (auto& r : s.rd)
+            if (access_overlap(w, r)) return true;
+    return false;
+}
+// The one way to make a step: what the profile shows of it (node, kernel, macs, bytes), the launch, and what that launch reads and
+// writes (rd / wr, see Step).  deps: the lists are complete AND the step may run beside its predecessors.  Without deps the lists change
+// nothing at run time -- run_steps reads them only behind deps, the step stays ordered -- they are what plan_i8's check reads
+inline Step make_step(const std::string& node, const std::string& kernel, double macs, double bytes, std::function<hipError_t(hipStream_t)> fn,
+                      std::vector<Access> rd = {}, std::vector<Access> wr = {}, bool deps = false)
 {
     Step st;
     st.node = node; st.kernel = kernel; st.macs = macs; st.bytes = bytes; st.fn = std::move(fn);
+    st.rd = std::move(rd); st.wr = std::move(wr); st.deps = deps;
     return st;
 }
 inline Access access_of(const HTensor& t)                         // dense tensor, or the channel slice of the concat buffer it lives in
@@ -114,6 +128,17 @@ inline Access access_of(const HTensor& t)                         // dense tenso
         if (t.is_view) { a.period = (size_t)t.cs; a.off = (size_t)t.c_off; a.len = (size_t)t.c; }
         else a.len = a.size;
     }
+    return a;
+}
+
+// channels [first, first + count) of every pixel of the NHWC int8 buffer that `t` lives in, counted from t's own first channel: what
+// access_of cannot say of a tensor that is no view (a concat input's slot of the concat's buffer)
+inline Access access_of_channels(const HTensor& t, int first, int count)
+{
+    Access a;
+    a.base = (const char*)t.dptr;
+    a.size = (size_t)t.n * t.h * t.w * t.cs;
+    a.period = (size_t)t.cs; a.off = (size_t)(t.c_off + first); a.len = (size_t)count;
     return a;
 }
 

@@ -1,9 +1,11 @@
-// What the translation units of the graph layer share (private).  Since round 6 the layer is six units instead of one:
+// What the translation units of the graph layer share (private).  Since round 6 the layer is eight units instead of one:
 //   graph.hip             the C ABI that builds, describes, pre-runs, profiles, reads and destroys a graph
 //   graph_infer.hip       shape inference, validation, the PriorBox evaluator, the error string
-//   graph_plan.hip        the int8 planner (arena, layout passes, one function per node kind, plan_i8)
+//   graph_plan.hip        the int8 planner (arena, layout passes, one function per node kind, plan_i8: the one place that appends a
+//                         launch and checks what it says it reads and writes) and the node planners that plan_u8 shares (byte maps by
+//                         table, PReLU, nearest Interp, Split / ShuffleChannel)
 //   graph_plan_conv.hip   .. its convolution / FC / pooling launches (requantisation folds, packers, one function per conv form)
-//   graph_plan_pairs.hip  .. its pair fusions (pwdw, dwpw) and the bottleneck-block fusion; graph_plan.h is what those three share
+//   graph_plan_pairs.hip  .. its fusions (pwdw, chain4, dwpw, the bottleneck block); graph_plan.h is what those three share
 //   plan_cache.hip        TAMD_PLAN_CACHE
 //   graph_pair.hip        a batched graph as two half-batch graphs side by side behind one handle (tamd_options.split_batch)
 //   graph_exec.hip        run_steps, the direct path's self-checks, zero-copy lists, the run-side entry points

@@ -1,7 +1,8 @@
 // What the three units of the int8 planner share (graph_plan.hip, graph_plan_conv.hip, graph_plan_pairs.hip); private.
 // Planned launches are values (Planned): a fuser is handed the launches of the nodes it covers, reads the constants they folded and
 // uploaded out of their kernel arguments, and builds its one launch with fused_step.  The rules every fuser shares are stated once
-// here: sole_reader (the one node behind a tensor), fused_step / reads_writes (the step of a launch that covers several nodes).
+// here: sole_reader (the one node behind a tensor), fused_step (the step of a launch that covers several nodes).  Every step says what
+// its launch reads and writes (graph.h: make_step); node functions hand their launches back and plan_i8 alone appends them.
 #pragma once
 #include <initializer_list>
 
@@ -60,18 +61,13 @@ inline int sole_reader(const tamd_graph* g, int tensor)
     return -1;
 }
 
-// all a launch touches in device memory besides constants: it reads x and writes y.  plan_i8 checks that the two do not overlap; `deps`:
-// the step may also run beside its predecessors (Step::deps)
-inline void reads_writes(Step& st, const HTensor& x, const HTensor& y, bool deps = true)
-{
-    st.rd.push_back(access_of(x)); st.wr.push_back(access_of(y)); st.deps = deps;
-}
-
 // the one launch for the planned launches `parts`: their node names joined by '+', their macs and bytes summed (SURVEY 8(d) accounting,
-// per layer: the intermediate tensors still count as algorithmic bytes)
-inline Step fused_step(std::initializer_list<const Planned*> parts, const std::string& kernel, std::function<hipError_t(hipStream_t)> fn)
+// per layer: the intermediate tensors still count as algorithmic bytes).  It reads x and writes y, nothing else besides constants;
+// deps: as make_step
+inline Step fused_step(std::initializer_list<const Planned*> parts, const std::string& kernel, std::function<hipError_t(hipStream_t)> fn, const HTensor& x,
+                       const HTensor& y, bool deps)
 {
-    Step st = make_step("", kernel, 0, 0, std::move(fn));
+    Step st = make_step("", kernel, 0, 0, std::move(fn), {access_of(x)}, {access_of(y)}, deps);
     for (const Planned* p : parts) {
         st.node += (p == *parts.begin() ? "" : "+") + p->step.node;
         st.macs += p->step.macs; st.bytes += p->step.bytes;

@@ -168,9 +168,11 @@ struct I8Layout {
     std::vector<char> fused, has_fuse;
     std::vector<FusedElt> fuse_at;
     std::vector<int> cat_shuffle;
+    // in_multi_cat[tensor]: written in place into the buffer of a Concat with SEVERAL inputs (plan_concat_views; plan_upsample: fix128)
+    std::vector<char> in_multi_cat;
     I8Layout(size_t nt, size_t nn)
         : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn),
-          cat_shuffle(nn, 0) {}
+          cat_shuffle(nn, 0), in_multi_cat(nt, 0) {}
 };
 
 // ---- DENSE tensors (the SSD head plumbing of an int8 graph).  The convolution stack lives in NHWC buffers
@@ -301,7 +303,7 @@ static int plan_concat_views(tamd_graph* g, I8Layout& L)
             // tensor must see: with a second reader it keeps its buffer and concat_copy_i8 copies.  (Conv, FC, Pool and Interp
             // saturate at +-127 and never hold the byte.)
             if (producer_op(i) == TAMD_OP_UPSAMPLE && n.in.size() > 1 && count_consumers(g, i) > 1) ok = false;
-            if (ok) { L.view_of[i] = n.out[0]; L.view_off[i] = off; }
+            if (ok) { L.view_of[i] = n.out[0]; L.view_off[i] = off; L.in_multi_cat[i] = n.in.size() > 1; }
             off += x.c;
         }
     }
@@ -493,14 +495,13 @@ static int resolve_views(tamd_graph* g, I8Layout& L)
                 t.dptr = o.dptr; t.cs = o.cs; t.c_off = o.c_off; t.is_view = o.is_view;
             }
         }
-    // input layout steps
+    // input layout steps.  in_steps / out_steps state no accesses and are outside plan_i8's check: they move a graph input / output
+    // between its staging buffer and its own NHWC buffer, and neither is ever shared (plan_buffers: pinned)
     for (auto& io : g->inputs) {
         HTensor& t = g->tensors[io.tensor];
         if (t.nchw_raw) continue;
         LayoutArgs a{io.stage, t.dptr, t.n, t.c, t.h, t.w, t.cs, esize(t.dtype)};
-        Step st; st.node = t.name; st.kernel = "nchw_to_nhwc";
-        st.fn = [a](hipStream_t s) { return launch_nchw_to_nhwc(a, s); };
-        g->in_steps.push_back(st);
+        g->in_steps.push_back(make_step(t.name, "nchw_to_nhwc", 0, 0, [a](hipStream_t s) { return launch_nchw_to_nhwc(a, s); }));
     }
     return 0;
 }
@@ -543,31 +544,29 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
 
 // Permute(0, 2, 3, 1) and Reshape of a convolution-stack tensor: one copy into the reference's dense element order, the source read
 // as flatcat_i8 kind 1 (permuted) | 2 (NCHW)
-static void push_dense_copy(tamd_graph* g, HNode& n, int kind, const char* kernel)
+static Step dense_copy(tamd_graph* g, HNode& n, int kind, const char* kernel)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
     FlatCatI8Args a{};
     a.nsrc = 1; a.y = (int8_t*)y.dptr; a.outer = x.n; a.out_row = x.c * x.h * x.w; a.row_begin = 0; a.row_len = a.out_row;
     a.src[0] = FlatCatI8Src{(const int8_t*)x.dptr + x.c_off, kind, a.out_row, x.c, x.h * x.w, x.cs, 0, 1.f, 1};
-    Step st; st.node = n.name; st.kernel = kernel; st.bytes = 2.0 * x.elems();
-    st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
-    g->steps.push_back(st);
+    return make_step(n.name, kernel, 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, {access_of(x)}, {access_of(y)});
 }
 
 // permute_ref.c:305-343, order (0, 2, 3, 1): a byte permutation -- written only when somebody reads it
-static int plan_permute(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_permute(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     if (L.perm_src[n.out[0]] >= 0) g->fused_away[n.out[0]] = 1;         // its Concat reads the NHWC buffer itself
-    else push_dense_copy(g, n, 1, "permute_i8");
+    else out->push_back(dense_copy(g, n, 1, "permute_i8"));
     return 0;
 }
 
 // reshape_ref.c:76-90 (NCHW): the same bytes under another shape
-static int plan_reshape(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_reshape(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     if (L.alias_of[n.out[0]] >= 0) { if (L.perm_src[n.out[0]] >= 0) g->fused_away[n.out[0]] = 1; }     // dense input: a view
-    else push_dense_copy(g, n, 2, "reshape_i8");      // convolution-stack input: its NCHW element order, written once
+    else out->push_back(dense_copy(g, n, 2, "reshape_i8"));      // convolution-stack input: its NCHW element order, written once
     return 0;
 }
 
@@ -589,7 +588,7 @@ static int plan_priorbox(tamd_graph* g, HNode& n)
     return 0;
 }
 
-static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& y = g->tensors[n.out[0]];
     // dense output: for every index in front of the axis each input is one contiguous run of the output's run; up to
@@ -606,7 +605,9 @@ static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n)
     for (size_t k0 = 0; k0 < n.in.size(); k0 += kFlatCatMax) {
         FlatCatI8Args a{};
         a.y = (int8_t*)y.dptr; a.outer = outer; a.out_row = out_row; a.row_begin = begin;
-        Step st; st.node = n.name; st.kernel = "flatcat_i8"; st.once = all_const;
+        const char* kernel = "flatcat_i8";
+        double bytes = 0;
+        std::vector<Access> reads;                                     // every source as the launch actually reads it
         for (size_t k = k0; k < std::min(n.in.size(), k0 + (size_t)kFlatCatMax); k++) {
             HTensor& x = g->tensors[n.in[k]];
             if (x.dtype != y.dtype || x.scales.empty()) { set_error("concat %s: input %s: dtype / quant params", n.name.c_str(), x.name.c_str()); return -1; }
@@ -618,27 +619,30 @@ static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n)
                 HTensor& p = g->tensors[L.perm_src[n.in[k]]];
                 s.x = (const int8_t*)p.dptr + p.c_off; s.kind = 1; s.C = p.c; s.HW = p.h * p.w; s.cs = p.cs; s.chunk = p.c * p.h * p.w;
                 if (p.n != outer) { set_error("concat %s: a permuted input on axis %d", n.name.c_str(), ax); return -1; }
-                st.kernel = "permute_concat_i8";
+                kernel = "permute_concat_i8";
+                reads.push_back(access_of(p));                          // (the NHWC tensor, not its never-written permuted form)
             } else if (L.dense[n.in[k]]) {
                 s.x = (const int8_t*)x.dptr; s.kind = 0; s.chunk = (int)(x.dims[ax] * inner);
+                reads.push_back(access_of(x));
             } else {                                                   // a convolution-stack tensor, read in NCHW element order
                 s.x = (const int8_t*)x.dptr + x.c_off; s.kind = 2; s.C = x.c; s.HW = x.h * x.w; s.cs = x.cs;
                 s.chunk = (int)((size_t)x.n * x.c * x.h * x.w / (size_t)outer);
+                reads.push_back(access_of(x));
             }
             a.src[a.nsrc++] = s;
             begin += s.chunk;
-            st.bytes += 2.0 * outer * s.chunk;
+            bytes += 2.0 * outer * s.chunk;
         }
         a.row_len = begin - a.row_begin;
-        st.fn = [a](hipStream_t s) { return launch_flatcat_i8(a, s); };
-        g->steps.push_back(st);
+        out->push_back(make_step(n.name, kernel, 0, bytes, [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, reads, {access_of(y)}));
+        out->back().once = all_const;
     }
     if (begin != out_row) { set_error("concat %s: the inputs do not add up to the output", n.name.c_str()); return -1; }
     y.prerun_const = all_const;
     return 0;
 }
 
-static int plan_channel_concat(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_channel_concat(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& y = g->tensors[n.out[0]];
     int off = 0;
@@ -651,9 +655,9 @@ static int plan_channel_concat(tamd_graph* g, I8Layout& L, HNode& n)
             volatile float rs = x.scales[0] / y.scales[0];      // concat_kernel_ref_int8.c:70: rescale = in_scale / out_scale
             a.rescale = rs;
             a.identity = n.in.size() == 1;                      // :47-57: a single input is copied as it is
-            Step st; st.node = n.name; st.kernel = "concat_copy_i8"; st.bytes = 2.0 * a.pixels * x.c;
-            st.fn = [a](hipStream_t s) { return launch_concat_copy_i8(a, s); };
-            g->steps.push_back(st);
+            // writes this input's slot of the output's pixels alone: the slots beside it may be views that are read here
+            out->push_back(make_step(n.name, "concat_copy_i8", 0, 2.0 * a.pixels * x.c, [a](hipStream_t s) { return launch_concat_copy_i8(a, s); }, {access_of(x)},
+                                     {access_of_channels(y, off, x.c)}));
         }
         off += x.c;
     }
@@ -666,8 +670,7 @@ static int fuse_stem(tamd_graph* g, HNode& conv, HNode& pool, const Planned& c, 
 {
     if (c.kind != Planned::FIRST || !conv_first_pool_applicable(c.first, p.pool)) return 0;
     const FirstPoolArgs fa = conv_first_pool_args(c.first, p.pool);
-    *fused = fused_step({&c, &p}, "conv_first_pool_i8", [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); });
-    reads_writes(*fused, g->tensors[conv.in[0]], g->tensors[pool.out[0]]);
+    *fused = fused_step({&c, &p}, "conv_first_pool_i8", [fa](hipStream_t s) { return launch_conv_first_pool(fa, s); }, g->tensors[conv.in[0]], g->tensors[pool.out[0]], true);
     g->fused_away[conv.out[0]] = 1;
     return 1;
 }
@@ -701,12 +704,12 @@ static int try_dwpw(tamd_graph* g, I8Layout& L, size_t dwi, const Planned& pd, S
 // output feeds exactly one convolution that carries an eltwise SUM tail (scan_eltwise_fusion) with ni's INPUT as the other operand;
 // neither intermediate is a view or a graph output (count_consumers counts those).  The three are planned here, the later two ahead
 // of their node order (each reads only what is written by then), and either become one launch (plan_block) or are pushed as
-// planned.  1: pushed, 0: not such a block (nothing planned), -1: error.
+// planned.  1: handed back in *out, 0: not such a block (nothing planned), -1: error.
 // Where the block fuses, plan_conv has uploaded each convolution's GEMM-family weight panel and run its plan-time race although only
 // its bias and requantisation vectors are read by the fused launch: dead device memory (res2: 3 x 68 KB), prerun time, and possibly
 // plan-cache entries for launches that never run -- try_dwpw's known waste, kept for the same reason (one plan_conv, no second path
 // that folds a requantisation).  The switch and the match on the eltwise tail are tested here only; plan_block takes what it is given.
-static int try_block(tamd_graph* g, I8Layout& L, size_t ni)
+static int try_block(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
     if (!fuse_block_enabled()) return 0;
     HNode& na = g->nodes[ni];
@@ -731,19 +734,19 @@ static int try_block(tamd_graph* g, I8Layout& L, size_t ni)
     Step st;
     const int took = plan_block(g, na, g->nodes[ib], g->nodes[ic], L.fuse_at[ic], a, b, c, &st);
     if (took < 0) return -1;
-    if (took) g->steps.push_back(st);
-    else { g->steps.push_back(a.step); g->steps.push_back(b.step); g->steps.push_back(c.step); }
+    if (took) out->push_back(st);
+    else out->insert(out->end(), {a.step, b.step, c.step});
     return 1;
 }
 
 // A convolution node and its fusions: the bottleneck block (opt-in), then the three pairings conv + pool (stem), pointwise + its tail
-// (pwdw; two adjacent ones as a chain of four: chain4), depthwise + pointwise (dwpw).  Each plans the launches involved as values and pushes either the fused launch or the
+// (pwdw; two adjacent ones as a chain of four: chain4), depthwise + pointwise (dwpw).  Each plans the launches involved as values and hands back either the fused launch or the
 // planned ones.
-static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
+static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
     HNode& n = g->nodes[ni];
     Step st;
-    const int blk = try_block(g, L, ni);
+    const int blk = try_block(g, L, ni, out);
     if (blk) return blk < 0 ? -1 : 0;
     // stem (TAMD_FIRST_POOL=0: two launches, for A/B runs and the fused == unfused tests)
     if (!L.has_fuse[ni] && g->tensors[n.in[0]].nchw_raw) {
@@ -754,8 +757,8 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
             if (plan_conv(g, n, false, nullptr, &c)) return -1;
             if (plan_pool(g, g->nodes[pool_node], &p)) return -1;
             L.fused[pool_node] = 1;
-            if (fuse_stem(g, n, g->nodes[pool_node], c, p, &st)) g->steps.push_back(st);
-            else { g->steps.push_back(c.step); g->steps.push_back(p.step); }
+            if (fuse_stem(g, n, g->nodes[pool_node], c, p, &st)) out->push_back(st);
+            else out->insert(out->end(), {c.step, p.step});
             return 0;
         }
     }
@@ -773,14 +776,14 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
         // no tile configuration fits, this pair goes on as before and the second pair is planned again at its own node (try_dwpw's known
         // waste).  The chain's launch runs HERE and writes the second depthwise's output while it reads this conv's input: safe only
         // because plan_buffers starts that output's lifetime three hops up for this node shape (dw <- 1x1 <- dw <- this conv); a change to
-        // that rule or to this look-ahead that lets the two share memory fails prerun (plan_i8: writes_what_it_reads)
+        // that rule or to this look-ahead that lets the two share memory fails prerun (plan_i8: step_writes_what_it_reads)
         int pw2 = -1, dw2 = -1;
         if (tmode == 1 && find_chain4(g, ni, tail, prod, L.fused, L.has_fuse, &pw2, &dw2)) {
             Planned c, d;
             if (plan_conv(g, g->nodes[pw2], false, nullptr, &c) || plan_conv(g, g->nodes[dw2], false, nullptr, &d)) return -1;
             const int chained = plan_chain4(g, n, g->nodes[tail], g->nodes[pw2], g->nodes[dw2], prod, a, b, c, d, &st);
             if (chained < 0) return -1;
-            if (chained) { L.fused[pw2] = 1; L.fused[dw2] = 1; g->steps.push_back(st); return 0; }
+            if (chained) { L.fused[pw2] = 1; L.fused[dw2] = 1; out->push_back(st); return 0; }
         }
         // Where the depthwise tail can go together with ITS consumer (dwpw.hip: batched 14x14-class maps, stride 1), that pairing is
         // tried FIRST.  In a chain pw, dw, pw, dw, .. either pairing covers every layer once per period, and in a pass dwpw is the
@@ -789,23 +792,23 @@ static int plan_conv_node(tamd_graph* g, I8Layout& L, size_t ni)
         // (profiles/r05_layers_mobilenet_v1_int8_b64.txt, the evidence plan: the 14x14 block 120 us; with this order 95 us)
         int took = tmode == 1 ? try_dwpw(g, L, (size_t)tail, b, &st) : 0;
         if (took < 0) return -1;
-        if (took) { g->steps.push_back(a.step); g->steps.push_back(st); return 0; }
+        if (took) { out->insert(out->end(), {a.step, st}); return 0; }
         took = plan_pwdw(g, n, g->nodes[tail], tmode, prod, a, b, &st);
         if (took < 0) return -1;
-        if (took) g->steps.push_back(st);
-        else { g->steps.push_back(a.step); g->steps.push_back(b.step); }
+        if (took) out->push_back(st);
+        else out->insert(out->end(), {a.step, b.step});
         return 0;
     }
     Planned c;
     if (plan_conv(g, n, false, L.has_fuse[ni] ? &L.fuse_at[ni] : nullptr, &c)) return -1;
     const int took = try_dwpw(g, L, ni, c, &st);        // (anything but a depthwise 3x3 launch: 0)
     if (took < 0) return -1;
-    g->steps.push_back(took ? st : c.step);
+    out->push_back(took ? st : c.step);
     return 0;
 }
 
 // ResNet-50's prob; softmax_kernel_ref_int8.c over the channel axis
-static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
@@ -835,9 +838,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
             a.is1 = (long)x.h * x.w * x.cs; a.os1 = (long)y.h * y.w * y.cs; a.is2 = x.cs; a.os2 = y.cs;
             a.istride = (long)x.w * x.cs; a.ostride = (long)y.w * y.cs;
         }
-        Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * (double)x.elems();
-        st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
-        g->steps.push_back(st);
+        out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}));
         return 0;
     }
     if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || !softmax_i8_axis_fits(x.c)) {
@@ -856,9 +857,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
     a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
     a.positions = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.cs_out = y.cs;
     a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-    Step st; st.node = n.name; st.kernel = "softmax_i8"; st.bytes = 2.0 * a.positions * x.c;
-    st.fn = [a](hipStream_t s) { return launch_softmax_i8(a, s); };
-    g->steps.push_back(st);
+    out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * a.positions * x.c, [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}));
     return 0;
 }
 
@@ -866,13 +865,13 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n)
 // (misc_kernels.hip: the ReLU's byte map is non-decreasing, so it commutes with the max).  The pool is planned here, ahead of its
 // node, and its launch reads the ReLU's input; the ReLU's own output is never written.  A negative slope is not monotone, an average
 // pool does not commute, the global form has its own kernel: those stay two launches.  TAMD_PIN=relu_pool=0: two launches (A/B runs
-// and the fused == unfused tests).  1: pushed, 0: not such a pair, -1: error
+// and the fused == unfused tests).  1: handed back in *out, 0: not such a pair, -1: error
 // The pool may sit anywhere behind the ReLU in node order: its output is then written at the RELU's position, while the ReLU's input is
 // still being read.  That is safe only because plan_buffers starts a buffer's lifetime at the earliest producer within TWO hops above the
 // node that produces it (pool <- relu <- the ReLU's producer), so the pool's output can never share memory with the ReLU's input; a change
 // to that rule or to this look-ahead that lets the two share memory fails prerun: the step carries what it reads and writes, and plan_i8
-// checks it (writes_what_it_reads).  The ReLU's never-written output still owns its (shared) buffer.
-static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni)
+// checks it (step_writes_what_it_reads).  The ReLU's never-written output still owns its (shared) buffer.
+static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
     HNode& n = g->nodes[ni];
     HTensor& x = g->tensors[n.in[0]];
@@ -887,26 +886,23 @@ static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni)
     a.p = p.pool;
     a.p.x = (const int8_t*)x.dptr; a.p.cs_in = x.cs;
     a.slope = n.p.relu.negative_slope; a.relu_in_scale = x.scales[0];
-    Step st = make_step(n.name + "+" + g->nodes[pool_node].name, "relu_pool_i8", 0, p.step.bytes, [a](hipStream_t s) { return launch_relu_pool(a, s); });
-    reads_writes(st, x, g->tensors[g->nodes[pool_node].out[0]], false);
-    g->steps.push_back(st);
+    out->push_back(make_step(n.name + "+" + g->nodes[pool_node].name, "relu_pool_i8", 0, p.step.bytes, [a](hipStream_t s) { return launch_relu_pool(a, s); }, {access_of(x)},
+                             {access_of(g->tensors[g->nodes[pool_node].out[0]])}));
     L.fused[pool_node] = 1;
     g->fused_away[n.out[0]] = 1;
     return 1;
 }
 
-static int plan_relu(tamd_graph* g, I8Layout& L, size_t ni)
+static int plan_relu(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
     HNode& n = g->nodes[ni];
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
-    const int took = try_relu_pool(g, L, ni);
+    const int took = try_relu_pool(g, L, ni, out);
     if (took) return took < 0 ? -1 : 0;
     if (x.is_view || y.is_view) { set_error("relu %s on a concat view is not supported", n.name.c_str()); return -1; }
     ReluArgs a{(const int8_t*)x.dptr, (int8_t*)y.dptr, (size_t)x.n * x.h * x.w * x.cs, n.p.relu.negative_slope, x.scales[0], y.scales[0]};
-    Step st; st.node = n.name; st.kernel = "relu_i8"; st.bytes = 2.0 * x.n * x.h * x.w * x.c;
-    st.fn = [a](hipStream_t s) { return launch_relu(a, s); };
-    g->steps.push_back(st);
+    out->push_back(make_step(n.name, "relu_i8", 0, 2.0 * x.n * x.h * x.w * x.c, [a](hipStream_t s) { return launch_relu(a, s); }, {access_of(x)}, {access_of(y)}));
     return 0;
 }
 
@@ -943,8 +939,7 @@ int plan_lut(tamd_graph* g, HNode& n, Step* out)
     } else {
         a.count = x.elems();
     }
-    *out = make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); });
-    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
+    *out = make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)});
     return 0;
 }
 
@@ -988,7 +983,7 @@ int plan_prelu(tamd_graph* g, HNode& n, Step* out)
         PreluI8Args a{};
         a.x = (const int8_t*)x.dptr; a.y = (int8_t*)y.dptr; a.count = (size_t)x.n * x.h * x.w * x.cs; a.C = C; a.cs = x.cs;
         a.slope = dslope; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-        *out = make_step(n.name, "prelu_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_i8(a, s); });
+        *out = make_step(n.name, "prelu_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_i8(a, s); }, {access_of(x)}, {access_of(y)});
     } else {
         if (!x.nchw_raw || !y.nchw_raw) { set_error("prelu %s: input and output are not dense NCHW tensors", n.name.c_str()); return -1; }
         const size_t ntab = nslope == 1 ? 1 : (size_t)C;
@@ -1003,9 +998,8 @@ int plan_prelu(tamd_graph* g, HNode& n, Step* out)
         PreluU8Args a{};
         a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.planes = (long)x.dims[0] * C; a.C = C; a.HW = x.dims[2] * x.dims[3];
         a.tables = dtables; a.shared = nslope == 1 ? 1 : 0;
-        *out = make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); });
+        *out = make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); }, {access_of(x)}, {access_of(y)});
     }
-    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
     return 0;
 }
 
@@ -1043,7 +1037,7 @@ int plan_interp(tamd_graph* g, HNode& n, Step* out)
         a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs;
         a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
         a.iy = diy; a.ix = dix; a.table = dtable;
-        *out = make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); });
+        *out = make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); }, {access_of(x)}, {access_of(y)});
     } else {
         if (x.is_view) { set_error("interp %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
         InterpU8Args a{};
@@ -1053,9 +1047,8 @@ int plan_interp(tamd_graph* g, HNode& n, Step* out)
         a.iy = diy; a.ix = dix; a.table = dtable;
         a.identity = 1;
         for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
-        *out = make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); });
+        *out = make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)});
     }
-    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));       // (listed for plan_i8's overlap check; the step stays ordered: no deps)
     return 0;
 }
 
@@ -1089,9 +1082,9 @@ static int plan_chan_map_i8(tamd_graph* g, const std::string& node, const std::v
     if (upload(g, table, &dtable)) return -1;
     a.y = (int8_t*)y.dptr; a.pixels = (long)y.n * y.h * y.w; a.C = y.c; a.ldc = y.cs; a.c_off = y.c_off; a.table = dtable;
     a.fix128 = through_concat ? 1 : 0;                      // a Concat of several inputs: -128 -> 127 (chanmap.hip)
-    *out = make_step(node, "chan_map_i8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_i8(a, s); });
-    for (const HTensor* x : srcs) out->rd.push_back(access_of(*x));
-    out->wr.push_back(access_of(y));                                         // (complete lists; the step stays ordered: no deps)
+    std::vector<Access> reads;
+    for (const HTensor* x : srcs) reads.push_back(access_of(*x));
+    *out = make_step(node, "chan_map_i8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_i8(a, s); }, reads, {access_of(y)});
     return 0;
 }
 
@@ -1111,16 +1104,13 @@ static int try_chan_map_g2(tamd_graph* g, const std::string& node, const HTensor
     ChanMapG2Args k{};
     k.a = (const int8_t*)a.dptr + ra; k.b = (const int8_t*)b.dptr + rb; k.cs_a = a.cs; k.cs_b = b.cs;
     k.y = (int8_t*)y.dptr; k.pixels = (long)y.n * y.h * y.w; k.half = half; k.ldc = y.cs; k.c_off = y.c_off; k.fix128 = through_concat ? 1 : 0;
-    *out = make_step(node, "chan_map_i8_g2", 0, 2.0 * (double)y.elems(), [k](hipStream_t s) { return launch_chan_map_g2(k, s); });
-    out->rd.push_back(access_of(a));
-    if (&a != &b) out->rd.push_back(access_of(b));
-    out->wr.push_back(access_of(y));
+    *out = make_step(node, "chan_map_i8_g2", 0, 2.0 * (double)y.elems(), [k](hipStream_t s) { return launch_chan_map_g2(k, s); }, {access_of(a), access_of(b)}, {access_of(y)});
     return 1;
 }
 
 // split_ref.c:109-135: output i is channels [first_i, first_i + sizes[i]) of the input, bytes as they are.  An output that
 // plan_split_views made a view of the input has no launch; every other one is one chan_map_i8 launch with one source
-static int plan_split(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_split(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     std::vector<size_t> oq;
@@ -1136,7 +1126,7 @@ static int plan_split(tamd_graph* g, I8Layout& L, HNode& n)
             for (int c = 0; c < y.c; c++) sel[c] = {0, first + c};
             Step st;
             if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
-            g->steps.push_back(st);
+            out->push_back(st);
         }
         first += y.c;
     }
@@ -1154,7 +1144,7 @@ static int shuffle_sources(const HNode& n, const HTensor& x, const HTensor& y, s
     return 0;
 }
 
-static int plan_shuffle(tamd_graph* g, HNode& n)
+static int plan_shuffle(tamd_graph* g, HNode& n, std::vector<Step>* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
@@ -1163,17 +1153,16 @@ static int plan_shuffle(tamd_graph* g, HNode& n)
     std::vector<std::pair<int, int>> sel((size_t)y.c);
     for (int o = 0; o < y.c; o++) sel[o] = {0, src[o]};
     Step st;
-    if (n.p.shuffle.group == 2 && try_chan_map_g2(g, n.name, x, 0, x, x.c / 2, x.c / 2, y, false, &st)) { g->steps.push_back(st); return 0; }
-    if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
-    g->steps.push_back(st);
+    if (!(n.p.shuffle.group == 2 && try_chan_map_g2(g, n.name, x, 0, x, x.c / 2, x.c / 2, y, false, &st)) && plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
+    out->push_back(st);
     return 0;
 }
 
 // The pair match_cat_shuffle found, planned at the CONCAT's position: the launch reads the Concat's inputs and writes the
 // ShuffleChannel's output.  That output's lifetime starts at the earliest producer within two hops above the ShuffleChannel
 // (plan_buffers: shuffle <- concat <- the inputs' producers), so it never shares memory with an input; planned at the
-// ShuffleChannel's position an input's buffer could have been reused before it is read.  plan_i8 checks it (writes_what_it_reads)
-static int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj)
+// ShuffleChannel's position an input's buffer could have been reused before it is read.  plan_i8 checks it (step_writes_what_it_reads)
+static int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj, std::vector<Step>* out)
 {
     HNode& sh = g->nodes[sj];
     HTensor& mid = g->tensors[cat.out[0]];
@@ -1196,7 +1185,7 @@ static int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj)
     if (!(two_halves && try_chan_map_g2(g, cat.name + "+" + sh.name, *srcs[0], 0, *srcs[1], 0, srcs[0]->c, y, true, &st))
         && plan_chan_map_i8(g, cat.name + "+" + sh.name, srcs, sel, y, cat.in.size() > 1, &st))
         return -1;
-    g->steps.push_back(st);
+    out->push_back(st);
     L.fused[sj] = 1;
     g->fused_away[cat.out[0]] = 1;
     return 0;
@@ -1223,8 +1212,7 @@ static int plan_chan_map_u8(tamd_graph* g, const std::string& node, const HTenso
     a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
     a.N = y.n; a.C = y.c; a.HW = y.h * y.w; a.in_img = x.c * x.h * x.w; a.in_planes = x.c;
     a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.src_plane = dplanes; a.table = dtable;
-    *out = make_step(node, "chan_map_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_u8(a, s); });
-    out->rd.push_back(access_of(x)); out->wr.push_back(access_of(y));
+    *out = make_step(node, "chan_map_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_u8(a, s); }, {access_of(x)}, {access_of(y)});
     return 0;
 }
 
@@ -1263,7 +1251,7 @@ int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out)
 }
 
 // upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
-static int plan_upsample(tamd_graph* g, HNode& n)
+static int plan_upsample(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& x = g->tensors[n.in[0]];
     HTensor& y = g->tensors[n.out[0]];
@@ -1285,17 +1273,14 @@ static int plan_upsample(tamd_graph* g, HNode& n)
     a.copy = a.in_scale == a.out_scale && a.in_zp == a.out_zp;
     // written in place of a Concat's copy: that copy turns -128 into 127 when the Concat has several inputs (a single input is copied
     // byte for byte, concat_kernel_ref_int8.c:47-57), so the launch does.  plan_concat_views makes such an output a view only where the
-    // Concat is its one reader: anyone else reads the Upsample's own bytes, -128 included.  (A Concat's output is never a view itself.)
-    if (y.is_view)
-        for (auto& c : g->nodes)
-            if (c.op == TAMD_OP_CONCAT && c.in.size() > 1 && std::find(c.in.begin(), c.in.end(), n.out[0]) != c.in.end() && g->tensors[c.out[0]].dptr == y.dptr)
-                a.fix128 = 1;
-    Step st = make_step(n.name, "upsample_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_upsample_i8(a, s); });
-    g->steps.push_back(st);
+    // Concat is its one reader: anyone else reads the Upsample's own bytes, -128 included.
+    a.fix128 = L.in_multi_cat[n.out[0]] ? 1 : 0;
+    out->push_back(make_step(n.name, "upsample_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_upsample_i8(a, s); },
+                             {access_of(x)}, {access_of(y)}));
     return 0;
 }
 
-static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n)
+static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
 {
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
@@ -1316,9 +1301,7 @@ static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n)
         g->fused_away[n.out[0]] = 1;
     }
     a.y = (int8_t*)y->dptr;
-    Step st; st.node = n.name; st.kernel = kname; st.bytes = bytes;
-    st.fn = [a](hipStream_t s) { return launch_eltwise(a, s); };
-    g->steps.push_back(st);
+    out->push_back(make_step(n.name, kname, 0, bytes, [a](hipStream_t s) { return launch_eltwise(a, s); }, {access_of(xa), access_of(xb)}, {access_of(*y)}));
     return 0;
 }
 
@@ -1333,29 +1316,33 @@ static int plan_outputs(tamd_graph* g)
         if (t.h * t.w == 1 && t.cs == t.c && t.c_off == 0) { io.stage = t.dptr; continue; }
         if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
         LayoutArgs a{(const int8_t*)t.dptr + t.c_off, io.stage, t.n, t.c, t.h, t.w, t.cs, esize(t.dtype)};
-        Step st; st.node = t.name; st.kernel = "nhwc_to_nchw";
-        st.fn = [a](hipStream_t s) { return launch_nhwc_to_nchw(a, s); };
-        g->out_steps.push_back(st);
+        g->out_steps.push_back(make_step(t.name, "nhwc_to_nchw", 0, 0, [a](hipStream_t s) { return launch_nhwc_to_nchw(a, s); }));     // (no accesses: resolve_views)
     }
     return 0;
 }
 
-// A launch that writes what it reads is an error.  A fused launch runs at its first node's position -- chain4 and ReLU + pool even ahead
-// of node order -- and writes its output while other blocks still read its input; only plan_buffers' birth rule keeps the two out of one
-// shared buffer.  Every step that states what it reads and writes (reads_writes) is checked
-static int writes_what_it_reads(const tamd_graph* g)
+// The one place a launch goes onto g->steps.  Every compute launch of an int8 graph reads and writes some activation and says so
+// (graph.h: make_step), and a launch that writes what it reads is an error: a fused launch runs at its first node's position -- chain4
+// and ReLU + pool even ahead of node order, a convolution's eltwise tail and eltwise + ReLU a node or two ahead -- and writes its output
+// while other blocks still read its input; only plan_buffers' birth rule keeps the two out of one shared buffer
+static int append_steps(tamd_graph* g, const std::vector<Step>& launches)
 {
-    for (auto& st : g->steps)
-        for (auto& w : st.wr)
-            for (auto& r : st.rd)
-                if (access_overlap(w, r)) {
-                    set_error("launch %s (%s) writes memory that it reads: its output shares a buffer with its input", st.kernel.c_str(), st.node.c_str());
-                    return -1;
-                }
+    for (auto& st : launches) {
+        if (step_states_nothing(st)) {
+            set_error("launch %s (%s) does not state what it reads and writes", st.kernel.c_str(), st.node.c_str());
+            return -1;
+        }
+        if (step_writes_what_it_reads(st)) {
+            set_error("launch %s (%s) writes memory that it reads: its output shares a buffer with its input", st.kernel.c_str(), st.node.c_str());
+            return -1;
+        }
+        g->steps.push_back(st);
+    }
     return 0;
 }
 
-// node list -> launch list: the layout passes in order, then one planner per node
+// node list -> launch list: the layout passes in order, then one planner per node.  A node function hands its launches back in `out`
+// (none for a node that is a view, runs inside another node's launch or -- PriorBox -- is evaluated here) and pushes nothing itself
 int plan_i8(tamd_graph* g)
 {
     for (auto& t : g->tensors) if (t.ttype != TAMD_TT_CONST) nhwc_geom(t);
@@ -1368,37 +1355,38 @@ int plan_i8(tamd_graph* g)
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (L.fused[ni]) continue;
-        Planned one;
+        std::vector<Step> out;
+        Planned one;                 // FC / pooling: a single launch as plan_conv / plan_pool hand it to the fusers
+        Step st;                     // .. and as the planners that plan_u8 shares hand it out
         int r = 0;
         switch (n.op) {
         case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN: break;
-        case TAMD_OP_PERMUTE: r = plan_permute(g, L, n); break;
-        case TAMD_OP_RESHAPE: r = plan_reshape(g, L, n); break;
+        case TAMD_OP_PERMUTE: r = plan_permute(g, L, n, &out); break;
+        case TAMD_OP_RESHAPE: r = plan_reshape(g, L, n, &out); break;
         case TAMD_OP_PRIORBOX: r = plan_priorbox(g, n); break;
         case TAMD_OP_CONCAT:
-            r = L.flat_concat[ni] ? plan_flat_concat(g, L, n) : L.cat_shuffle[ni] ? plan_cat_shuffle(g, L, n, (size_t)L.cat_shuffle[ni] - 1) : plan_channel_concat(g, L, n);
+            r = L.flat_concat[ni] ? plan_flat_concat(g, L, n, &out)
+                : L.cat_shuffle[ni] ? plan_cat_shuffle(g, L, n, (size_t)L.cat_shuffle[ni] - 1, &out) : plan_channel_concat(g, L, n, &out);
             break;
-        case TAMD_OP_CONV: r = plan_conv_node(g, L, ni); break;
-        case TAMD_OP_FC: if (!(r = plan_conv(g, n, true, nullptr, &one))) g->steps.push_back(one.step); break;
-        case TAMD_OP_POOL: if (!(r = plan_pool(g, n, &one))) g->steps.push_back(one.step); break;
-        case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n); break;
-        case TAMD_OP_RELU: r = plan_relu(g, L, ni); break;
-        case TAMD_OP_UPSAMPLE: r = plan_upsample(g, n); break;
-        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n); break;
-        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
-            if (!(r = plan_lut(g, n, &one.step))) g->steps.push_back(one.step);
-            break;
-        case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &one.step))) g->steps.push_back(one.step); break;
-        case TAMD_OP_SPLIT: r = plan_split(g, L, n); break;
-        case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n); break;
-        case TAMD_OP_PRELU: if (!(r = plan_prelu(g, n, &one.step))) g->steps.push_back(one.step); break;
+        case TAMD_OP_CONV: r = plan_conv_node(g, L, ni, &out); break;
+        case TAMD_OP_FC: if (!(r = plan_conv(g, n, true, nullptr, &one))) out.push_back(one.step); break;
+        case TAMD_OP_POOL: if (!(r = plan_pool(g, n, &one))) out.push_back(one.step); break;
+        case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n, &out); break;
+        case TAMD_OP_RELU: r = plan_relu(g, L, ni, &out); break;
+        case TAMD_OP_UPSAMPLE: r = plan_upsample(g, L, n, &out); break;
+        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, &out); break;
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: if (!(r = plan_lut(g, n, &st))) out.push_back(st); break;
+        case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &st))) out.push_back(st); break;
+        case TAMD_OP_SPLIT: r = plan_split(g, L, n, &out); break;
+        case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n, &out); break;
+        case TAMD_OP_PRELU: if (!(r = plan_prelu(g, n, &st))) out.push_back(st); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;
         }
-        if (r) return -1;
+        if (r || append_steps(g, out)) return -1;
     }
-    return writes_what_it_reads(g) ? -1 : plan_outputs(g);
+    return plan_outputs(g);
 }
 
 }  // namespace tamd

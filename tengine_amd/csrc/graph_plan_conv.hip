@@ -479,19 +479,18 @@ int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* 
 {
     ConvI8 c{g, n, g->tensors[n.in[0]], g->tensors[n.in[1]], n.in.size() > 2 ? &g->tensors[n.in[2]] : nullptr, g->tensors[n.out[0]]};
     if (conv_i8_open(c, as_fc)) return -1;
-    Step& st = out->step;
-    st.node = n.name; st.macs = c.macs; st.bytes = c.bytes;
+    // the step without kernel and launch, which the form fills in.  Constants aside, all a convolution / FC launch touches is its input
+    // and its output; with an eltwise tail (a GEMM form always: scan_eltwise_fusion) it also reads the other operand and stores the
+    // tail's output instead of its own, and stays ordered
+    if (fz) out->step = make_step(n.name, "", c.macs, c.bytes, nullptr, {access_of(c.x), access_of(g->tensors[fz->res_tensor])}, {access_of(g->tensors[fz->out_tensor])});
+    else out->step = make_step(n.name, "", c.macs, c.bytes, nullptr, {access_of(c.x)}, {access_of(c.y)}, true);
     out->elt_tail = fz != nullptr;
-    int r = 0;
     switch (conv_i8_form(c)) {
-    case Planned::FIRST: r = conv_i8_first(c, out); break;
-    case Planned::DW3X3: r = conv_i8_dw3x3(c, out); break;
-    case Planned::GEMM: r = conv_i8_gemm(c, fz, out); break;
-    default: r = conv_i8_direct(c, out); break;
+    case Planned::FIRST: return conv_i8_first(c, out);
+    case Planned::DW3X3: return conv_i8_dw3x3(c, out);
+    case Planned::GEMM: return conv_i8_gemm(c, fz, out);
+    default: return conv_i8_direct(c, out);
     }
-    if (r) return -1;
-    if (!fz) reads_writes(st, c.x, c.y);      // its input, its output (constants aside), one launch: all a convolution / FC step touches
-    return 0;
 }
 
 
@@ -507,7 +506,9 @@ int plan_pool(tamd_graph* g, HNode& n, Planned* out)
     a.method = n.p.pool.pool_method; a.caffe_flavor = n.p.pool.caffe_flavor;
     a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
     out->kind = Planned::POOL; out->pool = a;
-    out->step = make_step(n.name, "pool_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_pool(a, s); });
+    // (x and y may be channel slices of ONE concat buffer -- concat(x, pool(x), ..) -- which access_overlap tells apart)
+    out->step = make_step(n.name, "pool_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_pool(a, s); },
+                          {access_of(x)}, {access_of(y)});
     return 0;
 }
 

@@ -277,9 +277,8 @@ int plan_pwdw(tamd_graph* g, HNode& pw, HNode& tl, int tmode, int prod, const Pl
     char nm[48];
     if (tmode == 1) snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d%s>", prod == 1 ? "firstdw" : "pwdw", a.S, v.TH, v.TW, threads, v.sl == 4 ? ",c64" : v.sl == 2 ? ",c32" : "");
     else snprintf(nm, sizeof(nm), "pwpool_i8<%d>", threads);
-    *fused = fused_step({&pa, &pb}, nm, [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); });
     // reads the pointwise input, writes the tail's output, nothing else; the first layer pair may run beside its predecessors (run_steps: wrap)
-    reads_writes(*fused, x, y, prod == 1 && tmode == 1);
+    *fused = fused_step({&pa, &pb}, nm, [v, threads](hipStream_t s) { return launch_pwdw(v, threads, s); }, x, y, prod == 1 && tmode == 1);
     g->fused_away[pw.out[0]] = 1;
     return 1;
 }
@@ -442,8 +441,8 @@ int plan_chain4(tamd_graph* g, HNode& n0, HNode& d1, HNode& p2, HNode& d2, int p
     const int threads = cfgs[best].threads;
     char nm[64];
     snprintf(nm, sizeof(nm), "%s_i8<s%d,%dx%d,%d>", prod == 1 ? "firstchain4" : "chain4", a.S2, v.TH, v.TW, threads);
-    *fused = fused_step({&pa, &pb, &pc, &pd}, nm, [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); });
-    reads_writes(*fused, x, y, prod == 1);      // reads the producer's input, writes the last depthwise's output, nothing else (deps: as plan_pwdw)
+    // reads the producer's input, writes the last depthwise's output, nothing else (deps: as plan_pwdw)
+    *fused = fused_step({&pa, &pb, &pc, &pd}, nm, [v, threads](hipStream_t s) { return launch_chain4(v, threads, s); }, x, y, prod == 1);
     g->fused_away[n0.out[0]] = 1;
     g->fused_away[d1.out[0]] = 1;
     g->fused_away[p2.out[0]] = 1;
@@ -483,8 +482,7 @@ int plan_dwpw(tamd_graph* g, HNode& dw, HNode& pw, const Planned& pd, const Plan
         fuse = w == 1;
     }
     if (!fuse) return 0;
-    *fused = fused_step({&pd, &pc}, "dwpw_i8", [a](hipStream_t s) { return launch_dwpw(a, s); });
-    reads_writes(*fused, g->tensors[dw.in[0]], g->tensors[pw.out[0]]);
+    *fused = fused_step({&pd, &pc}, "dwpw_i8", [a](hipStream_t s) { return launch_dwpw(a, s); }, g->tensors[dw.in[0]], g->tensors[pw.out[0]], true);
     g->fused_away[dw.out[0]] = 1;
     return 1;
 }
@@ -513,8 +511,7 @@ int plan_block(tamd_graph* g, HNode& na, HNode& nb, HNode& nc, const FusedElt& f
     int8_t* dwp = nullptr;
     if (upload(g, wp, &dwp)) return -1;
     const BlockArgs v = block_args(a, pb.gemm, pc.gemm_tail, dwp);
-    *fused = fused_step({&pa, &pb, &pc}, "block_i8", [v](hipStream_t s) { return launch_block(v, s); });
-    reads_writes(*fused, g->tensors[na.in[0]], g->tensors[fz.out_tensor]);
+    *fused = fused_step({&pa, &pb, &pc}, "block_i8", [v](hipStream_t s) { return launch_block(v, s); }, g->tensors[na.in[0]], g->tensors[fz.out_tensor], true);
     g->fused_away[na.out[0]] = 1;
     g->fused_away[nb.out[0]] = 1;
     return 1;

@@ -1,5 +1,6 @@
 // Host check of the dependency test behind the barrier-free launches of the direct path (tengine_amd/csrc/graph.h: Access,
-// access_of, access_overlap, step_conflict): which steps may run beside each other.  No device is touched.
+// access_of, access_overlap, step_conflict): which steps may run beside each other -- and of what the int8 planner refuses of one step
+// (access_of_channels, step_writes_what_it_reads, step_states_nothing).  No device is touched.
 // build: hipcc -std=c++17 -I tengine_amd/csrc -I include step_conflict_check.cc -o step_conflict_check
 #include <cstdio>
 
@@ -57,6 +58,33 @@ int main()
     EXPECT(step_conflict(next, conv_conf));                                                   // RAW + WAR
     Step again = conv_loc;
     EXPECT(step_conflict(again, conv_loc));                                                   // WAW
+    // a concat input's slot in an NHWC buffer (access_of_channels) against views of the same buffer: a 2x4x4 map, cs = 32
+    const Access slot_lo = access_of_channels(whole, 0, 16), slot_hi = access_of_channels(whole, 16, 16), slot_mid = access_of_channels(whole, 8, 16);
+    EXPECT(slot_lo.size == 2u * 16 * 32 && slot_lo.period == 32 && slot_hi.off == 16 && slot_hi.len == 16);
+    EXPECT(!access_overlap(slot_lo, slot_hi) && !access_overlap(slot_lo, access_of(n1)) && !access_overlap(slot_hi, access_of(n0)));
+    EXPECT(access_overlap(slot_lo, access_of(n0)) && access_overlap(slot_hi, access_of(n1)));
+    EXPECT(access_overlap(slot_mid, slot_lo) && access_overlap(slot_mid, slot_hi) && access_overlap(slot_mid, access_of(n0)) && access_overlap(slot_mid, access_of(n1)));
+    EXPECT(access_overlap(slot_lo, access_of(whole)) && access_overlap(access_of(whole), slot_hi));      // a slot against the whole buffer
+    EXPECT(access_of_channels(n1, 0, 16).off == 16);                                                      // counted from the tensor's own first channel
+    // one step against itself (what plan_i8 refuses): reading view [0,16) and writing view [16,32) of one buffer is fine (SPP, DenseNet)
+    auto none = [](hipStream_t) { return hipSuccess; };
+    HTensor d0 = whole, d1 = whole, d2 = whole;                       // three dense NHWC buffers
+    d1.dptr = buf + 8192; d2.dptr = buf + 16384;
+    const Step spp = make_step("pool", "pool_i8", 0, 0, none, {access_of(n0)}, {access_of(n1)});
+    EXPECT(!step_states_nothing(spp) && !step_writes_what_it_reads(spp) && !spp.deps);
+    EXPECT(make_step("conv", "k", 0, 0, none, {access_of(d0)}, {access_of(d1)}, true).deps);
+    const Step in_place = make_step("add", "eltwise_i8", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d0)});
+    EXPECT(step_writes_what_it_reads(in_place));
+    const Step residual = make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d1)});       // only the SECOND read
+    EXPECT(step_writes_what_it_reads(residual));
+    EXPECT(!step_writes_what_it_reads(make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d2)})));
+    EXPECT(step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_mid})));
+    EXPECT(!step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_hi})));
+    // a step that states no read or no write "states nothing"
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none)));
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)})));
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {}, {access_of(d0)})));
+    EXPECT(!step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)}, {access_of(d1)})));
     printf("step_conflict_check: %d failures\n", bad);
     return bad != 0;
 }

@@ -94,6 +94,32 @@ def test_concat_same_tensor_twice():
     assert names.count("concat_copy_i8") == 3, names              # a read twice: neither position is written in place
 
 
+def test_spp_pools_read_one_slice_of_the_concat_buffer_and_write_another():
+    """concat(x, maxpool3(x), maxpool5(x)), everything on the concat's scale: x is written in place at channel 0 and each pool launch reads
+    that slice of the (shared) concat buffer while it writes its own slice of the same buffer -- which the planner has to tell apart
+    from a launch that writes what it reads"""
+    rng = np.random.default_rng(55)
+    n, c, h, w = 1, 16, 6, 6
+    g, x = conv_graph(55, n, 16, h, w, c, 1, 1, 0)
+    a = g.nodes[-1].outputs[0]
+    sa = g.tensors[a].scales[0]
+    ins = [a]
+    for k in (3, 5):
+        p = g.add_tensor("pool%d" % k, [n, c, h, w], DT_INT8, tm2.TT_VAR, None, [sa], [0])
+        g.add_node("pool%d" % k, "Pooling", [a], [p], alg=0, kernel_h=k, kernel_w=k, stride_h=1, stride_w=1, **{"global": 0}, caffe_flavor=0,
+                   pad_h0=k // 2, pad_w0=k // 2, pad_h1=k // 2, pad_w1=k // 2)
+        ins.append(p)
+    cat = g.add_tensor("cat", [n, 3 * c, h, w], DT_INT8, tm2.TT_VAR, None, [sa], [0])
+    g.add_node("cat", "Concat", ins, [cat], axis=1)
+    wq = rng.integers(-127, 128, size=(20, 3 * c, 1, 1)).astype(np.int8)
+    ws = _scales(rng, 20)
+    o = g.add_tensor("head_out", [n, 20, h, w], DT_INT8, tm2.TT_VAR, None, [float(np.float32(sa * np.mean(ws) * 73.0 * np.sqrt(3 * c) * 73.0 / 60.0))], [0])
+    g.output_nodes = [g.add_node("head", "Convolution", [cat, g.add_const("w2", wq, DT_INT8, ws, [0] * 20)], [o], kernel_h=1, kernel_w=1, stride_h=1, stride_w=1,
+                                 dilation_h=1, dilation_w=1, input_channel=3 * c, output_channel=20, group=1, activation=-1, pad_h0=0, pad_w0=0, pad_h1=0, pad_w1=0)]
+    names = check(g, x)
+    assert names.count("pool_i8") == 2 and "concat_copy_i8" not in names, names       # three views: the Concat launches nothing
+
+
 @pytest.mark.parametrize("as_output", [False, True])
 def test_flatten_of_a_map(as_output):
     """conv -> Flatten -> FC: the FC weight indexes [c][h][w] (NCHW flatten order) while the device tensor is NHWC"""

@@ -4,7 +4,8 @@ fresh process that imports a private copy of the tengine_amd package holding the
 library only once), plans from its own plan file, checks its bytes against the other build's and times the step as bench.py does.
 
 usage: ab_lib.py model batch dtype iters rounds  NAME=/path/to/libtengine_amd.so  NAME=...   (NAME=product: the tree's own build)
-       [env TAMD_U8_INT=1 etc. is inherited; AB_LAYERS=1 adds per-launch tables (isolated launches, HIP events): the first build beside each other one;
+       [env TAMD_U8_INT=1 etc. is inherited; with TAMD_DEBUG=1 each round also shows the planner's "activations: .. buffers share .. MB" line;
+        AB_LAYERS=1 adds per-launch tables (isolated launches, HIP events): the first build beside each other one;
         a worker that dies ends the run with exit status 1: nothing more is started on a GPU that may have faulted]"""
 import hashlib
 import json
@@ -47,6 +48,7 @@ def main():
             shutil.copyfile(path, os.path.join(pkg, "tengine_amd", "lib", "libtengine_amd.so"))
         variants.append((nm, pkg, os.path.join(tmp, nm + "_plan.txt")))
     res = {nm: [] for nm, _, _ in variants}
+    prerun = {nm: [] for nm, _, _ in variants}
     sha = {}
     layers = {}
     for r in range(rounds):
@@ -61,8 +63,11 @@ def main():
                 sys.exit(1)
             j = json.loads(line[-1])
             res[nm].append(j["us"])
+            prerun[nm].append(j["prerun_ms"])
             sha[nm] = j["sha"]
-            print("  round %d %-20s %9.2f us  %d launches  sha %s" % (r, nm, j["us"], j["launches"], j["sha"]), flush=True)
+            shared = [l.split("activations: ")[1] for l in p.stderr.splitlines() if l.startswith("[tamd] activations: ")]
+            print("  round %d %-20s %9.2f us  %d launches  sha %s  prerun %8.1f ms%s" % (r, nm, j["us"], j["launches"], j["sha"], j["prerun_ms"], "  | " + " / ".join(shared) if shared else ""),
+                  flush=True)
             for node, kern, us in j.get("layers", []):
                 key = (node, kern)
                 layers.setdefault(nm, {})
@@ -72,6 +77,10 @@ def main():
         v = sorted(res[nm])
         if v:
             print("  %-28s min %9.2f  median %9.2f  max %9.2f | output sha %s%s" % (nm, v[0], v[len(v) // 2], v[-1], sha.get(nm), "" if len(set(sha.values())) == 1 else "  (DIFFERS between builds)"))
+    for nm, _, _ in variants:                              # round 0 times the plan-time races, the later rounds take its plan file
+        v = sorted(prerun[nm][1:])
+        if v:
+            print("  %-28s prerun_ms, rounds 1..: min %8.1f  median %8.1f  max %8.1f   (round 0, racing: %.1f)" % (nm, v[0], v[len(v) // 2], v[-1], prerun[nm][0]))
     for other in variants[1:] if layers else []:          # AB_LAYERS=1: isolated launches (HIP events), min over the rounds, the first build beside each other one
         a, b = variants[0][0], other[0]
         print("  per launch, isolated (us): %-24s %-34s %8s | %-34s %8s" % ("node", a, "", b, ""))
