@@ -1,7 +1,7 @@
 // The channel-moving operators of quantised graphs: Split (split_ref.c), ShuffleChannel (shuffle_channel_ref.c) and a channel Concat
 // whose only reader is a ShuffleChannel.  In the reference they are memcpys -- no quantisation parameter is read, -128 stays -128 --
 // except the uint8 Split, which requantises one byte to one byte.  Nothing is computed here either: which source channel an output
-// channel takes, and the uint8 byte map, come from the host, built at prerun (chanmap_tables.cc, graph_plan.hip), so every one of
+// channel takes, and the uint8 byte map, come from the host, built at prerun (chanmap_tables.cc, graph_plan_maps.hip), so every one of
 // these nodes is the same kernel and its bytes are the reference's by construction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -81,8 +81,8 @@ struct Step {                  // one device launch of the compiled plan
     bool once = false;         // every input is a prerun constant (PriorBox outputs): launched once at the end of prerun
     // rd / wr list EVERYTHING the step's launch reads / writes in device memory that another step may write (constants left
     // out) -- only then is deps set, and only a step with deps may run beside its predecessors (graph_exec.hip run_steps).  Every
-    // compute step of an int8 graph lists them, most without deps (they stay ordered): plan_i8 refuses a step that states nothing
-    // and one whose wr overlaps its rd (graph_plan.hip)
+    // compute step of every graph lists them, most without deps (they stay ordered): append_steps refuses a step that states
+    // nothing and one whose wr overlaps its rd (graph_plan_common.hip)
     bool deps = false;
     std::vector<Access> rd, wr;
 };
@@ -102,9 +102,10 @@ inline bool step_writes_what_it_reads(const Step& s)             // any write ag
 }
 // The one way to make a step: what the profile shows of it (node, kernel, macs, bytes), the launch, and what that launch reads and
 // writes (rd / wr, see Step).  deps: the lists are complete AND the step may run beside its predecessors.  Without deps the lists change
-// nothing at run time -- run_steps reads them only behind deps, the step stays ordered -- they are what plan_i8's check reads
+// nothing at run time -- run_steps reads them only behind deps, the step stays ordered -- they are what append_steps' check reads.
+// No defaults: only the layout launches (in_steps / out_steps) state nothing, and they say so with explicit empty lists
 inline Step make_step(const std::string& node, const std::string& kernel, double macs, double bytes, std::function<hipError_t(hipStream_t)> fn,
-                      std::vector<Access> rd = {}, std::vector<Access> wr = {}, bool deps = false)
+                      std::vector<Access> rd, std::vector<Access> wr, bool deps)
 {
     Step st;
     st.node = node; st.kernel = kernel; st.macs = macs; st.bytes = bytes; st.fn = std::move(fn);
@@ -130,6 +131,13 @@ inline Access access_of(const HTensor& t)                         // dense tenso
     }
     return a;
 }
+// raw bytes [p, p + bytes): a buffer that is no tensor (the fp32 copy of a uint8 tensor, the Winograd workspaces)
+inline Access access_of_bytes(const void* p, size_t bytes)
+{
+    Access a;
+    a.base = (const char*)p; a.size = bytes; a.len = bytes;
+    return a;
+}
 
 // channels [first, first + count) of every pixel of the NHWC int8 buffer that `t` lives in, counted from t's own first channel: what
 // access_of cannot say of a tensor that is no view (a concat input's slot of the concat's buffer)
@@ -139,6 +147,15 @@ inline Access access_of_channels(const HTensor& t, int first, int count)
     a.base = (const char*)t.dptr;
     a.size = (size_t)t.n * t.h * t.w * t.cs;
     a.period = (size_t)t.cs; a.off = (size_t)(t.c_off + first); a.len = (size_t)count;
+    return a;
+}
+// elements [off, off + len) of every `period` elements of the dense tensor `y`, `esz` bytes per element: a concat input's slot of the
+// NCHW planners' concat output (any axis: period = the output's elements per index in front of the axis)
+inline Access access_of_slot(const HTensor& y, size_t period, size_t off, size_t len, size_t esz)
+{
+    Access a;
+    a.base = (const char*)y.dptr;
+    a.size = y.elems() * esz; a.period = period * esz; a.off = off * esz; a.len = len * esz;
     return a;
 }
 
@@ -244,7 +261,7 @@ struct tamd_graph {
 
 namespace tamd {
 
-// planner helpers shared by graph_plan.hip (int8, NHWC) and graph_u8.hip (uint8, NCHW)
+// planner helpers shared by graph_plan.hip (int8, NHWC), graph_u8.hip (uint8, NCHW) and graph_f32.hip (fp32, NCHW): graph_plan_common.hip
 PoolGeom pool_geom(const tamd_pool_param& p, int h, int w);
 int dev_alloc(tamd_graph* g, void** p, size_t bytes, bool zero);
 // plan-time races (plan_cache.hip).  A candidate: the plan-cache tag that names it, how to launch it (one launch, or several
@@ -265,23 +282,27 @@ int plan_race(tamd_graph* g, const std::string& node, const std::vector<RaceCand
 int plan_cached(const std::string& key, const std::vector<RaceCand>& cands);
 bool autotune_enabled();           // TAMD_AUTOTUNE=0: no site races, every one keeps its incumbent
 void nhwc_geom(HTensor& t);
+// The one place a launch goes onto g->steps, for all three planners: refuses, at the node that planned it, a launch that states no read
+// or no write and one whose write overlaps its own read
+int append_steps(tamd_graph* g, const std::vector<Step>& launches);
 int count_consumers(const tamd_graph* g, int tensor);
 // the front and the tail that the NCHW planners (graph_u8.hip, graph_f32.hip) share: dense buffers of `esz` bytes per element for
 // inputs and tensors, views for Dropout / Flatten / Reshape and for channel-concat inputs that `in_place` allows; graph outputs
 int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place);
 int plan_nchw_outputs(tamd_graph* g, size_t esz);
-// a Sigmoid / Clip / HardSwish / Mish node of an int8 or uint8 graph as ONE launch (graph_plan.hip): table upload + lut_u8
-int plan_lut(tamd_graph* g, HNode& n, Step* out);
-// a nearest Interp node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch (graph_plan.hip): index vectors and byte map uploaded,
+// The byte-map node planners that both quantised graphs call (graph_plan_maps.hip); each hands its launches back in *out.
+// a Sigmoid / Clip / HardSwish / Mish node of an int8 or uint8 graph as ONE launch: table upload + lut_u8
+int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// a nearest Interp node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch: index vectors and byte map uploaded,
 // interp_nearest_i8 / interp_nearest_u8; reads and writes channel slices (concat views)
-int plan_interp(tamd_graph* g, HNode& n, Step* out);
-// Split / ShuffleChannel of a uint8 (NCHW) graph (graph_plan.hip): one chan_map_u8 launch per output tensor, the plane map and the
-// Split's byte map uploaded.  The int8 forms are planned inside graph_plan.hip
+int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// Split / ShuffleChannel of a uint8 (NCHW) graph: one chan_map_u8 launch per output tensor, the plane map and the
+// Split's byte map uploaded.  The int8 forms are declared in graph_plan.h
 int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
-int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out);
-// a PReLU node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch (graph_plan.hip): the slopes widened (int8) or one byte table per
+int plan_shuffle_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// a PReLU node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch: the slopes widened (int8) or one byte table per
 // channel built (uint8) and uploaded, prelu_i8 / prelu_u8 (prelu.hip)
-int plan_prelu(tamd_graph* g, HNode& n, Step* out);
+int plan_prelu(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // prelu_refusal (node_rules.h) asked of a node of this graph, payload included: validate_graph and plan_prelu
 const char* prelu_refusal_of(const tamd_graph* g, const HNode& n);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)

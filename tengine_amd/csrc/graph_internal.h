@@ -1,15 +1,18 @@
-// What the translation units of the graph layer share (private).  Since round 6 the layer is eight units instead of one:
+// What the translation units of the graph layer share (private).  The layer is ten units:
 //   graph.hip             the C ABI that builds, describes, pre-runs, profiles, reads and destroys a graph
 //   graph_infer.hip       shape inference, validation, the PriorBox evaluator, the error string
-//   graph_plan.hip        the int8 planner (arena, layout passes, one function per node kind, plan_i8: the one place that appends a
-//                         launch and checks what it says it reads and writes) and the node planners that plan_u8 shares (byte maps by
-//                         table, PReLU, nearest Interp, Split / ShuffleChannel)
+//   graph_plan_common.hip what every planner shares: dev_alloc (arena), tensor geometry, the NCHW planners' buffer front and output
+//                         tail, axis_split, conv_tap_table, and append_steps: the one place that appends a launch and checks what it
+//                         says it reads and writes
+//   graph_plan.hip        the int8 planner (layout passes, one function per node kind, plan_i8)
 //   graph_plan_conv.hip   .. its convolution / FC / pooling launches (requantisation folds, packers, one function per conv form)
-//   graph_plan_pairs.hip  .. its fusions (pwdw, chain4, dwpw, the bottleneck block); graph_plan.h is what those three share
+//   graph_plan_pairs.hip  .. its fusions (pwdw, chain4, dwpw, the bottleneck block)
+//   graph_plan_maps.hip   the byte-map node planners (tables, PReLU, nearest Interp, Split / ShuffleChannel), int8 and uint8 forms;
+//                         graph_plan.h is what the int8 units share
 //   plan_cache.hip        TAMD_PLAN_CACHE
 //   graph_pair.hip        a batched graph as two half-batch graphs side by side behind one handle (tamd_options.split_batch)
 //   graph_exec.hip        run_steps, the direct path's self-checks, zero-copy lists, the run-side entry points
-// (graph_u8.hip and graph_f32.hip are the uint8 / fp32 planners, as before.)
+//   graph_u8.hip, graph_f32.hip   the uint8 / fp32 planners (plan_u8, plan_f32): dense NCHW tensors
 // node_rules.h (through graph.h) states once the node-local rules that the support query, validate_graph and the planners share.
 #pragma once
 #include <mutex>

@@ -1,8 +1,9 @@
-// What the three units of the int8 planner share (graph_plan.hip, graph_plan_conv.hip, graph_plan_pairs.hip); private.
+// What the units of the int8 planner share (graph_plan.hip, graph_plan_conv.hip, graph_plan_pairs.hip, and the int8 side of
+// graph_plan_maps.hip); private.
 // Planned launches are values (Planned): a fuser is handed the launches of the nodes it covers, reads the constants they folded and
 // uploaded out of their kernel arguments, and builds its one launch with fused_step.  The rules every fuser shares are stated once
 // here: sole_reader (the one node behind a tensor), fused_step (the step of a launch that covers several nodes).  Every step says what
-// its launch reads and writes (graph.h: make_step); node functions hand their launches back and plan_i8 alone appends them.
+// its launch reads and writes (graph.h: make_step); node functions hand their launches back and plan_i8 alone appends them (append_steps).
 #pragma once
 #include <initializer_list>
 
@@ -34,6 +35,25 @@ struct FusedElt {            // an eltwise (+ReLU) node folded into the epilogue
     int out_tensor;          // where the result is stored: elt_tensor, or the ReLU's output when one follows
     int type;
     bool conv_is_first, relu;
+};
+
+// What the passes of plan_i8 hand on to each other, per tensor (layout) and per node (fusion).
+struct I8Layout {
+    // view_of / view_off: a concat input that lives in its concat's buffer at a channel offset; alias_of: an identity op's output
+    // (Dropout, Flatten, Reshape of a dense tensor); dense / perm_src / flat_concat: see plan_dense
+    std::vector<int> view_of, view_off, alias_of, perm_src;
+    std::vector<char> dense, flat_concat;
+    // fused[node]: planned inside another node's launch (skipped at its own position); has_fuse / fuse_at[node]: the convolution
+    // that takes an eltwise (+ReLU) into its epilogue
+    // cat_shuffle[node]: a channel Concat that runs together with the ShuffleChannel behind it, node index cat_shuffle[node] - 1
+    std::vector<char> fused, has_fuse;
+    std::vector<FusedElt> fuse_at;
+    std::vector<int> cat_shuffle;
+    // in_multi_cat[tensor]: written in place into the buffer of a Concat with SEVERAL inputs (plan_concat_views; plan_upsample: fix128)
+    std::vector<char> in_multi_cat;
+    I8Layout(size_t nt, size_t nn)
+        : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn),
+          cat_shuffle(nn, 0), in_multi_cat(nt, 0) {}
 };
 
 // One planned launch, as plan_conv / plan_pool hand it out: the step, which form it took, and that form's kernel arguments for a
@@ -78,6 +98,11 @@ inline Step fused_step(std::initializer_list<const Planned*> parts, const std::s
 // graph_plan_conv.hip.  One convolution / FC (as_fc) / pooling node as ONE launch, handed out in *out; fz: the eltwise tail it takes
 int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* out);
 int plan_pool(tamd_graph* g, HNode& n, Planned* out);
+
+// graph_plan_maps.hip.  Split, ShuffleChannel and Concat + ShuffleChannel (node sj) of an int8 graph: chan_map_i8 launches
+int plan_split(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out);
+int plan_shuffle(tamd_graph* g, HNode& n, std::vector<Step>* out);
+int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj, std::vector<Step>* out);
 
 // graph_plan_pairs.hip.  The fusers: 1 = *fused is the one launch for both, 0 = not fused, -1 = error
 int find_pwdw_tail(tamd_graph* g, size_t ni, int* tmode, int* prod);

@@ -1,6 +1,7 @@
-// The int8 planner: device buffers (arena), the layout passes, one function per node kind and plan_i8() itself -- node list ->
-// launch list (NHWC int8).  The convolution / FC / pooling launches are planned in graph_plan_conv.hip, the pair fusions
-// (pointwise + depthwise, depthwise + pointwise) in graph_plan_pairs.hip.
+// The int8 planner: I8Layout's passes (dense tensors, views, activation buffers), one function per node kind and plan_i8() itself --
+// node list -> launch list (NHWC int8).  The convolution / FC / pooling launches are planned in graph_plan_conv.hip, the pair fusions
+// (pointwise + depthwise, depthwise + pointwise) in graph_plan_pairs.hip, the byte-map nodes (tables, PReLU, Interp, Split,
+// ShuffleChannel) in graph_plan_maps.hip; what all three planners share (dev_alloc, append_steps, ..) is graph_plan_common.hip.
 #include "graph.h"
 #include "graph_internal.h"
 #include "env.h"
@@ -12,168 +13,6 @@
 #include "graph_plan.h"
 
 namespace tamd {
-
-// ---------------------------------------------------------------------------------------------
-// planner
-// ---------------------------------------------------------------------------------------------
-int dev_alloc(tamd_graph* g, void** p, size_t bytes, bool zero)
-{
-    // slack: the pointwise kernels read whole 64-byte K steps, up to 8 of them past a pixel row's last channel (those
-    // bytes meet zero weights, but must be readable behind the last pixel of a buffer too)
-    const size_t slack = 1024;
-    const char* ae = tamd_pin("arena");                       // 0: one hipMalloc per buffer (round 1-3 behaviour; A/B runs)
-    if (ae && atoi(ae) == 0) {
-        HIPCHK(hipMalloc(p, bytes + slack));
-        g->dev_allocs.push_back(*p);
-        if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes + slack, g->stream));    // never the legacy stream: it would collide with another thread's capture
-        return 0;
-    }
-    // bump allocation out of a few large chunks: a model's tensors, weights and per-channel vectors are hundreds of buffers, and
-    // as separate hipMalloc ranges each brings its own page-table fragment -- inside a pass every launch then begins with
-    // translation misses on memory it last touched a step ago.  One contiguous range per 32 MB .. 1 GB maps with large fragments.
-    const size_t need = (bytes + slack + 255) & ~(size_t)255;
-    DevArena* a = g->arenas.empty() ? nullptr : &g->arenas.back();
-    if (!a || a->used + need > a->cap) {
-        size_t cap = g->arenas.empty() ? ((size_t)32 << 20) : std::min<size_t>(2 * g->arenas.back().cap, (size_t)1 << 30);
-        cap = (std::max(cap, need) + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        DevArena na;
-        HIPCHK(hipMalloc((void**)&na.base, cap));
-        na.cap = cap;
-        g->dev_allocs.push_back(na.base);
-        g->arenas.push_back(na);
-        a = &g->arenas.back();
-    }
-    *p = a->base + a->used;
-    a->used += need;
-    if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes + slack, g->stream));
-    return 0;
-}
-
-void nhwc_geom(HTensor& t)
-{
-    if (t.dims.size() == 4) { t.n = t.dims[0]; t.c = t.dims[1]; t.h = t.dims[2]; t.w = t.dims[3]; }
-    else if (t.dims.size() == 2) { t.n = t.dims[0]; t.c = t.dims[1]; t.h = t.w = 1; }
-    else { t.n = 1; t.c = (int)t.elems(); t.h = t.w = 1; }
-}
-
-// The NCHW planners' front: every non-constant tensor is dense NCHW bytes (read_tensor / IO copy them as they are), `esz` bytes per
-// element.  Allocation order: the graph inputs in their order, then every remaining tensor that owns a buffer in index order.
-// concat-by-offset: a node whose only consumer is a channel concat writes its channels straight into the concat
-// output, and the concat launch disappears, where in_place(producer, input, concat output) says that it may.
-int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const HNode& producer, const HTensor& x, const HTensor& cat)>& in_place)
-{
-    for (auto& t : g->tensors) {
-        if (t.ttype == TAMD_TT_CONST) continue;
-        nhwc_geom(t);
-        t.nchw_raw = true;
-        t.cs = 0; t.c_off = 0;
-    }
-    std::vector<int> alias_of(g->tensors.size(), -1);
-    for (auto& n : g->nodes)
-        if (n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) alias_of[n.out[0]] = n.in[0];   // dense NCHW: views
-    for (auto& io : g->inputs) {
-        HTensor& t = g->tensors[io.tensor];
-        io.bytes = t.elems() * esz;
-        if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
-        t.dptr = io.stage;
-    }
-    std::vector<int> view_of(g->tensors.size(), -1), view_off(g->tensors.size(), 0);
-    for (auto& n : g->nodes) {
-        if (n.op != TAMD_OP_CONCAT) continue;
-        HTensor& y = g->tensors[n.out[0]];
-        const int ax = n.p.concat.axis < 0 ? n.p.concat.axis + (int)y.dims.size() : n.p.concat.axis;
-        int off = 0;
-        for (int i : n.in) {
-            HTensor& xi = g->tensors[i];
-            bool ok = ax == 1 && xi.ttype == TAMD_TT_VAR && count_consumers(g, i) == 1 && alias_of[i] < 0 && view_of[i] < 0;
-            if (ok) {
-                ok = false;
-                for (auto& pn : g->nodes)
-                    if (!pn.out.empty() && pn.out[0] == i) ok = in_place(pn, xi, y);
-            }
-            if (ok) { view_of[i] = n.out[0]; view_off[i] = off; }
-            off += xi.c;
-        }
-    }
-    for (size_t i = 0; i < g->tensors.size(); i++) {
-        HTensor& t = g->tensors[i];
-        if (t.ttype == TAMD_TT_CONST || t.dptr || alias_of[i] >= 0 || view_of[i] >= 0) continue;
-        if (dev_alloc(g, &t.dptr, t.elems() * esz, true)) return -1;
-    }
-    for (size_t i = 0; i < g->tensors.size(); i++)
-        if (view_of[i] >= 0) {
-            HTensor& t = g->tensors[i];
-            HTensor& o = g->tensors[view_of[i]];
-            if (!o.dptr) { set_error("concat of concat views is not supported"); return -1; }
-            t.dptr = o.dptr; t.is_view = true; t.c_off = view_off[i]; t.cs = o.c;      // cs: channels of the enclosing buffer
-        }
-    for (int pass = 0; pass < 4; pass++)
-        for (size_t i = 0; i < g->tensors.size(); i++)
-            if (alias_of[i] >= 0) g->tensors[i].dptr = g->tensors[alias_of[i]].dptr;
-    return 0;
-}
-
-int plan_nchw_outputs(tamd_graph* g, size_t esz)
-{
-    for (auto& io : g->outputs) {
-        HTensor& t = g->tensors[io.tensor];
-        io.bytes = t.elems() * esz;
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
-        io.stage = t.dptr;
-    }
-    return 0;
-}
-
-int count_consumers(const tamd_graph* g, int tensor)
-{
-    int c = 0;
-    for (auto& n : g->nodes)
-        for (int i : n.in) c += (i == tensor);
-    for (auto& o : g->outputs) c += (o.tensor == tensor);
-    return c;
-}
-
-int axis_split(const std::vector<int>& dims, int axis, const char* what, const std::string& node, AxisSplit* s)
-{
-    const int ax = axis < 0 ? axis + (int)dims.size() : axis;
-    if (ax < 0 || ax >= (int)dims.size()) { set_error("%s %s: bad axis", what, node.c_str()); return -1; }
-    *s = AxisSplit{};
-    s->axis = ax; s->on = dims[ax];
-    for (int d = 0; d < ax; d++) s->outer *= dims[d];
-    for (size_t d = ax + 1; d < dims.size(); d++) s->inner *= dims[d];
-    return 0;
-}
-
-std::vector<unsigned> conv_tap_table(int K, int Kpad, int H, int W, int KH, int KW, int DH, int DW)
-{
-    std::vector<unsigned> lut(Kpad, 0u);
-    for (int k = 0; k < K; k++) {
-        const int kx = k % KW, ky = (k / KW) % KH, c = k / (KW * KH);
-        lut[k] = (unsigned)(c * H * W + ky * DH * W + kx * DW) | (unsigned)(kx * DW) << 24 | (unsigned)(ky * DH) << 28;
-    }
-    return lut;
-}
-
-
-// What the passes of plan_i8 hand on to each other, per tensor (layout) and per node (fusion).
-struct I8Layout {
-    // view_of / view_off: a concat input that lives in its concat's buffer at a channel offset; alias_of: an identity op's output
-    // (Dropout, Flatten, Reshape of a dense tensor); dense / perm_src / flat_concat: see plan_dense
-    std::vector<int> view_of, view_off, alias_of, perm_src;
-    std::vector<char> dense, flat_concat;
-    // fused[node]: planned inside another node's launch (skipped at its own position); has_fuse / fuse_at[node]: the convolution
-    // that takes an eltwise (+ReLU) into its epilogue
-    // cat_shuffle[node]: a channel Concat that runs together with the ShuffleChannel behind it, node index cat_shuffle[node] - 1
-    std::vector<char> fused, has_fuse;
-    std::vector<FusedElt> fuse_at;
-    std::vector<int> cat_shuffle;
-    // in_multi_cat[tensor]: written in place into the buffer of a Concat with SEVERAL inputs (plan_concat_views; plan_upsample: fix128)
-    std::vector<char> in_multi_cat;
-    I8Layout(size_t nt, size_t nn)
-        : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn),
-          cat_shuffle(nn, 0), in_multi_cat(nt, 0) {}
-};
 
 // ---- DENSE tensors (the SSD head plumbing of an int8 graph).  The convolution stack lives in NHWC buffers
 // with padded channels; what Permute(0,2,3,1) / PriorBox produce, and everything that is only a re-reading of it (Flatten, Reshape,
@@ -495,13 +334,13 @@ static int resolve_views(tamd_graph* g, I8Layout& L)
                 t.dptr = o.dptr; t.cs = o.cs; t.c_off = o.c_off; t.is_view = o.is_view;
             }
         }
-    // input layout steps.  in_steps / out_steps state no accesses and are outside plan_i8's check: they move a graph input / output
+    // input layout steps.  in_steps / out_steps state no accesses and are outside append_steps' check: they move a graph input / output
     // between its staging buffer and its own NHWC buffer, and neither is ever shared (plan_buffers: pinned)
     for (auto& io : g->inputs) {
         HTensor& t = g->tensors[io.tensor];
         if (t.nchw_raw) continue;
         LayoutArgs a{io.stage, t.dptr, t.n, t.c, t.h, t.w, t.cs, esize(t.dtype)};
-        g->in_steps.push_back(make_step(t.name, "nchw_to_nhwc", 0, 0, [a](hipStream_t s) { return launch_nchw_to_nhwc(a, s); }));
+        g->in_steps.push_back(make_step(t.name, "nchw_to_nhwc", 0, 0, [a](hipStream_t s) { return launch_nchw_to_nhwc(a, s); }, {}, {}, false));
     }
     return 0;
 }
@@ -551,7 +390,7 @@ static Step dense_copy(tamd_graph* g, HNode& n, int kind, const char* kernel)
     FlatCatI8Args a{};
     a.nsrc = 1; a.y = (int8_t*)y.dptr; a.outer = x.n; a.out_row = x.c * x.h * x.w; a.row_begin = 0; a.row_len = a.out_row;
     a.src[0] = FlatCatI8Src{(const int8_t*)x.dptr + x.c_off, kind, a.out_row, x.c, x.h * x.w, x.cs, 0, 1.f, 1};
-    return make_step(n.name, kernel, 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, {access_of(x)}, {access_of(y)});
+    return make_step(n.name, kernel, 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, {access_of(x)}, {access_of(y)}, false);
 }
 
 // permute_ref.c:305-343, order (0, 2, 3, 1): a byte permutation -- written only when somebody reads it
@@ -634,7 +473,7 @@ static int plan_flat_concat(tamd_graph* g, I8Layout& L, HNode& n, std::vector<St
             bytes += 2.0 * outer * s.chunk;
         }
         a.row_len = begin - a.row_begin;
-        out->push_back(make_step(n.name, kernel, 0, bytes, [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, reads, {access_of(y)}));
+        out->push_back(make_step(n.name, kernel, 0, bytes, [a](hipStream_t s) { return launch_flatcat_i8(a, s); }, reads, {access_of(y)}, false));
         out->back().once = all_const;
     }
     if (begin != out_row) { set_error("concat %s: the inputs do not add up to the output", n.name.c_str()); return -1; }
@@ -657,7 +496,7 @@ static int plan_channel_concat(tamd_graph* g, I8Layout& L, HNode& n, std::vector
             a.identity = n.in.size() == 1;                      // :47-57: a single input is copied as it is
             // writes this input's slot of the output's pixels alone: the slots beside it may be views that are read here
             out->push_back(make_step(n.name, "concat_copy_i8", 0, 2.0 * a.pixels * x.c, [a](hipStream_t s) { return launch_concat_copy_i8(a, s); }, {access_of(x)},
-                                     {access_of_channels(y, off, x.c)}));
+                                     {access_of_channels(y, off, x.c)}, false));
         }
         off += x.c;
     }
@@ -838,7 +677,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>*
             a.is1 = (long)x.h * x.w * x.cs; a.os1 = (long)y.h * y.w * y.cs; a.is2 = x.cs; a.os2 = y.cs;
             a.istride = (long)x.w * x.cs; a.ostride = (long)y.w * y.cs;
         }
-        out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}));
+        out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
         return 0;
     }
     if (ax != 1 || (x.dims.size() != 2 && x.dims.size() != 4) || !softmax_i8_axis_fits(x.c)) {
@@ -857,7 +696,7 @@ static int plan_softmax(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>*
     a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr + y.c_off;
     a.positions = (long)x.n * x.h * x.w; a.C = x.c; a.cs_in = x.cs; a.cs_out = y.cs;
     a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-    out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * a.positions * x.c, [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}));
+    out->push_back(make_step(n.name, "softmax_i8", 0, 2.0 * a.positions * x.c, [a](hipStream_t s) { return launch_softmax_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
     return 0;
 }
 
@@ -887,7 +726,7 @@ static int try_relu_pool(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step
     a.p.x = (const int8_t*)x.dptr; a.p.cs_in = x.cs;
     a.slope = n.p.relu.negative_slope; a.relu_in_scale = x.scales[0];
     out->push_back(make_step(n.name + "+" + g->nodes[pool_node].name, "relu_pool_i8", 0, p.step.bytes, [a](hipStream_t s) { return launch_relu_pool(a, s); }, {access_of(x)},
-                             {access_of(g->tensors[g->nodes[pool_node].out[0]])}));
+                             {access_of(g->tensors[g->nodes[pool_node].out[0]])}, false));
     L.fused[pool_node] = 1;
     g->fused_away[n.out[0]] = 1;
     return 1;
@@ -902,352 +741,8 @@ static int plan_relu(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* o
     if (took) return took < 0 ? -1 : 0;
     if (x.is_view || y.is_view) { set_error("relu %s on a concat view is not supported", n.name.c_str()); return -1; }
     ReluArgs a{(const int8_t*)x.dptr, (int8_t*)y.dptr, (size_t)x.n * x.h * x.w * x.cs, n.p.relu.negative_slope, x.scales[0], y.scales[0]};
-    out->push_back(make_step(n.name, "relu_i8", 0, 2.0 * x.n * x.h * x.w * x.c, [a](hipStream_t s) { return launch_relu(a, s); }, {access_of(x)}, {access_of(y)}));
+    out->push_back(make_step(n.name, "relu_i8", 0, 2.0 * x.n * x.h * x.w * x.c, [a](hipStream_t s) { return launch_relu(a, s); }, {access_of(x)}, {access_of(y)}, false));
     return 0;
-}
-
-// Sigmoid / Clip / HardSwish / Mish, int8 and uint8 graphs alike (graph_u8.hip calls this too): the node's 256-entry byte map is built
-// on the host with the reference's arithmetic (lut_tables.cc), uploaded once here, and applied by one lut_u8 launch (misc_kernels.hip).
-// An NHWC int8 tensor with padding lanes (cs > c) is mapped channel by channel and its padding is written as zero; everything else --
-// uint8 tensors, dense int8 tensors, NHWC tensors without padding -- is a run of bytes.  A concat view is refused by name, as plan_relu
-// does: neither planner makes one of these nodes' tensors a view (plan_concat_views: slice_capable; plan_u8: in_place), so the error
-// guards a change to those lists.
-int plan_lut(tamd_graph* g, HNode& n, Step* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    const char* what = n.op == TAMD_OP_SIGMOID ? "sigmoid" : n.op == TAMD_OP_CLIP ? "clip" : n.op == TAMD_OP_HARDSWISH ? "hardswish" : "mish";
-    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
-    if (x.scales.empty() || y.scales.empty()) { set_error("%s %s: missing quant params", what, n.name.c_str()); return -1; }
-    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("%s %s: output shape / type mismatch", what, n.name.c_str()); return -1; }
-    if (!lut_rank_on_device(n.op, (int)x.dims.size())) { set_error("%s %s: only a 4-D tensor runs on the device", what, n.name.c_str()); return -1; }
-    const void* param = n.op == TAMD_OP_CLIP ? (const void*)&n.p.clip : n.op == TAMD_OP_HARDSWISH ? (const void*)&n.p.hardswish : nullptr;
-    std::vector<unsigned> table(64);
-    if (tamd_lut_table(n.op, x.dtype, param, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
-        set_error("%s %s: not supported on the device for data type %d", what, n.name.c_str(), x.dtype);
-        return -1;
-    }
-    unsigned* dtable = nullptr;
-    if (upload(g, table, &dtable)) return -1;
-    LutArgs a{};
-    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
-    const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
-    if (x_nhwc != y_nhwc || (x_nhwc && (x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off))) { set_error("%s %s: input and output layouts differ", what, n.name.c_str()); return -1; }
-    if (x_nhwc) {
-        a.count = (size_t)x.n * x.h * x.w * x.cs;
-        if (x.cs != x.c) { a.C = x.c; a.cs = x.cs; }
-    } else {
-        a.count = x.elems();
-    }
-    *out = make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)});
-    return 0;
-}
-
-const char* prelu_refusal_of(const tamd_graph* g, const HNode& n)
-{
-    if (n.in.size() != 2 || n.out.empty()) return "PReLU takes two inputs, the data and the slope";
-    const HTensor& x = g->tensors[n.in[0]];
-    const HTensor& sl = g->tensors[n.in[1]];
-    const bool payload = sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && sl.data.size() == sl.elems() * 2;
-    if (sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && !payload) return "PReLU: the slope's payload does not match its shape";
-    return prelu_refusal(x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), g->tensors[n.out[0]].scales.size(),
-                         sl.dtype, sl.ttype == TAMD_TT_CONST, sl.elems(), payload ? sl.data.data() : nullptr);
-}
-
-// PReLU, int8 and uint8 graphs alike (graph_u8.hip calls this too).  What the reference computes per channel is prepared HERE, once, on
-// the host (prelu_tables.cc): int8 -- NHWC, 16 channels in a lane's 16 bytes -- gets the slopes widened to fp32 by tamd_prelu_slope and
-// zero-padded to the pixel stride; uint8 -- dense NCHW, one slope per plane -- gets one 256-byte table per channel (one in all for a
-// shared slope) from tamd_prelu_table.  Uploaded once; one launch of prelu.hip.  A concat view on either side is refused by name, as in
-// plan_lut: neither planner makes a PReLU's tensors views (plan_concat_views: slice_capable; plan_u8: in_place)
-int plan_prelu(tamd_graph* g, HNode& n, Step* out)
-{
-    const char* why = prelu_refusal_of(g, n);
-    if (why) { set_error("prelu %s: %s", n.name.c_str(), why); return -1; }
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    const HTensor& sl = g->tensors[n.in[1]];
-    if (x.is_view || y.is_view) { set_error("prelu %s on a concat view is not supported", n.name.c_str()); return -1; }
-    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("prelu %s: output shape / type mismatch", n.name.c_str()); return -1; }
-    const unsigned short* half = (const unsigned short*)sl.data.data();
-    const size_t nslope = sl.elems();
-    const int C = x.dims[1];
-    if (x.dtype == TAMD_DT_INT8) {
-        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off || x.c != C || C > x.cs) {
-            set_error("prelu %s: input and output are not NHWC tensors of one pixel stride", n.name.c_str());
-            return -1;
-        }
-        std::vector<float> slope((size_t)x.cs, 0.f);
-        for (int c = 0; c < C; c++) slope[c] = tamd_prelu_slope(half[c]);
-        float* dslope = nullptr;
-        if (upload(g, slope, &dslope)) return -1;
-        PreluI8Args a{};
-        a.x = (const int8_t*)x.dptr; a.y = (int8_t*)y.dptr; a.count = (size_t)x.n * x.h * x.w * x.cs; a.C = C; a.cs = x.cs;
-        a.slope = dslope; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
-        *out = make_step(n.name, "prelu_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_i8(a, s); }, {access_of(x)}, {access_of(y)});
-    } else {
-        if (!x.nchw_raw || !y.nchw_raw) { set_error("prelu %s: input and output are not dense NCHW tensors", n.name.c_str()); return -1; }
-        const size_t ntab = nslope == 1 ? 1 : (size_t)C;
-        std::vector<unsigned> tables(ntab * 64);
-        for (size_t c = 0; c < ntab; c++)
-            if (tamd_prelu_table(x.dtype, half[c], x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)(tables.data() + c * 64))) {
-                set_error("prelu %s: PReLU: a slope widens to inf or NaN", n.name.c_str());
-                return -1;
-            }
-        unsigned* dtables = nullptr;
-        if (upload(g, tables, &dtables)) return -1;
-        PreluU8Args a{};
-        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.planes = (long)x.dims[0] * C; a.C = C; a.HW = x.dims[2] * x.dims[3];
-        a.tables = dtables; a.shared = nslope == 1 ? 1 : 0;
-        *out = make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); }, {access_of(x)}, {access_of(y)});
-    }
-    return 0;
-}
-
-// Nearest Interp, int8 and uint8 graphs alike (graph_u8.hip calls this too).  Everything the reference computes for the node is done
-// HERE, once: the scales and the output size (interp_resolve), the source row of every output row and the source column of every
-// output column (tamd_interp_indices), the byte map between the two tensors' quantisation parameters (tamd_interp_table) -- uploaded,
-// and one launch of interp.hip looks them up.  int8: NHWC with padded channel stride, reads a channel slice, writes one (a concat
-// view), like plan_upsample.  uint8: dense NCHW; writes a channel range of a concat buffer (out_img / out_c0), like plan_map_u8.
-int plan_interp(tamd_graph* g, HNode& n, Step* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    InterpGeom geom;
-    std::vector<int> iy, ix;
-    const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), &geom, &iy, &ix);
-    if (why) { set_error("interp %s: %s", n.name.c_str(), why); return -1; }
-    if (y.dtype != x.dtype || y.n != x.n || y.c != x.c || y.h != geom.out_h || y.w != geom.out_w) { set_error("interp %s: output shape / type mismatch", n.name.c_str()); return -1; }
-    std::vector<unsigned> table(64);
-    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
-        set_error("interp %s: not supported on the device for data type %d", n.name.c_str(), x.dtype);
-        return -1;
-    }
-    int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
-    if (upload(g, iy, &diy) || upload(g, ix, &dix) || upload(g, table, &dtable)) return -1;
-    const double bytes = 2.0 * (double)y.elems();
-    if (x.dtype == TAMD_DT_INT8) {
-        // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
-        const int cv = rup(x.c, 16);
-        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || y.cs <= 0 || x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + cv > x.cs || y.c_off + cv > y.cs) {
-            set_error("interp %s: channel slice not 16-byte aligned", n.name.c_str());
-            return -1;
-        }
-        InterpI8Args a{};
-        a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
-        a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs;
-        a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
-        a.iy = diy; a.ix = dix; a.table = dtable;
-        *out = make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); }, {access_of(x)}, {access_of(y)});
-    } else {
-        if (x.is_view) { set_error("interp %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
-        InterpU8Args a{};
-        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
-        a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w;
-        a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
-        a.iy = diy; a.ix = dix; a.table = dtable;
-        a.identity = 1;
-        for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
-        *out = make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)});
-    }
-    return 0;
-}
-
-// ---- Split, ShuffleChannel and Concat + ShuffleChannel of an int8 graph: chan_map_i8 (chanmap.hip).  ONE launch writes tensor y from
-// up to kChanMapMaxSrc source tensors; sel[o] = {source, channel of that source} for output channel o.  The table is built and checked
-// here -- every entry inside its source's pixel -- and uploaded once; sources and output are addressed where they lie (whole tensors,
-// concat views, Split views), the output's padding lanes are written as zero
-static int plan_chan_map_i8(tamd_graph* g, const std::string& node, const std::vector<const HTensor*>& srcs, const std::vector<std::pair<int, int>>& sel, HTensor& y,
-                            bool through_concat, Step* out)
-{
-    if (srcs.empty() || srcs.size() > (size_t)kChanMapMaxSrc || sel.size() != (size_t)y.c) { set_error("%s: at most %d sources, one entry per output channel", node.c_str(), kChanMapMaxSrc); return -1; }
-    const int cv = rup(y.c, 16);
-    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + cv > y.cs) { set_error("%s: output channel slice not 16-byte aligned", node.c_str()); return -1; }
-    ChanMapI8Args a{};
-    a.nsrc = (int)srcs.size();
-    for (size_t i = 0; i < srcs.size(); i++) {
-        const HTensor& x = *srcs[i];
-        if (x.dtype != TAMD_DT_INT8 || x.nchw_raw || x.cs <= 0 || !x.dptr || x.n != y.n || x.h != y.h || x.w != y.w || x.c_off + x.c > x.cs) {
-            set_error("%s: source %s is not an NHWC int8 tensor of the output's map", node.c_str(), x.name.c_str());
-            return -1;
-        }
-        a.src[i] = ChanMapI8Src{(const int8_t*)x.dptr, x.cs};
-    }
-    std::vector<unsigned> table((size_t)cv, kChanMapZero);
-    for (int o = 0; o < y.c; o++) {
-        const int s = sel[o].first, c = sel[o].second;
-        if (s < 0 || s >= a.nsrc || c < 0 || c >= srcs[s]->c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
-        table[o] = (unsigned)s << 28 | (unsigned)(srcs[s]->c_off + c);
-    }
-    unsigned* dtable = nullptr;
-    if (upload(g, table, &dtable)) return -1;
-    a.y = (int8_t*)y.dptr; a.pixels = (long)y.n * y.h * y.w; a.C = y.c; a.ldc = y.cs; a.c_off = y.c_off; a.table = dtable;
-    a.fix128 = through_concat ? 1 : 0;                      // a Concat of several inputs: -128 -> 127 (chanmap.hip)
-    std::vector<Access> reads;
-    for (const HTensor* x : srcs) reads.push_back(access_of(*x));
-    *out = make_step(node, "chan_map_i8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_i8(a, s); }, reads, {access_of(y)});
-    return 0;
-}
-
-// group 2 over two halves of equal width `half` -- channels [a0, a0 + half) of tensor a and [b0, b0 + half) of tensor b -- as the
-// interleave launch (chanmap.hip: chan_map_i8_g2) where both halves can be read in aligned 8-byte words inside their own pixels.
-// 1: *out is that launch, 0: the table form has to do it.  TAMD_PIN=chan_map_g2=0: always the table form (A/B runs, and the test that
-// demands the same bytes of both)
-static int try_chan_map_g2(tamd_graph* g, const std::string& node, const HTensor& a, int a0, const HTensor& b, int b0, int half, HTensor& y, bool through_concat,
-                           Step* out)
-{
-    if (!tamd_pin_int("chan_map_g2", 1) || y.c != 2 * half || half < 1) return 0;
-    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + rup(y.c, 16) > y.cs) return 0;
-    const int ra = a.c_off + a0, rb = b.c_off + b0, rv = rup(half, 8);
-    for (const HTensor* x : {&a, &b})
-        if (x->dtype != TAMD_DT_INT8 || x->nchw_raw || x->cs <= 0 || x->cs % 8 || !x->dptr || x->n != y.n || x->h != y.h || x->w != y.w) return 0;
-    if (a0 < 0 || b0 < 0 || a0 + half > a.c || b0 + half > b.c || ra % 8 || rb % 8 || ra + rv > a.cs || rb + rv > b.cs) return 0;
-    ChanMapG2Args k{};
-    k.a = (const int8_t*)a.dptr + ra; k.b = (const int8_t*)b.dptr + rb; k.cs_a = a.cs; k.cs_b = b.cs;
-    k.y = (int8_t*)y.dptr; k.pixels = (long)y.n * y.h * y.w; k.half = half; k.ldc = y.cs; k.c_off = y.c_off; k.fix128 = through_concat ? 1 : 0;
-    *out = make_step(node, "chan_map_i8_g2", 0, 2.0 * (double)y.elems(), [k](hipStream_t s) { return launch_chan_map_g2(k, s); }, {access_of(a), access_of(b)}, {access_of(y)});
-    return 1;
-}
-
-// split_ref.c:109-135: output i is channels [first_i, first_i + sizes[i]) of the input, bytes as they are.  An output that
-// plan_split_views made a view of the input has no launch; every other one is one chan_map_i8 launch with one source
-static int plan_split(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    std::vector<size_t> oq;
-    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
-    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
-    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
-    int first = 0;
-    for (size_t i = 0; i < n.out.size(); i++) {
-        HTensor& y = g->tensors[n.out[i]];
-        if (y.dtype != x.dtype || y.dims.size() != 4 || y.n != x.n || y.c != n.p.split.sizes[i] || y.h != x.h || y.w != x.w) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
-        if (!(L.view_of[n.out[i]] == n.in[0] && L.view_off[n.out[i]] == first)) {
-            std::vector<std::pair<int, int>> sel((size_t)y.c);
-            for (int c = 0; c < y.c; c++) sel[c] = {0, first + c};
-            Step st;
-            if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
-            out->push_back(st);
-        }
-        first += y.c;
-    }
-    return 0;
-}
-
-// shuffle_channel_ref.c: output channel group * j + i takes input channel (C / group) * i + j (tamd_shuffle_sources), bytes as they are
-static int shuffle_sources(const HNode& n, const HTensor& x, const HTensor& y, std::vector<int>* src)
-{
-    const char* why = shuffle_refusal(&n.p.shuffle, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size());
-    if (why) { set_error("shufflechannel %s: %s", n.name.c_str(), why); return -1; }
-    if (y.dtype != x.dtype || y.dims != x.dims) { set_error("shufflechannel %s: output shape / type mismatch", n.name.c_str()); return -1; }
-    src->resize((size_t)x.dims[1]);
-    if (tamd_shuffle_sources(x.dims[1], n.p.shuffle.group, src->data())) { set_error("shufflechannel %s: the group count must divide the channels", n.name.c_str()); return -1; }
-    return 0;
-}
-
-static int plan_shuffle(tamd_graph* g, HNode& n, std::vector<Step>* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    std::vector<int> src;
-    if (shuffle_sources(n, x, y, &src)) return -1;
-    std::vector<std::pair<int, int>> sel((size_t)y.c);
-    for (int o = 0; o < y.c; o++) sel[o] = {0, src[o]};
-    Step st;
-    if (!(n.p.shuffle.group == 2 && try_chan_map_g2(g, n.name, x, 0, x, x.c / 2, x.c / 2, y, false, &st)) && plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
-    out->push_back(st);
-    return 0;
-}
-
-// The pair match_cat_shuffle found, planned at the CONCAT's position: the launch reads the Concat's inputs and writes the
-// ShuffleChannel's output.  That output's lifetime starts at the earliest producer within two hops above the ShuffleChannel
-// (plan_buffers: shuffle <- concat <- the inputs' producers), so it never shares memory with an input; planned at the
-// ShuffleChannel's position an input's buffer could have been reused before it is read.  plan_i8 checks it (step_writes_what_it_reads)
-static int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj, std::vector<Step>* out)
-{
-    HNode& sh = g->nodes[sj];
-    HTensor& mid = g->tensors[cat.out[0]];
-    HTensor& y = g->tensors[sh.out[0]];
-    std::vector<int> src;
-    if (shuffle_sources(sh, mid, y, &src)) return -1;
-    std::vector<const HTensor*> srcs;
-    std::vector<int> begin;                                  // first Concat channel of every input
-    int total = 0;
-    for (int i : cat.in) { srcs.push_back(&g->tensors[i]); begin.push_back(total); total += g->tensors[i].c; }
-    if (total != mid.c) { set_error("concat %s: the inputs do not add up to the output", cat.name.c_str()); return -1; }
-    std::vector<std::pair<int, int>> sel((size_t)y.c);
-    for (int o = 0; o < y.c; o++) {
-        int k = (int)cat.in.size() - 1;
-        while (k > 0 && begin[k] > src[o]) k--;
-        sel[o] = {k, src[o] - begin[k]};
-    }
-    Step st;
-    const bool two_halves = sh.p.shuffle.group == 2 && srcs.size() == 2 && srcs[0]->c == srcs[1]->c;
-    if (!(two_halves && try_chan_map_g2(g, cat.name + "+" + sh.name, *srcs[0], 0, *srcs[1], 0, srcs[0]->c, y, true, &st))
-        && plan_chan_map_i8(g, cat.name + "+" + sh.name, srcs, sel, y, cat.in.size() > 1, &st))
-        return -1;
-    out->push_back(st);
-    L.fused[sj] = 1;
-    g->fused_away[cat.out[0]] = 1;
-    return 0;
-}
-
-// The uint8 forms (graph_u8.hip calls these): dense NCHW, one chan_map_u8 launch per output tensor.  Neither planner makes these
-// nodes' tensors concat views (plan_u8: in_place), which the errors below guard
-static int plan_chan_map_u8(tamd_graph* g, const std::string& node, const HTensor& x, const HTensor& y, const std::vector<int>& planes, const unsigned char* map,
-                            Step* out)
-{
-    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("%s on a concat view is not supported in a uint8 graph", node.c_str()); return -1; }
-    if (planes.size() != (size_t)y.c || y.n != x.n || y.h != x.h || y.w != x.w) { set_error("%s: output shape mismatch", node.c_str()); return -1; }
-    for (int p : planes)
-        if (p < 0 || p >= x.c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
-    ChanMapU8Args a{};
-    a.identity = 1;
-    std::vector<unsigned> table(64, 0u);
-    if (map) {
-        memcpy(table.data(), map, 256);
-        for (int b = 0; b < 256; b++) a.identity &= map[b] == b;
-    }
-    int* dplanes = nullptr; unsigned* dtable = nullptr;
-    if (upload(g, planes, &dplanes) || upload(g, table, &dtable)) return -1;
-    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
-    a.N = y.n; a.C = y.c; a.HW = y.h * y.w; a.in_img = x.c * x.h * x.w; a.in_planes = x.c;
-    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.src_plane = dplanes; a.table = dtable;
-    *out = make_step(node, "chan_map_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_u8(a, s); }, {access_of(x)}, {access_of(y)});
-    return 0;
-}
-
-// split_ref.c:68-107: output i is channels [first_i, ..) of the input, every byte through tamd_split_table between the two tensors'
-// parameters (the identity between equal ones: no lookups)
-int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    std::vector<size_t> oq;
-    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
-    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
-    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
-    int first = 0;
-    for (size_t i = 0; i < n.out.size(); i++) {
-        HTensor& y = g->tensors[n.out[i]];
-        if (y.dtype != x.dtype || y.dims.size() != 4 || y.c != n.p.split.sizes[i]) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
-        std::vector<int> planes((size_t)y.c);
-        for (int c = 0; c < y.c; c++) planes[c] = first + c;
-        unsigned char map[256];
-        if (tamd_split_table(x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], map)) { set_error("split %s: no byte map", n.name.c_str()); return -1; }
-        Step st;
-        if (plan_chan_map_u8(g, n.name, x, y, planes, map, &st)) return -1;
-        out->push_back(st);
-        first += y.c;
-    }
-    return 0;
-}
-
-int plan_shuffle_u8(tamd_graph* g, HNode& n, Step* out)
-{
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    std::vector<int> src;
-    if (shuffle_sources(n, x, y, &src)) return -1;
-    return plan_chan_map_u8(g, n.name, x, y, src, nullptr, out);
 }
 
 // upsample_ref.c:74-130 on the int8 bytes (misc_kernels.hip: upsample_i8); reads a channel slice, writes one (a concat view)
@@ -1276,7 +771,7 @@ static int plan_upsample(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>
     // Concat is its one reader: anyone else reads the Upsample's own bytes, -128 included.
     a.fix128 = L.in_multi_cat[n.out[0]] ? 1 : 0;
     out->push_back(make_step(n.name, "upsample_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_upsample_i8(a, s); },
-                             {access_of(x)}, {access_of(y)}));
+                             {access_of(x)}, {access_of(y)}, false));
     return 0;
 }
 
@@ -1301,7 +796,7 @@ static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>*
         g->fused_away[n.out[0]] = 1;
     }
     a.y = (int8_t*)y->dptr;
-    out->push_back(make_step(n.name, kname, 0, bytes, [a](hipStream_t s) { return launch_eltwise(a, s); }, {access_of(xa), access_of(xb)}, {access_of(*y)}));
+    out->push_back(make_step(n.name, kname, 0, bytes, [a](hipStream_t s) { return launch_eltwise(a, s); }, {access_of(xa), access_of(xb)}, {access_of(*y)}, false));
     return 0;
 }
 
@@ -1316,33 +811,14 @@ static int plan_outputs(tamd_graph* g)
         if (t.h * t.w == 1 && t.cs == t.c && t.c_off == 0) { io.stage = t.dptr; continue; }
         if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
         LayoutArgs a{(const int8_t*)t.dptr + t.c_off, io.stage, t.n, t.c, t.h, t.w, t.cs, esize(t.dtype)};
-        g->out_steps.push_back(make_step(t.name, "nhwc_to_nchw", 0, 0, [a](hipStream_t s) { return launch_nhwc_to_nchw(a, s); }));     // (no accesses: resolve_views)
-    }
-    return 0;
-}
-
-// The one place a launch goes onto g->steps.  Every compute launch of an int8 graph reads and writes some activation and says so
-// (graph.h: make_step), and a launch that writes what it reads is an error: a fused launch runs at its first node's position -- chain4
-// and ReLU + pool even ahead of node order, a convolution's eltwise tail and eltwise + ReLU a node or two ahead -- and writes its output
-// while other blocks still read its input; only plan_buffers' birth rule keeps the two out of one shared buffer
-static int append_steps(tamd_graph* g, const std::vector<Step>& launches)
-{
-    for (auto& st : launches) {
-        if (step_states_nothing(st)) {
-            set_error("launch %s (%s) does not state what it reads and writes", st.kernel.c_str(), st.node.c_str());
-            return -1;
-        }
-        if (step_writes_what_it_reads(st)) {
-            set_error("launch %s (%s) writes memory that it reads: its output shares a buffer with its input", st.kernel.c_str(), st.node.c_str());
-            return -1;
-        }
-        g->steps.push_back(st);
+        g->out_steps.push_back(make_step(t.name, "nhwc_to_nchw", 0, 0, [a](hipStream_t s) { return launch_nhwc_to_nchw(a, s); }, {}, {}, false));     // (no accesses: resolve_views)
     }
     return 0;
 }
 
 // node list -> launch list: the layout passes in order, then one planner per node.  A node function hands its launches back in `out`
-// (none for a node that is a view, runs inside another node's launch or -- PriorBox -- is evaluated here) and pushes nothing itself
+// (none for a node that is a view, runs inside another node's launch or -- PriorBox -- is evaluated here) and pushes nothing itself;
+// append_steps (graph_plan_common.hip) checks what each says it reads and writes
 int plan_i8(tamd_graph* g)
 {
     for (auto& t : g->tensors) if (t.ttype != TAMD_TT_CONST) nhwc_geom(t);
@@ -1357,7 +833,6 @@ int plan_i8(tamd_graph* g)
         if (L.fused[ni]) continue;
         std::vector<Step> out;
         Planned one;                 // FC / pooling: a single launch as plan_conv / plan_pool hand it to the fusers
-        Step st;                     // .. and as the planners that plan_u8 shares hand it out
         int r = 0;
         switch (n.op) {
         case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_DROPOUT: case TAMD_OP_FLATTEN: break;
@@ -1375,11 +850,11 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_RELU: r = plan_relu(g, L, ni, &out); break;
         case TAMD_OP_UPSAMPLE: r = plan_upsample(g, L, n, &out); break;
         case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, &out); break;
-        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: if (!(r = plan_lut(g, n, &st))) out.push_back(st); break;
-        case TAMD_OP_INTERP: if (!(r = plan_interp(g, n, &st))) out.push_back(st); break;
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: r = plan_lut(g, n, &out); break;
+        case TAMD_OP_INTERP: r = plan_interp(g, n, &out); break;
         case TAMD_OP_SPLIT: r = plan_split(g, L, n, &out); break;
         case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n, &out); break;
-        case TAMD_OP_PRELU: if (!(r = plan_prelu(g, n, &st))) out.push_back(st); break;
+        case TAMD_OP_PRELU: r = plan_prelu(g, n, &out); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

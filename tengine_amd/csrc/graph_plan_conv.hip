@@ -482,7 +482,7 @@ int plan_conv(tamd_graph* g, HNode& n, bool as_fc, const FusedElt* fz, Planned* 
     // the step without kernel and launch, which the form fills in.  Constants aside, all a convolution / FC launch touches is its input
     // and its output; with an eltwise tail (a GEMM form always: scan_eltwise_fusion) it also reads the other operand and stores the
     // tail's output instead of its own, and stays ordered
-    if (fz) out->step = make_step(n.name, "", c.macs, c.bytes, nullptr, {access_of(c.x), access_of(g->tensors[fz->res_tensor])}, {access_of(g->tensors[fz->out_tensor])});
+    if (fz) out->step = make_step(n.name, "", c.macs, c.bytes, nullptr, {access_of(c.x), access_of(g->tensors[fz->res_tensor])}, {access_of(g->tensors[fz->out_tensor])}, false);
     else out->step = make_step(n.name, "", c.macs, c.bytes, nullptr, {access_of(c.x)}, {access_of(c.y)}, true);
     out->elt_tail = fz != nullptr;
     switch (conv_i8_form(c)) {
@@ -508,7 +508,7 @@ int plan_pool(tamd_graph* g, HNode& n, Planned* out)
     out->kind = Planned::POOL; out->pool = a;
     // (x and y may be channel slices of ONE concat buffer -- concat(x, pool(x), ..) -- which access_overlap tells apart)
     out->step = make_step(n.name, "pool_i8", 0, (double)x.n * x.h * x.w * x.c + (double)y.n * y.h * y.w * y.c, [a](hipStream_t s) { return launch_pool(a, s); },
-                          {access_of(x)}, {access_of(y)});
+                          {access_of(x)}, {access_of(y)}, false);
     return 0;
 }
 

@@ -1,0 +1,362 @@
+// The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
+// table (plan_lut), PReLU, nearest Interp, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu and plan_interp
+// serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
+// graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
+#include "graph.h"
+#include "graph_internal.h"
+#include "env.h"
+
+#include <cstring>
+
+#include "graph_plan.h"
+
+namespace tamd {
+
+// Sigmoid / Clip / HardSwish / Mish, int8 and uint8 graphs alike (graph_u8.hip calls this too): the node's 256-entry byte map is built
+// on the host with the reference's arithmetic (lut_tables.cc), uploaded once here, and applied by one lut_u8 launch (misc_kernels.hip).
+// An NHWC int8 tensor with padding lanes (cs > c) is mapped channel by channel and its padding is written as zero; everything else --
+// uint8 tensors, dense int8 tensors, NHWC tensors without padding -- is a run of bytes.  A concat view is refused by name, as plan_relu
+// does: neither planner makes one of these nodes' tensors a view (plan_concat_views: slice_capable; plan_u8: in_place), so the error
+// guards a change to those lists.
+int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const char* what = n.op == TAMD_OP_SIGMOID ? "sigmoid" : n.op == TAMD_OP_CLIP ? "clip" : n.op == TAMD_OP_HARDSWISH ? "hardswish" : "mish";
+    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
+    if (x.scales.empty() || y.scales.empty()) { set_error("%s %s: missing quant params", what, n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("%s %s: output shape / type mismatch", what, n.name.c_str()); return -1; }
+    if (!lut_rank_on_device(n.op, (int)x.dims.size())) { set_error("%s %s: only a 4-D tensor runs on the device", what, n.name.c_str()); return -1; }
+    const void* param = n.op == TAMD_OP_CLIP ? (const void*)&n.p.clip : n.op == TAMD_OP_HARDSWISH ? (const void*)&n.p.hardswish : nullptr;
+    std::vector<unsigned> table(64);
+    if (tamd_lut_table(n.op, x.dtype, param, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
+        set_error("%s %s: not supported on the device for data type %d", what, n.name.c_str(), x.dtype);
+        return -1;
+    }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    LutArgs a{};
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
+    const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
+    if (x_nhwc != y_nhwc || (x_nhwc && (x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off))) { set_error("%s %s: input and output layouts differ", what, n.name.c_str()); return -1; }
+    if (x_nhwc) {
+        a.count = (size_t)x.n * x.h * x.w * x.cs;
+        if (x.cs != x.c) { a.C = x.c; a.cs = x.cs; }
+    } else {
+        a.count = x.elems();
+    }
+    out->push_back(make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
+const char* prelu_refusal_of(const tamd_graph* g, const HNode& n)
+{
+    if (n.in.size() != 2 || n.out.empty()) return "PReLU takes two inputs, the data and the slope";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& sl = g->tensors[n.in[1]];
+    const bool payload = sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && sl.data.size() == sl.elems() * 2;
+    if (sl.ttype == TAMD_TT_CONST && sl.dtype == TAMD_DT_FP16 && !payload) return "PReLU: the slope's payload does not match its shape";
+    return prelu_refusal(x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), g->tensors[n.out[0]].scales.size(),
+                         sl.dtype, sl.ttype == TAMD_TT_CONST, sl.elems(), payload ? sl.data.data() : nullptr);
+}
+
+// PReLU, int8 and uint8 graphs alike (graph_u8.hip calls this too).  What the reference computes per channel is prepared HERE, once, on
+// the host (prelu_tables.cc): int8 -- NHWC, 16 channels in a lane's 16 bytes -- gets the slopes widened to fp32 by tamd_prelu_slope and
+// zero-padded to the pixel stride; uint8 -- dense NCHW, one slope per plane -- gets one 256-byte table per channel (one in all for a
+// shared slope) from tamd_prelu_table.  Uploaded once; one launch of prelu.hip.  A concat view on either side is refused by name, as in
+// plan_lut: neither planner makes a PReLU's tensors views (plan_concat_views: slice_capable; plan_u8: in_place)
+int plan_prelu(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    const char* why = prelu_refusal_of(g, n);
+    if (why) { set_error("prelu %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const HTensor& sl = g->tensors[n.in[1]];
+    if (x.is_view || y.is_view) { set_error("prelu %s on a concat view is not supported", n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("prelu %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const unsigned short* half = (const unsigned short*)sl.data.data();
+    const size_t nslope = sl.elems();
+    const int C = x.dims[1];
+    if (x.dtype == TAMD_DT_INT8) {
+        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off || x.c != C || C > x.cs) {
+            set_error("prelu %s: input and output are not NHWC tensors of one pixel stride", n.name.c_str());
+            return -1;
+        }
+        std::vector<float> slope((size_t)x.cs, 0.f);
+        for (int c = 0; c < C; c++) slope[c] = tamd_prelu_slope(half[c]);
+        float* dslope = nullptr;
+        if (upload(g, slope, &dslope)) return -1;
+        PreluI8Args a{};
+        a.x = (const int8_t*)x.dptr; a.y = (int8_t*)y.dptr; a.count = (size_t)x.n * x.h * x.w * x.cs; a.C = C; a.cs = x.cs;
+        a.slope = dslope; a.in_scale = x.scales[0]; a.out_scale = y.scales[0];
+        out->push_back(make_step(n.name, "prelu_i8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    } else {
+        if (!x.nchw_raw || !y.nchw_raw) { set_error("prelu %s: input and output are not dense NCHW tensors", n.name.c_str()); return -1; }
+        const size_t ntab = nslope == 1 ? 1 : (size_t)C;
+        std::vector<unsigned> tables(ntab * 64);
+        for (size_t c = 0; c < ntab; c++)
+            if (tamd_prelu_table(x.dtype, half[c], x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)(tables.data() + c * 64))) {
+                set_error("prelu %s: PReLU: a slope widens to inf or NaN", n.name.c_str());
+                return -1;
+            }
+        unsigned* dtables = nullptr;
+        if (upload(g, tables, &dtables)) return -1;
+        PreluU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.planes = (long)x.dims[0] * C; a.C = C; a.HW = x.dims[2] * x.dims[3];
+        a.tables = dtables; a.shared = nslope == 1 ? 1 : 0;
+        out->push_back(make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    }
+    return 0;
+}
+
+// Nearest Interp, int8 and uint8 graphs alike (graph_u8.hip calls this too).  Everything the reference computes for the node is done
+// HERE, once: the scales and the output size (interp_resolve), the source row of every output row and the source column of every
+// output column (tamd_interp_indices), the byte map between the two tensors' quantisation parameters (tamd_interp_table) -- uploaded,
+// and one launch of interp.hip looks them up.  int8: NHWC with padded channel stride, reads a channel slice, writes one (a concat
+// view), like plan_upsample.  uint8: dense NCHW; writes a channel range of a concat buffer (out_img / out_c0), like plan_map_u8.
+int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    InterpGeom geom;
+    std::vector<int> iy, ix;
+    const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), &geom, &iy, &ix);
+    if (why) { set_error("interp %s: %s", n.name.c_str(), why); return -1; }
+    if (y.dtype != x.dtype || y.n != x.n || y.c != x.c || y.h != geom.out_h || y.w != geom.out_w) { set_error("interp %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    std::vector<unsigned> table(64);
+    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
+        set_error("interp %s: not supported on the device for data type %d", n.name.c_str(), x.dtype);
+        return -1;
+    }
+    int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, iy, &diy) || upload(g, ix, &dix) || upload(g, table, &dtable)) return -1;
+    const double bytes = 2.0 * (double)y.elems();
+    if (x.dtype == TAMD_DT_INT8) {
+        // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
+        const int cv = rup(x.c, 16);
+        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || y.cs <= 0 || x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + cv > x.cs || y.c_off + cv > y.cs) {
+            set_error("interp %s: channel slice not 16-byte aligned", n.name.c_str());
+            return -1;
+        }
+        InterpI8Args a{};
+        a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+        a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs;
+        a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
+        a.iy = diy; a.ix = dix; a.table = dtable;
+        out->push_back(make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    } else {
+        if (x.is_view) { set_error("interp %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
+        InterpU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+        a.N = x.n; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w;
+        a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+        a.iy = diy; a.ix = dix; a.table = dtable;
+        a.identity = 1;
+        for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
+        out->push_back(make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    }
+    return 0;
+}
+
+// ---- Split, ShuffleChannel and Concat + ShuffleChannel of an int8 graph: chan_map_i8 (chanmap.hip).  ONE launch writes tensor y from
+// up to kChanMapMaxSrc source tensors; sel[o] = {source, channel of that source} for output channel o.  The table is built and checked
+// here -- every entry inside its source's pixel -- and uploaded once; sources and output are addressed where they lie (whole tensors,
+// concat views, Split views), the output's padding lanes are written as zero
+static int plan_chan_map_i8(tamd_graph* g, const std::string& node, const std::vector<const HTensor*>& srcs, const std::vector<std::pair<int, int>>& sel, HTensor& y,
+                            bool through_concat, Step* out)
+{
+    if (srcs.empty() || srcs.size() > (size_t)kChanMapMaxSrc || sel.size() != (size_t)y.c) { set_error("%s: at most %d sources, one entry per output channel", node.c_str(), kChanMapMaxSrc); return -1; }
+    const int cv = rup(y.c, 16);
+    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + cv > y.cs) { set_error("%s: output channel slice not 16-byte aligned", node.c_str()); return -1; }
+    ChanMapI8Args a{};
+    a.nsrc = (int)srcs.size();
+    for (size_t i = 0; i < srcs.size(); i++) {
+        const HTensor& x = *srcs[i];
+        if (x.dtype != TAMD_DT_INT8 || x.nchw_raw || x.cs <= 0 || !x.dptr || x.n != y.n || x.h != y.h || x.w != y.w || x.c_off + x.c > x.cs) {
+            set_error("%s: source %s is not an NHWC int8 tensor of the output's map", node.c_str(), x.name.c_str());
+            return -1;
+        }
+        a.src[i] = ChanMapI8Src{(const int8_t*)x.dptr, x.cs};
+    }
+    std::vector<unsigned> table((size_t)cv, kChanMapZero);
+    for (int o = 0; o < y.c; o++) {
+        const int s = sel[o].first, c = sel[o].second;
+        if (s < 0 || s >= a.nsrc || c < 0 || c >= srcs[s]->c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
+        table[o] = (unsigned)s << 28 | (unsigned)(srcs[s]->c_off + c);
+    }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    a.y = (int8_t*)y.dptr; a.pixels = (long)y.n * y.h * y.w; a.C = y.c; a.ldc = y.cs; a.c_off = y.c_off; a.table = dtable;
+    a.fix128 = through_concat ? 1 : 0;                      // a Concat of several inputs: -128 -> 127 (chanmap.hip)
+    std::vector<Access> reads;
+    for (const HTensor* x : srcs) reads.push_back(access_of(*x));
+    *out = make_step(node, "chan_map_i8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_i8(a, s); }, reads, {access_of(y)}, false);
+    return 0;
+}
+
+// group 2 over two halves of equal width `half` -- channels [a0, a0 + half) of tensor a and [b0, b0 + half) of tensor b -- as the
+// interleave launch (chanmap.hip: chan_map_i8_g2) where both halves can be read in aligned 8-byte words inside their own pixels.
+// 1: *out is that launch, 0: the table form has to do it.  TAMD_PIN=chan_map_g2=0: always the table form (A/B runs, and the test that
+// demands the same bytes of both)
+static int try_chan_map_g2(tamd_graph* g, const std::string& node, const HTensor& a, int a0, const HTensor& b, int b0, int half, HTensor& y, bool through_concat,
+                           Step* out)
+{
+    if (!tamd_pin_int("chan_map_g2", 1) || y.c != 2 * half || half < 1) return 0;
+    if (y.dtype != TAMD_DT_INT8 || y.nchw_raw || y.cs <= 0 || y.cs % 16 || y.c_off % 16 || y.c_off + rup(y.c, 16) > y.cs) return 0;
+    const int ra = a.c_off + a0, rb = b.c_off + b0, rv = rup(half, 8);
+    for (const HTensor* x : {&a, &b})
+        if (x->dtype != TAMD_DT_INT8 || x->nchw_raw || x->cs <= 0 || x->cs % 8 || !x->dptr || x->n != y.n || x->h != y.h || x->w != y.w) return 0;
+    if (a0 < 0 || b0 < 0 || a0 + half > a.c || b0 + half > b.c || ra % 8 || rb % 8 || ra + rv > a.cs || rb + rv > b.cs) return 0;
+    ChanMapG2Args k{};
+    k.a = (const int8_t*)a.dptr + ra; k.b = (const int8_t*)b.dptr + rb; k.cs_a = a.cs; k.cs_b = b.cs;
+    k.y = (int8_t*)y.dptr; k.pixels = (long)y.n * y.h * y.w; k.half = half; k.ldc = y.cs; k.c_off = y.c_off; k.fix128 = through_concat ? 1 : 0;
+    *out = make_step(node, "chan_map_i8_g2", 0, 2.0 * (double)y.elems(), [k](hipStream_t s) { return launch_chan_map_g2(k, s); }, {access_of(a), access_of(b)}, {access_of(y)}, false);
+    return 1;
+}
+
+// split_ref.c:109-135: output i is channels [first_i, first_i + sizes[i]) of the input, bytes as they are.  An output that
+// plan_split_views made a view of the input has no launch; every other one is one chan_map_i8 launch with one source
+int plan_split(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    std::vector<size_t> oq;
+    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
+    int first = 0;
+    for (size_t i = 0; i < n.out.size(); i++) {
+        HTensor& y = g->tensors[n.out[i]];
+        if (y.dtype != x.dtype || y.dims.size() != 4 || y.n != x.n || y.c != n.p.split.sizes[i] || y.h != x.h || y.w != x.w) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
+        if (!(L.view_of[n.out[i]] == n.in[0] && L.view_off[n.out[i]] == first)) {
+            std::vector<std::pair<int, int>> sel((size_t)y.c);
+            for (int c = 0; c < y.c; c++) sel[c] = {0, first + c};
+            Step st;
+            if (plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
+            out->push_back(st);
+        }
+        first += y.c;
+    }
+    return 0;
+}
+
+// shuffle_channel_ref.c: output channel group * j + i takes input channel (C / group) * i + j (tamd_shuffle_sources), bytes as they are
+static int shuffle_sources(const HNode& n, const HTensor& x, const HTensor& y, std::vector<int>* src)
+{
+    const char* why = shuffle_refusal(&n.p.shuffle, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size());
+    if (why) { set_error("shufflechannel %s: %s", n.name.c_str(), why); return -1; }
+    if (y.dtype != x.dtype || y.dims != x.dims) { set_error("shufflechannel %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    src->resize((size_t)x.dims[1]);
+    if (tamd_shuffle_sources(x.dims[1], n.p.shuffle.group, src->data())) { set_error("shufflechannel %s: the group count must divide the channels", n.name.c_str()); return -1; }
+    return 0;
+}
+
+int plan_shuffle(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(n, x, y, &src)) return -1;
+    std::vector<std::pair<int, int>> sel((size_t)y.c);
+    for (int o = 0; o < y.c; o++) sel[o] = {0, src[o]};
+    Step st;
+    if (!(n.p.shuffle.group == 2 && try_chan_map_g2(g, n.name, x, 0, x, x.c / 2, x.c / 2, y, false, &st)) && plan_chan_map_i8(g, n.name, {&x}, sel, y, false, &st)) return -1;
+    out->push_back(st);
+    return 0;
+}
+
+// The pair match_cat_shuffle found, planned at the CONCAT's position: the launch reads the Concat's inputs and writes the
+// ShuffleChannel's output.  That output's lifetime starts at the earliest producer within two hops above the ShuffleChannel
+// (plan_buffers: shuffle <- concat <- the inputs' producers), so it never shares memory with an input; planned at the
+// ShuffleChannel's position an input's buffer could have been reused before it is read.  plan_i8 checks it (step_writes_what_it_reads)
+int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj, std::vector<Step>* out)
+{
+    HNode& sh = g->nodes[sj];
+    HTensor& mid = g->tensors[cat.out[0]];
+    HTensor& y = g->tensors[sh.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(sh, mid, y, &src)) return -1;
+    std::vector<const HTensor*> srcs;
+    std::vector<int> begin;                                  // first Concat channel of every input
+    int total = 0;
+    for (int i : cat.in) { srcs.push_back(&g->tensors[i]); begin.push_back(total); total += g->tensors[i].c; }
+    if (total != mid.c) { set_error("concat %s: the inputs do not add up to the output", cat.name.c_str()); return -1; }
+    std::vector<std::pair<int, int>> sel((size_t)y.c);
+    for (int o = 0; o < y.c; o++) {
+        int k = (int)cat.in.size() - 1;
+        while (k > 0 && begin[k] > src[o]) k--;
+        sel[o] = {k, src[o] - begin[k]};
+    }
+    Step st;
+    const bool two_halves = sh.p.shuffle.group == 2 && srcs.size() == 2 && srcs[0]->c == srcs[1]->c;
+    if (!(two_halves && try_chan_map_g2(g, cat.name + "+" + sh.name, *srcs[0], 0, *srcs[1], 0, srcs[0]->c, y, true, &st))
+        && plan_chan_map_i8(g, cat.name + "+" + sh.name, srcs, sel, y, cat.in.size() > 1, &st))
+        return -1;
+    out->push_back(st);
+    L.fused[sj] = 1;
+    g->fused_away[cat.out[0]] = 1;
+    return 0;
+}
+
+// The uint8 forms (graph_u8.hip calls these): dense NCHW, one chan_map_u8 launch per output tensor.  Neither planner makes these
+// nodes' tensors concat views (plan_u8: in_place), which the errors below guard
+static int plan_chan_map_u8(tamd_graph* g, const std::string& node, const HTensor& x, const HTensor& y, const std::vector<int>& planes, const unsigned char* map,
+                            Step* out)
+{
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("%s on a concat view is not supported in a uint8 graph", node.c_str()); return -1; }
+    if (planes.size() != (size_t)y.c || y.n != x.n || y.h != x.h || y.w != x.w) { set_error("%s: output shape mismatch", node.c_str()); return -1; }
+    for (int p : planes)
+        if (p < 0 || p >= x.c) { set_error("%s: a source channel leaves its tensor", node.c_str()); return -1; }
+    ChanMapU8Args a{};
+    a.identity = 1;
+    std::vector<unsigned> table(64, 0u);
+    if (map) {
+        memcpy(table.data(), map, 256);
+        for (int b = 0; b < 256; b++) a.identity &= map[b] == b;
+    }
+    int* dplanes = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, planes, &dplanes) || upload(g, table, &dtable)) return -1;
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+    a.N = y.n; a.C = y.c; a.HW = y.h * y.w; a.in_img = x.c * x.h * x.w; a.in_planes = x.c;
+    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.src_plane = dplanes; a.table = dtable;
+    *out = make_step(node, "chan_map_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_chan_map_u8(a, s); }, {access_of(x)}, {access_of(y)}, false);
+    return 0;
+}
+
+// split_ref.c:68-107: output i is channels [first_i, ..) of the input, every byte through tamd_split_table between the two tensors'
+// parameters (the identity between equal ones: no lookups)
+int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    std::vector<size_t> oq;
+    for (int o : n.out) oq.push_back(g->tensors[o].scales.size());
+    const char* why = split_refusal(&n.p.split, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)n.out.size(), oq.data());
+    if (why) { set_error("split %s: %s", n.name.c_str(), why); return -1; }
+    int first = 0;
+    for (size_t i = 0; i < n.out.size(); i++) {
+        HTensor& y = g->tensors[n.out[i]];
+        if (y.dtype != x.dtype || y.dims.size() != 4 || y.c != n.p.split.sizes[i]) { set_error("split %s: output shape / type mismatch", n.name.c_str()); return -1; }
+        std::vector<int> planes((size_t)y.c);
+        for (int c = 0; c < y.c; c++) planes[c] = first + c;
+        unsigned char map[256];
+        if (tamd_split_table(x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], map)) { set_error("split %s: no byte map", n.name.c_str()); return -1; }
+        Step st;
+        if (plan_chan_map_u8(g, n.name, x, y, planes, map, &st)) return -1;
+        out->push_back(st);
+        first += y.c;
+    }
+    return 0;
+}
+
+int plan_shuffle_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    std::vector<int> src;
+    if (shuffle_sources(n, x, y, &src)) return -1;
+    Step st;
+    if (plan_chan_map_u8(g, n.name, x, y, src, nullptr, &st)) return -1;
+    out->push_back(st);
+    return 0;
+}
+
+}  // namespace tamd

@@ -8,8 +8,8 @@
 //   conv (grouped)  weights -> fp32 as conv_kernel_ref_uint8.c:82-86, OIHW kept
 //   fc              weights -> fp32 as fc_ref.c:150-160, transposed to [hidden][nout_pad]
 //
-// Structure: plan_u8 walks the nodes and calls one function per node kind; each hands back the launches it planned and plan_u8
-// alone appends them to g->steps.  A convolution is a ConvU8 (the node's tensors, quantisation, fused tail, bias, step skeleton)
+// Structure: plan_u8 walks the nodes and calls one function per node kind; each hands back the launches it planned, every one stating
+// what it reads and writes (graph.h: make_step), and plan_u8 alone appends them through append_steps.  A convolution is a ConvU8 (the node's tensors, quantisation, fused tail, bias, step skeleton)
 // that one of four forms turns into a launch: conv_u8_dma, conv_u8_int, conv_u8_exact, conv_u8_direct.
 #include <hip/hip_runtime.h>
 #include "env.h"
@@ -61,7 +61,7 @@ struct ConvU8 {
     U8Q qx{}, qw{}, qy{};
     U8Relu fr{};
     const int32_t* dbias = nullptr;
-    Step st;                   // node, macs, bytes: every form starts from it
+    Step st;                   // node, macs, bytes, what the launch touches: every form starts from it
     // device copies of the weights, each made when a candidate that reads it is first launched or chosen
     std::map<int, uint8_t*> wgemm;     // (BM, KC) -> raw bytes packed for that GEMM tile shape
     float* wfrag = nullptr;            // dequantised, in MFMA fragment order: one copy serves every patch configuration, conv_u8_pw and conv_u8_c3
@@ -76,23 +76,20 @@ static int conv_u8_open(ConvU8& c)
     c.K = c.x.c / c.p.group * c.p.kernel_h * c.p.kernel_w; c.cout = c.y.c;
     if ((size_t)c.cout * c.K != c.w.data.size()) { set_error("conv %s: weight size mismatch", c.n.name.c_str()); return -1; }
     if (upload_bias(c.g, c.b, c.cout, &c.dbias)) return -1;
+    // everything a form's launch touches besides constants: the input, the output (a concat slice when it is a view), the pooled output
+    std::vector<Access> wr{access_of(c.y)};
+    if (c.pool) wr.push_back(access_of(c.g->tensors[c.pool->out[0]]));
     c.st = make_step(c.n.name, "", (double)c.y.n * c.y.h * c.y.w * c.cout * c.K,
-                     (double)c.x.n * c.x.c * c.x.h * c.x.w + (double)c.y.n * c.cout * c.y.h * c.y.w + 1.0 * c.cout * c.K, nullptr);
+                     (double)c.x.n * c.x.c * c.x.h * c.x.w + (double)c.y.n * c.cout * c.y.h * c.y.w + 1.0 * c.cout * c.K, nullptr, {access_of(c.x)}, wr, false);
     return 0;
 }
 
-// the launch of a form: the skeleton, the kernel's name with the fused tail's suffixes and, where the form declares them, everything
-// the launch touches besides constants: the input, the output (a concat slice when it is a view), the pooled output
-static Step conv_u8_step(const ConvU8& c, const char* kernel, bool accesses, std::function<hipError_t(hipStream_t)> fn)
+// the launch of a form: the skeleton and the kernel's name with the fused tail's suffixes.  deps: as make_step
+static Step conv_u8_step(const ConvU8& c, const char* kernel, bool deps, std::function<hipError_t(hipStream_t)> fn)
 {
     Step st = c.st;
     st.kernel = std::string(kernel) + (c.relu ? "+relu" : "") + (c.pool ? "+maxpool" : "");
-    if (accesses) {
-        st.rd.push_back(access_of(c.x));
-        st.wr.push_back(access_of(c.y));
-        if (c.pool) st.wr.push_back(access_of(c.g->tensors[c.pool->out[0]]));
-        st.deps = true;
-    }
+    st.deps = deps;
     st.fn = std::move(fn);
     return st;
 }
@@ -155,7 +152,8 @@ static int conv_u8_dma(ConvU8& c, Step* dq, Step* out)
         const size_t cnt = x.elems();
         const float zp = (float)c.qx.zp, sc = c.qx.scale;
         *dq = make_step(x.name, "dequant_u8_f32", 0, 5.0 * cnt,
-                        [src, xf, cnt, zp, sc](hipStream_t s) { return launch_dequant_u8_f32(src, xf, cnt, zp, sc, s); });
+                        [src, xf, cnt, zp, sc](hipStream_t s) { return launch_dequant_u8_f32(src, xf, cnt, zp, sc, s); },
+                        {access_of(x)}, {access_of_bytes(xf, cnt * sizeof(float))}, false);
     } else
         xf = it->second;
     if (!g->zero_page) { if (dev_alloc(g, &g->zero_page, 256, true)) return -1; }
@@ -165,6 +163,7 @@ static int conv_u8_dma(ConvU8& c, Step* dq, Step* out)
     a.bias_scale = c.qx.scale * c.qw.scale;           // conv_kernel_x86.c:1723
     a.act = p.activation; a.out_scale = c.qy.scale; a.out_zp = c.qy.zp;
     *out = conv_u8_step(c, conv_f32_mfma_kernel_name(a), false, [a](hipStream_t s) { return launch_conv_f32_mfma(a, s); });
+    out->rd = {access_of_bytes(xf, x.elems() * sizeof(float))};      // the launch reads the fp32 copy, not x
     out->bytes = 4.0 * x.elems() + (double)y.elems() + 4.0 * cout * K;
     return 0;
 }
@@ -613,7 +612,7 @@ static int plan_fc_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
     a.batch = batch; a.hidden = hidden; a.nout = nout; a.nout_pad = nout_pad;
     a.in_scale = qx.scale; a.in_zp = (float)qx.zp; a.out_scale = qy.scale; a.out_zp = qy.zp;
     out->push_back(make_step(n.name, "fc_u8", (double)batch * hidden * nout, 4.0 * hidden * nout + batch * (hidden + nout),
-                             [a](hipStream_t s) { return launch_fc_u8(a, s); }));
+                             [a](hipStream_t s) { return launch_fc_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
     return 0;
 }
 
@@ -627,7 +626,8 @@ static int plan_softmax_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* 
     a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
     a.outer = sp.outer; a.inner = sp.inner; a.on = sp.on;
     if (q_of(x, &a.in, "tensor") || q_of(y, &a.out, "tensor")) return -1;
-    out->push_back(make_step(n.name, "softmax_u8", 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_softmax_u8(a, s); }));
+    out->push_back(make_step(n.name, "softmax_u8", 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_softmax_u8(a, s); }, {access_of(x)},
+                             {access_of(y)}, false));
     return 0;
 }
 
@@ -640,7 +640,8 @@ static int plan_pool_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* out
     a.KH = pg.kh; a.KW = pg.kw; a.SH = pg.sh; a.SW = pg.sw; a.PH = pg.ph0; a.PW = pg.pw0;
     a.method = n.p.pool.pool_method; a.caffe_flavor = n.p.pool.caffe_flavor;
     if (q_of(x, &a.in, "tensor") || q_of(y, &a.out, "tensor")) return -1;
-    out->push_back(make_step(n.name, "pool_u8", 0, (double)x.elems() + (double)y.elems(), [a](hipStream_t s) { return launch_pool_u8(a, s); }));
+    out->push_back(make_step(n.name, "pool_u8", 0, (double)x.elems() + (double)y.elems(), [a](hipStream_t s) { return launch_pool_u8(a, s); }, {access_of(x)},
+                             {access_of(y)}, false));
     return 0;
 }
 
@@ -655,7 +656,7 @@ static int plan_map_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* out)
     if (q_of(x, &a.in, "tensor") || q_of(y, &a.out, "tensor")) return -1;
     const bool up = n.op == TAMD_OP_UPSAMPLE;
     out->push_back(make_step(n.name, up ? "upsample_u8" : "relu_u8", 0, (double)x.elems() + (double)y.elems(),
-                             [a, up](hipStream_t s) { return up ? launch_upsample_u8(a, s) : launch_relu_u8(a, s); }));
+                             [a, up](hipStream_t s) { return up ? launch_upsample_u8(a, s) : launch_relu_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
     return 0;
 }
 
@@ -668,7 +669,8 @@ static int plan_permute_u8(HNode& n, HTensor& x, HTensor& y, std::vector<Step>* 
     a.perm_c = x.dims[1]; a.perm_p = x.dims[2] * x.dims[3];
     a.out_img = a.in_img; a.out_off = 0; a.identity = 1;
     a.in.scale = a.out.scale = 1.f;
-    out->push_back(make_step(n.name, "permute_u8", 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_u8(a, s); }));
+    out->push_back(make_step(n.name, "permute_u8", 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_u8(a, s); }, {access_of(x)}, {access_of(y)},
+                             false));
     return 0;
 }
 
@@ -721,13 +723,10 @@ static int plan_concat_u8(tamd_graph* g, HNode& n, const std::vector<int>& perm_
             a.x = (const uint8_t*)s.dptr; a.perm_c = s.dims[1]; a.perm_p = s.dims[2] * s.dims[3];
             kname = "permute_concat_u8";
         }
-        Step st = make_step(n.name, kname, 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_u8(a, s); });
+        // reads its source, writes ITS slot of every outer slice
+        Step st = make_step(n.name, kname, 0, 2.0 * x.elems(), [a](hipStream_t s) { return launch_flatcat_u8(a, s); },
+                            {access_of(perm_src[i] >= 0 ? g->tensors[perm_src[i]] : x)}, {access_of_slot(y, out_img, off, in_img, 1)}, !y.is_view);
         st.once = all_const;                                     // e.g. mbox_priorbox: PriorBox outputs only
-        {                                                        // reads its source, writes ITS slot of every outer slice
-            Access r = access_of(perm_src[i] >= 0 ? g->tensors[perm_src[i]] : x), wa;
-            wa.base = (const char*)y.dptr; wa.size = y.elems(); wa.period = (size_t)out_img; wa.off = (size_t)off; wa.len = (size_t)in_img;
-            st.rd.push_back(r); st.wr.push_back(wa); st.deps = !y.is_view;
-        }
         each.push_back(st);
         if (multi.count < 8) { multi.src[multi.count] = a; multi.rescale[multi.count] = a.in.scale / a.out.scale; }
         multi.count++;
@@ -765,7 +764,8 @@ static int plan_eltwise_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
     a.count = xa.elems(); a.type = n.p.elt.type;
     if (!eltwise_type_on_device(a.type)) { set_error("eltwise %s: type %d unsupported", n.name.c_str(), a.type); return -1; }
     if (q_of(xa, &a.qa, "tensor") || q_of(xb, &a.qb, "tensor") || q_of(y, &a.out, "tensor")) return -1;
-    out->push_back(make_step(n.name, "eltwise_u8", 0, 3.0 * xa.elems(), [a](hipStream_t s) { return launch_eltwise_u8(a, s); }));
+    out->push_back(make_step(n.name, "eltwise_u8", 0, 3.0 * xa.elems(), [a](hipStream_t s) { return launch_eltwise_u8(a, s); }, {access_of(xa), access_of(xb)},
+                             {access_of(y)}, false));
     return 0;
 }
 
@@ -877,7 +877,7 @@ int plan_u8(tamd_graph* g)
         if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) continue;
         HTensor& x = g->tensors[n.in[0]];
         HTensor& y = g->tensors[n.out[0]];
-        std::vector<Step> out;                             // the node's launches: the only thing that goes onto g->steps
+        std::vector<Step> out;                             // the node's launches: the only thing that goes onto g->steps (append_steps)
         int rc = 0;
         switch (n.op) {
         case TAMD_OP_SOFTMAX: rc = plan_softmax_u8(n, x, y, &out); break;
@@ -885,27 +885,12 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_FC: rc = plan_fc_u8(g, n, &out); break;
         case TAMD_OP_POOL: rc = plan_pool_u8(n, x, y, &out); break;
         case TAMD_OP_RELU: case TAMD_OP_UPSAMPLE: rc = plan_map_u8(n, x, y, &out); break;
-        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: {     // byte maps by table: the planner both graphs share
-            Step st;
-            if (!(rc = plan_lut(g, n, &st))) out.push_back(st);
-            break;
-        }
-        case TAMD_OP_INTERP: {                  // nearest: index vectors + byte map at prerun, one launch (graph_plan.hip: plan_interp)
-            Step st;
-            if (!(rc = plan_interp(g, n, &st))) out.push_back(st);
-            break;
-        }
-        case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // plane maps at prerun, one chan_map_u8 launch per output (graph_plan.hip)
-        case TAMD_OP_SHUFFLECHANNEL: {
-            Step st;
-            if (!(rc = plan_shuffle_u8(g, n, &st))) out.push_back(st);
-            break;
-        }
-        case TAMD_OP_PRELU: {                   // one byte table per channel at prerun, one launch (graph_plan.hip: plan_prelu)
-            Step st;
-            if (!(rc = plan_prelu(g, n, &st))) out.push_back(st);
-            break;
-        }
+        // the byte-map planners both quantised graphs share (graph_plan_maps.hip): tables, index vectors and plane maps at prerun
+        case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: rc = plan_lut(g, n, &out); break;
+        case TAMD_OP_INTERP: rc = plan_interp(g, n, &out); break;
+        case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // one chan_map_u8 launch per output
+        case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
+        case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;
@@ -916,8 +901,7 @@ int plan_u8(tamd_graph* g)
             set_error("op %d (%s) is not supported on the device for uint8", n.op, n.name.c_str());
             rc = -1;
         }
-        if (rc) return -1;
-        g->steps.insert(g->steps.end(), out.begin(), out.end());
+        if (rc || append_steps(g, out)) return -1;
     }
     return plan_nchw_outputs(g, 1);
 }

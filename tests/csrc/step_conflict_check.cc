@@ -1,6 +1,6 @@
 // Host check of the dependency test behind the barrier-free launches of the direct path (tengine_amd/csrc/graph.h: Access,
-// access_of, access_overlap, step_conflict): which steps may run beside each other -- and of what the int8 planner refuses of one step
-// (access_of_channels, step_writes_what_it_reads, step_states_nothing).  No device is touched.
+// access_of, access_overlap, step_conflict): which steps may run beside each other -- and of what the planners refuse of one step
+// (access_of_channels, access_of_bytes, access_of_slot, step_writes_what_it_reads, step_states_nothing).  No device is touched.
 // build: hipcc -std=c++17 -I tengine_amd/csrc -I include step_conflict_check.cc -o step_conflict_check
 #include <cstdio>
 
@@ -70,21 +70,56 @@ int main()
     auto none = [](hipStream_t) { return hipSuccess; };
     HTensor d0 = whole, d1 = whole, d2 = whole;                       // three dense NHWC buffers
     d1.dptr = buf + 8192; d2.dptr = buf + 16384;
-    const Step spp = make_step("pool", "pool_i8", 0, 0, none, {access_of(n0)}, {access_of(n1)});
+    const Step spp = make_step("pool", "pool_i8", 0, 0, none, {access_of(n0)}, {access_of(n1)}, false);
     EXPECT(!step_states_nothing(spp) && !step_writes_what_it_reads(spp) && !spp.deps);
     EXPECT(make_step("conv", "k", 0, 0, none, {access_of(d0)}, {access_of(d1)}, true).deps);
-    const Step in_place = make_step("add", "eltwise_i8", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d0)});
+    const Step in_place = make_step("add", "eltwise_i8", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d0)}, false);
     EXPECT(step_writes_what_it_reads(in_place));
-    const Step residual = make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d1)});       // only the SECOND read
+    const Step residual = make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d1)}, false);       // only the SECOND read
     EXPECT(step_writes_what_it_reads(residual));
-    EXPECT(!step_writes_what_it_reads(make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d2)})));
-    EXPECT(step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_mid})));
-    EXPECT(!step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_hi})));
+    EXPECT(!step_writes_what_it_reads(make_step("conv+add", "k+eltwise", 0, 0, none, {access_of(d0), access_of(d1)}, {access_of(d2)}, false)));
+    EXPECT(step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_mid}, false)));
+    EXPECT(!step_writes_what_it_reads(make_step("copy", "concat_copy_i8", 0, 0, none, {access_of(n0)}, {slot_hi}, false)));
     // a step that states no read or no write "states nothing"
-    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none)));
-    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)})));
-    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {}, {access_of(d0)})));
-    EXPECT(!step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)}, {access_of(d1)})));
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {}, {}, false)));
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)}, {}, false)));
+    EXPECT(step_states_nothing(make_step("n", "k", 0, 0, none, {}, {access_of(d0)}, false)));
+    EXPECT(!step_states_nothing(make_step("n", "k", 0, 0, none, {access_of(d0)}, {access_of(d1)}, false)));
+    // raw bytes (access_of_bytes): the fp32 copy of a uint8 tensor, the Winograd workspaces.  `copy` holds 2x8x4x4 floats
+    HTensor ux = dense_u8(buf + 32768, 2, 8, 4, 4), uy = dense_u8(buf + 36864, 2, 8, 4, 4);
+    const Access copy = access_of_bytes(buf + 40960, 256 * sizeof(float));
+    EXPECT(copy.base == buf + 40960 && copy.size == 1024 && copy.len == 1024 && copy.period == 0 && copy.off == 0);
+    HTensor inside = dense_u8(buf + 40960 + 512, 2, 8, 4, 4), beside = dense_u8(buf + 40960 + 1024, 2, 8, 4, 4);
+    EXPECT(access_overlap(copy, access_of(inside)) && access_overlap(access_of(inside), copy));
+    EXPECT(!access_overlap(copy, access_of(beside)) && !access_overlap(access_of(beside), copy));
+    EXPECT(!access_overlap(copy, access_of(ux)) && !access_overlap(copy, access_of(uy)));
+    const Step dequant = make_step("x", "dequant_u8_f32", 0, 0, none, {access_of(ux)}, {copy}, false);
+    const Step conv_dma = make_step("conv", "conv_f32_mfma", 0, 0, none, {copy}, {access_of(uy)}, false);
+    EXPECT(!step_states_nothing(dequant) && !step_writes_what_it_reads(dequant));
+    EXPECT(!step_states_nothing(conv_dma) && !step_writes_what_it_reads(conv_dma));
+    EXPECT(step_conflict(dequant, conv_dma) && step_conflict(conv_dma, dequant));               // RAW on the copy
+    // a concat input's slot of a DENSE output (access_of_slot): a 2 x (3 + 5) x 4 x 4 channel concat.  At esz = 1 exactly the fields
+    // plan_concat_u8 used to build by hand: base y, size y.elems(), period out_img, off, len in_img
+    HTensor cat = dense_u8(buf + 65536, 2, 8, 4, 4);
+    const size_t out_img = 8 * 16;
+    const Access u_lo = access_of_slot(cat, out_img, 0, 3 * 16, 1), u_hi = access_of_slot(cat, out_img, 3 * 16, 5 * 16, 1);
+    EXPECT(u_lo.base == buf + 65536 && u_lo.size == 256 && u_lo.period == 128 && u_lo.off == 0 && u_lo.len == 48);
+    EXPECT(u_hi.base == buf + 65536 && u_hi.size == 256 && u_hi.period == 128 && u_hi.off == 48 && u_hi.len == 80);
+    EXPECT(!access_overlap(u_lo, u_hi));
+    // the same concat in fp32
+    HTensor catf = cat; catf.dtype = TAMD_DT_FP32;
+    const Access f_lo = access_of_slot(catf, out_img, 0, 3 * 16, 4), f_hi = access_of_slot(catf, out_img, 3 * 16, 5 * 16, 4);
+    EXPECT(f_lo.base == buf + 65536 && f_lo.size == 1024 && f_lo.period == 512 && f_lo.off == 0 && f_lo.len == 192);
+    EXPECT(f_hi.size == 1024 && f_hi.period == 512 && f_hi.off == 192 && f_hi.len == 320);
+    EXPECT(!access_overlap(f_lo, f_hi) && !access_overlap(f_hi, f_lo));                           // two slots of one concat: disjoint
+    // .. against access_of views of the same buffer: channels [0,3) and [3,8) written in place by their producers
+    HTensor fv0 = catf, fv1 = catf;
+    fv0.is_view = fv1.is_view = true; fv0.cs = fv1.cs = 8; fv0.c = 3; fv1.c = 5; fv0.c_off = 0; fv1.c_off = 3; fv0.dims = {2, 3, 4, 4}; fv1.dims = {2, 5, 4, 4};
+    EXPECT(access_overlap(f_lo, access_of(fv0)) && access_overlap(f_hi, access_of(fv1)));       // the same channels: overlap
+    EXPECT(!access_overlap(f_lo, access_of(fv1)) && !access_overlap(f_hi, access_of(fv0)));
+    EXPECT(access_overlap(u_lo, access_of(v0)) == false);                                         // (another buffer altogether)
+    EXPECT(access_overlap(f_lo, access_of(catf)) && access_overlap(access_of(catf), f_hi));      // a slot against the whole buffer
+    EXPECT(access_overlap(u_hi, access_of(cat)));
     printf("step_conflict_check: %d failures\n", bad);
     return bad != 0;
 }

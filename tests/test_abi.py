@@ -274,8 +274,8 @@ def test_hidden_argument_offsets_are_read_from_code_object_metadata(tmp_path):
 
 def test_dependency_test_of_the_barrier_free_launches(tmp_path):
     """which launch may run beside which (tengine_amd/csrc/graph.h: access_of / access_overlap / step_conflict -- NCHW tensors,
-    uint8 concat slices, int8 NHWC channel views, concat slots; RAW / WAR / WAW), and what the int8 planner refuses of ONE launch
-    (access_of_channels, step_writes_what_it_reads, step_states_nothing): checked on the host, no device involved
+    uint8 concat slices, int8 NHWC channel views, concat slots; RAW / WAR / WAW), and what the planners refuse of ONE launch
+    (access_of_channels, access_of_bytes, access_of_slot, step_writes_what_it_reads, step_states_nothing): checked on the host, no device involved
     (tests/csrc/step_conflict_check.cc)"""
     import shutil
     import subprocess
