@@ -180,8 +180,11 @@ typedef struct tamd_options {
                            * environment variable itself is honoured too */
     int direct_dispatch;  /* 1: tamd_graph_launch replays the launch list as AQL packets on the graph's own HSA queue instead
                            * of hipGraphLaunch (shorter launch boundaries, no hole between replays; csrc/direct.cc).  The
-                           * passes are ordered among themselves and observed by tamd_graph_sync / _download_outputs /
-                           * _run; work on tamd_graph_stream() is NOT ordered behind them.  TAMD_DIRECT_DISPATCH=0|1
+                           * passes queued between two calls that wait (tamd_graph_sync / _download_outputs / _upload_inputs /
+                           * _run / _read_tensor ...) all compute the same input and are observed TOGETHER by the next such call;
+                           * a graph with two slots (split_batch below, tamd_graph_slots) runs two of them at a time on two HSA
+                           * queues, so they are not ordered among themselves -- nothing a caller can see depends on that order.
+                           * Work on tamd_graph_stream() is NOT ordered behind them.  TAMD_DIRECT_DISPATCH=0|1
                            * overrides.  Falls back to the hipGraph silently when the list cannot be dispatched directly. */
     int keep_tensors;     /* 1: every intermediate tensor keeps a buffer of its own, so tamd_graph_read_tensor can return any of
                            * them after a run (the TG_DEBUG_DATA analogue).  0 (default): tensors whose lifetimes do not overlap
@@ -203,7 +206,17 @@ typedef struct tamd_options {
                            * as two contiguous halves.  0 (default): where it pays -- int8 graphs with direct_dispatch from batch 16
                            * on; 1: never (final: a caller that splits batches by itself, as the plugin does); 2: wherever it is possible.
                            * TAMD_SPLIT_BATCH=0|1|2 overrides 0 and 2 (0: never, 1: default rule, 2: wherever possible -- the values the
-                           * plugin's switch of the same name takes).  tamd_graph_halves() tells which form a graph took. */
+                           * plugin's switch of the same name takes).  tamd_graph_halves() tells which form a graph took.
+                           *   TWO SLOTS (csrc/graph_slots.hip): a graph that is not such a pair may instead keep two passes of its ONE
+                           * launch list in flight -- a second program of the list on a second HSA queue, with everything a pass writes
+                           * re-pointed at a private copy (weights, tables and the input staging buffers are shared), and
+                           * tamd_graph_launch alternating between the two.  This raises THROUGHPUT where a pass leaves the device idle
+                           * (int8 MobileNet-v1 batch 1: 27.7 us per pass against 49.2, profiles/two_slots_ab.txt); it does not shorten
+                           * a pass: tamd_graph_run, a lone launch + sync and tamd_graph_time_launches are what they were.  0 (default):
+                           * int8 graphs with direct_dispatch at batch 1; 1: never; 2: every int8 graph with direct_dispatch that is
+                           * not a pair.  A list that does not qualify (a launch that ran once at prerun, no second queue, a slot that
+                           * does not reproduce the eager pass byte for byte at prerun) stays one list, silently (TAMD_DEBUG=1 says
+                           * why).  tamd_graph_slots() tells. */
 } tamd_options;
 /* does a blob that carries `size` hold `field` whole?  Every reader of a caller's blob asks this field by field; a field the blob
  * does not reach keeps the reader's default */
@@ -287,6 +300,9 @@ TAMD_API int tamd_graph_set_batch(tamd_graph* g, int batch);
 TAMD_API int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt);
 /* 2: the graph was compiled as two half-batch device graphs (tamd_options.split_batch); 0: one launch list */
 TAMD_API int tamd_graph_halves(const tamd_graph* g);
+/* 2: tamd_graph_launch keeps two passes of the launch list in flight on two HSA queues (tamd_options.split_batch, "two slots");
+ * 0: one pass at a time.  Every other entry point behaves alike in both forms. */
+TAMD_API int tamd_graph_slots(const tamd_graph* g);
 TAMD_API int tamd_graph_input_num(const tamd_graph* g);
 TAMD_API int tamd_graph_output_num(const tamd_graph* g);
 /* dims/dtype of graph input / output `idx` (NCHW); returns dim_num */
@@ -324,17 +340,27 @@ TAMD_API int tamd_graph_direct_meta_packets(const tamd_graph* g);
  * dispatch directly.  tamd_graph_direct_packet_name(g, i): kernel symbol of packet i. */
 TAMD_API int tamd_graph_direct_timestamps(tamd_graph* g, int passes, double* dur_us, double* gap_us, int max_packets);
 TAMD_API const char* tamd_graph_direct_packet_name(const tamd_graph* g, int i);
+/* MEASUREMENT, a graph with two slots: ONE burst of `passes` rounds, each a pass on slot 0's queue and a pass on slot 1's, every
+ * packet stamped as above.  Raw stamps in microseconds on the common clock, counted from the earliest start:
+ * start_us / end_us[(round * 2 + slot) * packets + packet], packets = tamd_graph_direct_packets().  Returns the rounds stamped
+ * (max_stamps >= passes * 2 * packets), -1 when the graph has one slot.  tamd_graph_direct_timestamps and tamd_graph_time_launches keep
+ * running slot 0 ALONE: they describe a pass as the dependent chain it is. */
+TAMD_API int tamd_graph_slot_timestamps(tamd_graph* g, int passes, double* start_us, double* end_us, int max_stamps);
 TAMD_API int tamd_graph_download_outputs(tamd_graph* g);
 /* device pointer + byte size of graph output `idx` in the reference's NCHW order (for RCCL gather).  Valid after any pass: a
  * direct-dispatch tamd_graph_run / tamd_graph_wait leaves its outputs in the pinned host buffers only (zero-copy lists) and this
  * call refreshes the device copy from there first; it fails while asynchronous runs are in flight.  For a graph compiled as two
  * half-batch device graphs (tamd_options.split_batch) the pointer is a buffer of the pair into which THIS CALL gathers the two halves'
- * outputs (it waits for their passes first): call it after the pass whose outputs are wanted, not once before a loop of passes. */
+ * outputs (it waits for their passes first): call it after the pass whose outputs are wanted, not once before a loop of passes.
+ * With two slots (tamd_graph_slots) the pointer stays what it is for one list: a PERSISTENT view of slot 0's buffer, taken once,
+ * valid after every tamd_graph_sync, no copy -- slot 0 runs first after every call that waits, and every pass since computed the same
+ * bytes. */
 TAMD_API int tamd_graph_output_device(tamd_graph* g, int idx, void** dptr, size_t* bytes);
 TAMD_API void* tamd_graph_stream(tamd_graph* g);          /* hipStream_t                           */
 /* wall time tamd_graph_prerun took (planning incl. the plan-time autotune, capture, direct-dispatch programs), milliseconds */
 TAMD_API double tamd_graph_prerun_ms(const tamd_graph* g);
-/* time `iters` back-to-back launches with HIP events on the graph's stream -> total ms */
+/* time `iters` back-to-back launches with HIP events on the graph's stream -> total ms (direct dispatch: the host's clock around
+ * submit .. complete, on ONE queue -- slot 0 alone where the graph has two slots: the duration of a pass, not the throughput step) */
 TAMD_API int tamd_graph_time_launches(tamd_graph* g, int iters, float* total_ms);
 
 /* ---- introspection / profiling: the TG_DEBUG_TIME / TG_DEBUG_DATA analogues of the CPU device

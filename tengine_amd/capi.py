@@ -28,11 +28,11 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 EXPORTS = [
     "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
-    "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves",
+    "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
     "tamd_graph_set_input", "tamd_graph_set_output", "tamd_graph_run", "tamd_graph_run_async", "tamd_graph_wait", "tamd_graph_inflight", "tamd_graph_upload_inputs",
     "tamd_graph_launch", "tamd_graph_sync", "tamd_graph_direct_packets", "tamd_graph_direct_meta_packets", "tamd_graph_download_outputs", "tamd_graph_output_device",
-    "tamd_graph_direct_timestamps", "tamd_graph_direct_packet_name", "tamd_graph_stream", "tamd_graph_time_launches", "tamd_graph_prerun_ms", "tamd_graph_kernel_num", "tamd_graph_profile",
+    "tamd_graph_direct_timestamps", "tamd_graph_slot_timestamps", "tamd_graph_direct_packet_name", "tamd_graph_stream", "tamd_graph_time_launches", "tamd_graph_prerun_ms", "tamd_graph_kernel_num", "tamd_graph_profile",
     "tamd_graph_read_tensor", "tamd_graph_tensor_num", "tamd_graph_tensor_desc", "tamd_graph_destroy",
 ]
 
@@ -64,6 +64,10 @@ def lib():
         L.tamd_graph_direct_packet_name.restype = C.c_char_p
         L.tamd_graph_direct_packet_name.argtypes = [vp, ci]
         L.tamd_graph_direct_timestamps.argtypes = [vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), ci]
+        # (guarded: tools/exp/ab_lib.py loads an OLDER build of the library under this binding, which has no slots)
+        if hasattr(L, "tamd_graph_slots"):
+            L.tamd_graph_slot_timestamps.argtypes = [vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), ci]
+            L.tamd_graph_slots.argtypes = [vp]
         L.tamd_graph_prerun_ms.restype = C.c_double
         L.tamd_graph_prerun_ms.argtypes = [vp]
         for name, args in {
@@ -202,6 +206,18 @@ class Graph:
     def halves(self):
         """2: compiled as two half-batch device graphs behind this one handle (tamd_options.split_batch); 0: one launch list"""
         return lib().tamd_graph_halves(self._h)
+
+    def slots(self):
+        """2: launch() keeps two passes of the launch list in flight on two HSA queues (tamd_options.split_batch, two slots); 0: one at a time"""
+        return lib().tamd_graph_slots(self._h) if hasattr(lib(), "tamd_graph_slots") else 0
+
+    def slot_timestamps(self, passes=50):
+        """one burst of `passes` rounds of (a pass on slot 0's queue, a pass on slot 1's), every packet stamped: (start_us, end_us), two
+        float arrays of shape [rounds, 2, packets] on the common clock, counted from the earliest start"""
+        n = lib().tamd_graph_direct_packets(self._h)
+        t0, t1 = (C.c_double * (passes * 2 * n))(), (C.c_double * (passes * 2 * n))()
+        r = _check(lib().tamd_graph_slot_timestamps(self._h, passes, t0, t1, passes * 2 * n), "slot_timestamps")
+        return (np.array(t0[:r * 2 * n]).reshape(r, 2, n), np.array(t1[:r * 2 * n]).reshape(r, 2, n))
 
     def input_desc(self, idx=0):
         dims = (C.c_int * 8)()

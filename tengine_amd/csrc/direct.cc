@@ -377,6 +377,88 @@ const char* direct_packet_name(const DirectProgram* p, int i) { return (p && i >
 //   gap_us[i]  mean time from the end of packet i to the start of packet i + 1 (the launch boundary as the device saw it);
 //              gap_us[n - 1] = from the end of the last packet to the start of the first packet of the NEXT pass (0 for the last pass)
 // A measurement entry point (round 6: the timed path had never been seen by anything but the host's clock); not used by a run.
+
+// one pass of `p` with completion signal sig[i] on packet i (the stamps are read through them): direct_submit's packets otherwise
+static int submit_stamped(DirectProgram* p, const hsa_signal_t* sig)
+{
+    const int n = (int)p->pkts.size();
+    DirectQueue* dq = p->dq;
+    hsa_queue_t* q = dq->q;
+    hsa_kernel_dispatch_packet_t* base = (hsa_kernel_dispatch_packet_t*)q->base_address;
+    const uint64_t mask = q->size - 1;
+    const uint64_t idx0 = hsa_queue_add_write_index_relaxed(q, (uint64_t)n);
+    while (idx0 + n - hsa_queue_load_read_index_scacquire(q) > q->size)
+        if (dq->fault.load()) return -1;
+    for (int i = 0; i < n; i++) {
+        hsa_kernel_dispatch_packet_t* d = base + ((idx0 + i) & mask);
+        const hsa_kernel_dispatch_packet_t& s = p->pkts[i];
+        d->setup = s.setup;
+        d->workgroup_size_x = s.workgroup_size_x; d->workgroup_size_y = s.workgroup_size_y; d->workgroup_size_z = s.workgroup_size_z;
+        d->reserved0 = 0;
+        d->grid_size_x = s.grid_size_x; d->grid_size_y = s.grid_size_y; d->grid_size_z = s.grid_size_z;
+        d->private_segment_size = s.private_segment_size; d->group_segment_size = s.group_segment_size;
+        d->kernel_object = s.kernel_object; d->kernarg_address = s.kernarg_address; d->reserved2 = 0;
+        d->completion_signal = sig[i];
+        const uint16_t h = i == 0 ? (dq->open ? p->h_wrap : p->h_open) : p->hdr[i];
+        __atomic_store_n(&d->header, h, __ATOMIC_RELEASE);
+    }
+    const uint64_t to_end = q->size - (idx0 & mask);
+    if (to_end < (uint64_t)n) hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t)(idx0 + to_end - 1));
+    hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t)(idx0 + n - 1));
+    dq->open = true;
+    return 0;
+}
+
+// The second mode: ONE burst of `passes` rounds, each round a pass of `a` and a pass of `b` (the same launch list on two queues, as
+// tamd_graph_launch alternates between a graph's two slots), every packet stamped.  Raw stamps, microseconds on the common clock,
+// counted from the earliest start: start_us / end_us[(round * 2 + queue) * n + packet].  Rounds in front whose packets carry no stamps
+// (the warm-up rounds, and on a very short list sometimes more: see direct_timestamps) are not returned: the return value is the
+// number of rounds that are (<= passes), -1 on error.
+int direct_timestamps_two(DirectProgram* a, DirectProgram* b, int passes, double* start_us, double* end_us)
+{
+    const int n = (int)a->pkts.size();
+    if (n == 0 || (int)b->pkts.size() != n || passes < 1 || a->dq == b->dq) { direct_err("two programs of the same list on two queues are needed", 0); return -1; }
+    DirectProgram* prog[2] = {a, b};
+    if (direct_wait_all(a) || direct_wait_all(b)) return -1;
+    uint64_t freq = 0;
+    if (hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP_FREQUENCY, &freq) != HSA_STATUS_SUCCESS || !freq) { direct_err("no timestamp frequency", 0); return -1; }
+    for (DirectProgram* p : prog)
+        if (hsa_amd_profiling_set_profiler_enabled(p->dq->q, 1) != HSA_STATUS_SUCCESS) { direct_err("hsa_amd_profiling_set_profiler_enabled", 0); return -1; }
+    const int extra = 3, all = passes + extra;         // rounds in front that the queues may leave unstamped
+    std::vector<hsa_signal_t> sig((size_t)all * 2 * n);
+    for (auto& s : sig)
+        if (hsa_signal_create(1, 0, nullptr, &s) != HSA_STATUS_SUCCESS) { direct_err("hsa_signal_create", 0); return -1; }
+    int rc = 0;
+    for (int ps = 0; ps < all && !rc; ps++) {
+        for (int k = 0; k < 2 && !rc; k++) rc = submit_stamped(prog[k], &sig[((size_t)ps * 2 + k) * n]);
+        if (ps + 1 == extra && !rc) rc = direct_wait(a) || direct_wait(b) ? -1 : 0;        // the stamped rounds are one burst behind the warm-up
+    }
+    if (!rc) rc = direct_wait(a) || direct_wait(b) ? -1 : 0;
+    std::vector<uint64_t> t0(sig.size(), 0), t1(sig.size(), 0);
+    for (size_t k = 0; k < sig.size() && !rc; k++) {
+        hsa_amd_profiling_dispatch_time_t t{};
+        if (hsa_amd_profiling_get_dispatch_time(a->agent, sig[k], &t) != HSA_STATUS_SUCCESS) { direct_err("hsa_amd_profiling_get_dispatch_time", (int)k); rc = -1; break; }
+        t0[k] = t.start; t1[k] = t.end;
+    }
+    for (DirectProgram* p : prog) (void)hsa_amd_profiling_set_profiler_enabled(p->dq->q, 0);
+    for (auto& s : sig) (void)hsa_signal_destroy(s);
+    if (rc) return -1;
+    // the queues pick the profiling switch up some time after it is set (see direct_timestamps): rounds in front of the first one
+    // whose packets, and every later round's, all carry stamps are dropped -- the warm-up rounds at least
+    int first_ok = extra;
+    for (size_t k = 0; k < sig.size(); k++)
+        if (t1[k] <= t0[k]) first_ok = std::max(first_ok, (int)(k / ((size_t)2 * n)) + 1);
+    if (first_ok >= all) { direct_err("no round of the burst carries dispatch stamps throughout", all); return -1; }
+    const size_t first = (size_t)first_ok * 2 * n;
+    uint64_t origin = ~(uint64_t)0;
+    for (size_t k = first; k < sig.size(); k++) origin = std::min(origin, t0[k]);
+    for (size_t k = first; k < sig.size(); k++) {
+        start_us[k - first] = 1e6 * (double)(t0[k] - origin) / (double)freq;
+        end_us[k - first] = 1e6 * (double)(t1[k] - origin) / (double)freq;
+    }
+    return all - first_ok;
+}
+
 int direct_timestamps(DirectProgram* p, int passes, double* dur_us, double* gap_us)
 {
     const int n = (int)p->pkts.size();
@@ -397,31 +479,9 @@ int direct_timestamps(DirectProgram* p, int passes, double* dur_us, double* gap_
     for (auto& s : sig)
         if (hsa_signal_create(1, 0, nullptr, &s) != HSA_STATUS_SUCCESS) { direct_err("hsa_signal_create", 0); return -1; }
     int rc = 0;
-    hsa_queue_t* q = dq->q;
-    hsa_kernel_dispatch_packet_t* base = (hsa_kernel_dispatch_packet_t*)q->base_address;
-    const uint64_t mask = q->size - 1;
     for (int ps = 0; ps < passes && !rc; ps++) {
         // all passes go out back to back (one burst), as the timed loop of bench.py submits them
-        const uint64_t idx0 = hsa_queue_add_write_index_relaxed(q, (uint64_t)n);
-        while (idx0 + n - hsa_queue_load_read_index_scacquire(q) > q->size)
-            if (dq->fault.load()) { rc = -1; break; }
-        for (int i = 0; i < n && !rc; i++) {
-            hsa_kernel_dispatch_packet_t* d = base + ((idx0 + i) & mask);
-            const hsa_kernel_dispatch_packet_t& s = p->pkts[i];
-            d->setup = s.setup;
-            d->workgroup_size_x = s.workgroup_size_x; d->workgroup_size_y = s.workgroup_size_y; d->workgroup_size_z = s.workgroup_size_z;
-            d->reserved0 = 0;
-            d->grid_size_x = s.grid_size_x; d->grid_size_y = s.grid_size_y; d->grid_size_z = s.grid_size_z;
-            d->private_segment_size = s.private_segment_size; d->group_segment_size = s.group_segment_size;
-            d->kernel_object = s.kernel_object; d->kernarg_address = s.kernarg_address; d->reserved2 = 0;
-            d->completion_signal = sig[(size_t)ps * n + i];
-            const uint16_t h = i == 0 ? (dq->open ? p->h_wrap : p->h_open) : p->hdr[i];
-            __atomic_store_n(&d->header, h, __ATOMIC_RELEASE);
-        }
-        const uint64_t to_end = q->size - (idx0 & mask);
-        if (to_end < (uint64_t)n) hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t)(idx0 + to_end - 1));
-        hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t)(idx0 + n - 1));
-        dq->open = true;
+        rc = submit_stamped(p, &sig[(size_t)ps * n]);
         // the warm-up pass completes before the stamped ones are written: with a handful of short passes the whole burst used to be in the
         // ring before the packet processor had looked at the first doorbell, and the first stamped pass read start == end as well
         // (tests/test_gpu_split_batch.py: 5 passes of a batch-2 MobileNet; 30+ passes never showed it)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/tengine_amd.h"
+#include "graph_slots.h"
 #include "kernels.h"
 #include "node_rules.h"
 
@@ -231,6 +232,14 @@ struct tamd_graph {
     tamd::DirectProgram* direct = nullptr;     // tamd_options.direct_dispatch: the launch list as AQL packets (direct.cc)
     tamd::DirectProgram* direct_io = nullptr;  // .. the host-to-host list of I/O slot 0 (tamd_graph_run), same HSA queue
     tamd::DirectProgram* direct_io2 = nullptr; // .. of I/O slot 1 (the second asynchronous run in flight)
+    // two slots (graph_slots.hip): a second program of the SAME launch list on an HSA queue of its own, its written buffers re-pointed
+    // at a private copy (slot_block); tamd_graph_launch alternates between the two, so two passes are in flight.  nullptr: one list
+    tamd::DirectProgram* direct1 = nullptr;
+    void* slot_block = nullptr;                // slot 1's copy of everything a pass writes (one allocation)
+    std::vector<tamd::SlotSpan> slot_spans;    // where each written span of slot 0 lives in it
+    int slot_turn = 0;                         // whose turn the next tamd_graph_launch is; direct_drain sets it back to 0
+    bool slot_hold = false;                    // tamd_graph_time_launches: slot 0 alone (the pass as the dependent chain it is)
+    bool had_once = false;                     // the plan held launches that ran once at prerun (their results exist in slot 0 only)
     int autotune_cold = -1;                    // plan-time timing mode, decided once (autotune_cold())
     double prerun_ms = 0;                      // wall time of tamd_graph_prerun (planning, autotune, capture)
     bool direct_busy = false;                  // passes submitted since the last wait

@@ -333,7 +333,11 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
         if (TAMD_OPTIONS_HAS(have, direct_dispatch)) o.direct_dispatch = opt->direct_dispatch;
         if (TAMD_OPTIONS_HAS(have, keep_tensors)) o.keep_tensors = opt->keep_tensors;
         if (TAMD_OPTIONS_HAS(have, u8_integer)) o.u8_integer = opt->u8_integer;
+        if (TAMD_OPTIONS_HAS(have, split_batch)) o.split_batch = (opt->split_batch == 1 || opt->split_batch == 2) ? opt->split_batch : 0;
     }
+    // (read as graph_pair.hip reads it: 1 from the caller is final; TAMD_SPLIT_BATCH = 0 never, 1 default rule, 2 wherever possible)
+    if (o.split_batch != 1)
+        if (const char* sb = getenv("TAMD_SPLIT_BATCH")) { const int v = atoi(sb); o.split_batch = v == 0 ? 1 : v == 2 ? 2 : 0; }
     if (const char* ui = getenv("TAMD_U8_INT")) o.u8_integer = atoi(ui) != 0;
     if (const char* dd = getenv("TAMD_DIRECT_DISPATCH")) o.direct_dispatch = atoi(dd) != 0;
     // a tool that intercepts HSA queues (rocprofv3) crashes in its doorbell handler on packets it did not see HIP write
@@ -361,7 +365,7 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
     if (any_u8 ? plan_u8(g) : any_f32 ? plan_f32(g) : plan_i8(g)) return -1;
     // launches whose inputs are all prerun constants (the Concat of the PriorBox outputs) run now and never again
     for (auto& st : g->steps)
-        if (st.once) HIPCHK(st.fn(g->stream));
+        if (st.once) { HIPCHK(st.fn(g->stream)); g->had_once = true; }
     g->steps.erase(std::remove_if(g->steps.begin(), g->steps.end(), [](const Step& st) { return st.once; }), g->steps.end());
     for (auto* v : {&g->inputs, &g->outputs})
         for (auto& io : *v) HIPCHK(hipHostMalloc(&io.pinned2, std::max<size_t>(io.bytes, 16), hipHostMallocDefault));
@@ -408,6 +412,7 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
                 direct_destroy(g->direct);
                 g->direct = nullptr;
             }
+            const std::vector<LaunchRec> pass_recs = recs;
             for (int slot = 0; slot < 2 && g->direct && g->hexec_io[slot][0]; slot++) {
                 // the host-to-host list of I/O slot 0 | 1 (upload launch, compute, download launch) on the same queue:
                 // tamd_graph_run and the asynchronous pair
@@ -440,6 +445,9 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
             if (!g->direct_io || !g->direct_io2) {          // both or none: the asynchronous pair alternates between them
                 if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
             }
+            // two passes in flight: the same list once more on a second queue, its written buffers re-pointed (graph_slots.hip).  Never
+            // an error: whatever is in the way leaves the graph one launch list
+            if (g->direct && o.split_batch != 1) slots_try_build(g, pass_recs, o.split_batch);
             if (getenv("TAMD_DEBUG") && g->direct_io)
                 fprintf(stderr, "[tamd] host-to-host list: %d packets%s\n", direct_packets(g->direct_io), g->io_zero_copy ? ", outputs stored straight into the pinned host buffers" : "");
         }
@@ -451,6 +459,7 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
 }
 
 int tamd_graph_halves(const tamd_graph* g) { return g && g->half[0] ? 2 : 0; }
+int tamd_graph_slots(const tamd_graph* g) { return g && !g->half[0] && g->direct && g->direct1 ? 2 : 0; }
 int tamd_graph_input_num(const tamd_graph* g) { return (int)g->inputs.size(); }
 int tamd_graph_output_num(const tamd_graph* g) { return (int)g->outputs.size(); }
 
@@ -622,6 +631,7 @@ void tamd_graph_destroy(tamd_graph* g)
     std::lock_guard<std::mutex> lk(g_capture_mutex);      // hipFree is device-synchronous: not while another thread captures
     if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
     if (g->direct_io) { direct_destroy(g->direct_io); g->direct_io = nullptr; }
+    slots_destroy(g);
     if (g->direct) { direct_destroy(g->direct); g->direct = nullptr; }
     for (int i = 0; i < g->nexec; i++) if (g->hexecs[i]) hipGraphExecDestroy(g->hexecs[i]);
     for (int slot = 0; slot < 2; slot++) {

@@ -92,7 +92,7 @@ int launch_io(tamd_graph* g, int slot)
 // One direct pass against the eager pass of the same launch list, every graph output compared byte for byte.  Two pseudo-random
 // inputs: eager(A) -> want; eager(B) leaves B's results in every buffer; direct(A) must bring want back -- a pass that writes
 // nothing, or the wrong thing, shows up, and outputs that are prerun constants (PriorBox) are the same in all three.  0: identical.
-static void selfcheck_noise(const tamd_graph* g, const IOBind& io, unsigned* lcg_state, std::vector<unsigned char>* noise)
+void selfcheck_noise(const tamd_graph* g, const IOBind& io, unsigned* lcg_state, std::vector<unsigned char>* noise)
 {
     unsigned lcg = *lcg_state;
     noise->resize(io.bytes);
@@ -250,9 +250,11 @@ int bind_device(tamd_graph* g)
 int direct_drain(tamd_graph* g)
 {
     if (g->direct && g->direct_busy) {
-        if (direct_wait(g->direct)) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
+        // both slots' queues (graph_slots.hip); a queue with nothing open returns at once
+        if (direct_wait(g->direct) || (g->direct1 && direct_wait(g->direct1))) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
         g->direct_busy = false;
     }
+    g->slot_turn = 0;          // slot 0 runs first after every drain: its buffers are the ones everybody reads
     return 0;
 }
 
@@ -265,6 +267,7 @@ void direct_abandon(tamd_graph* g, const char* why)
     // direct_destroy waits for what is still running unless the queue has faulted; a hung burst is bounded by TAMD_DIRECT_TIMEOUT_S
     if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
     if (g->direct_io) { direct_destroy(g->direct_io); g->direct_io = nullptr; }
+    slots_destroy(g);
     if (g->direct) { direct_destroy(g->direct); g->direct = nullptr; }
     g->direct_busy = false;
 }
@@ -325,7 +328,10 @@ int tamd_graph_launch(tamd_graph* g)
         // the pass reads what the stream wrote (uploaded inputs): drain it before the first packet of a burst
         if (!g->direct_busy) { HIPCHK(hipStreamSynchronize(g->stream)); g->stream_dirty = false; }
         g->direct_busy = true;
-        if (direct_submit(g->direct)) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
+        // two slots: the passes of a burst alternate between the two queues, slot 0 first (graph_slots.hip)
+        DirectProgram* p = g->direct;
+        if (g->direct1 && !g->slot_hold) { if (g->slot_turn) p = g->direct1; g->slot_turn ^= 1; }
+        if (direct_submit(p)) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
         return 0;
     }
     g->stream_dirty = true;
@@ -358,6 +364,19 @@ int tamd_graph_direct_timestamps(tamd_graph* g, int passes, double* dur_us, doub
     const int n = direct_timestamps(g->direct, passes, dur_us, gap_us);
     if (n < 0) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
     return n;
+}
+int tamd_graph_slot_timestamps(tamd_graph* g, int passes, double* start_us, double* end_us, int max_stamps)
+{
+    if (!g) { set_error("null graph"); return -1; }
+    TAMD_ONE_THREAD(g);
+    if (bind_device(g)) return -1;
+    if (!g->prepared || g->half[0]) { set_error("tamd_graph_slot_timestamps: the graph has one launch list (tamd_graph_slots() == 0)"); return -1; }
+    if (!g->inflight.empty()) { set_error("tamd_graph_slot_timestamps while asynchronous runs are in flight"); return -1; }
+    if (direct_drain(g)) return -1;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    g->stream_dirty = false;
+    g->out_fresh_in = 0;                       // the passes write the staging buffers themselves
+    return slots_timestamps(g, passes, start_us, end_us, max_stamps);
 }
 double tamd_graph_prerun_ms(const tamd_graph* g) { return g ? g->prerun_ms : 0.0; }
 
@@ -545,10 +564,14 @@ int tamd_graph_time_launches(tamd_graph* g, int iters, float* total_ms)
     if (g->direct) {        // the passes are not on the stream: host clock around submit .. complete
         if (direct_drain(g)) return -1;
         HIPCHK(hipStreamSynchronize(g->stream));
+        // slot 0 alone: this figure describes a pass as the dependent chain it is (tools/make_plans.py ranks plans by it, and
+        // tamd_graph_direct_timestamps stamps the same chain)
+        g->slot_hold = true;
         const auto t0 = std::chrono::steady_clock::now();
-        for (int i = 0; i < iters; i++)
-            if (tamd_graph_launch(g)) return -1;
-        if (direct_drain(g)) return -1;
+        int rc = 0;
+        for (int i = 0; i < iters && !rc; i++) rc = tamd_graph_launch(g);
+        g->slot_hold = false;
+        if (rc || direct_drain(g)) return -1;
         *total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return 0;
     }

@@ -1,4 +1,4 @@
-// What the translation units of the graph layer share (private).  The layer is ten units:
+// What the translation units of the graph layer share (private).  The layer is eleven units:
 //   graph.hip             the C ABI that builds, describes, pre-runs, profiles, reads and destroys a graph
 //   graph_infer.hip       shape inference, validation, the PriorBox evaluator, the error string
 //   graph_plan_common.hip what every planner shares: dev_alloc (arena), tensor geometry, the NCHW planners' buffer front and output
@@ -11,6 +11,7 @@
 //                         graph_plan.h is what the int8 units share
 //   plan_cache.hip        TAMD_PLAN_CACHE
 //   graph_pair.hip        a batched graph as two half-batch graphs side by side behind one handle (tamd_options.split_batch)
+//   graph_slots.hip       one launch list as two slots on two HSA queues: two passes in flight (graph_slots.h: the host-only arithmetic)
 //   graph_exec.hip        run_steps, the direct path's self-checks, zero-copy lists, the run-side entry points
 //   graph_u8.hip, graph_f32.hip   the uint8 / fp32 planners (plan_u8, plan_f32): dense NCHW tensors
 // node_rules.h (through graph.h) states once the node-local rules that the support query, validate_graph and the planners share.
@@ -38,6 +39,7 @@ void plan_cache_flush();                     // plan_cache.hip
 int run_steps(tamd_graph* g, hipStream_t s, int io_slot = -1);
 int launch_io(tamd_graph* g, int slot);
 int direct_selfcheck(tamd_graph* g);
+void selfcheck_noise(const tamd_graph* g, const IOBind& io, unsigned* lcg_state, std::vector<unsigned char>* noise);   // pseudo-random bytes (finite floats) for one graph input
 bool io_zero_copy_wanted();
 bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot);
 bool zero_copy_inputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot);
@@ -46,6 +48,11 @@ int bind_device(tamd_graph* g);
 int direct_drain(tamd_graph* g);
 void direct_abandon(tamd_graph* g, const char* why);
 int stage_from_pinned(tamd_graph* g);
+
+// graph_slots.hip: two passes in flight on two HSA queues behind one handle (tamd_options.split_batch)
+void slots_try_build(tamd_graph* g, const std::vector<LaunchRec>& recs, int mode);   // never an error: the graph stays one list when anything is in the way
+void slots_destroy(tamd_graph* g);           // waits for slot 1's passes, then releases its program, queue and memory
+int slots_timestamps(tamd_graph* g, int passes, double* start_us, double* end_us, int max_stamps);
 
 // graph_pair.hip: a batched graph as two half-batch device graphs behind one tamd_graph (tamd_options.split_batch); every entry point
 // of the C ABI forwards to these when g->half[0] is set

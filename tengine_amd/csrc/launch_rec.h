@@ -81,6 +81,9 @@ const char* direct_packet_name(const DirectProgram* p, int i);       // kernel s
 // `passes` back-to-back passes with every packet stamped by the HSA runtime's dispatch profiling: mean duration of packet i and mean
 // gap to the next packet's start, microseconds (direct.cc); returns the packet count, -1 on error
 int direct_timestamps(DirectProgram* p, int passes, double* dur_us, double* gap_us);
+// one burst of `passes` rounds of (a pass of `a`, a pass of `b`) on their two queues, every packet stamped: raw start / end in
+// microseconds from the earliest start, [(round * 2 + queue) * packets + packet]; returns the rounds stamped, -1 on error
+int direct_timestamps_two(DirectProgram* a, DirectProgram* b, int passes, double* start_us, double* end_us);
 int direct_meta_packets(const DirectProgram* p);      // of those, how many took their hidden-argument offsets from code-object metadata
 void direct_destroy(DirectProgram* p);
 
