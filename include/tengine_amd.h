@@ -52,7 +52,11 @@ enum {
     TAMD_OP_FC = 3,      /* param: tamd_fc_param    */
     TAMD_OP_POOL = 4,    /* param: tamd_pool_param  */
     TAMD_OP_RELU = 5,    /* param: tamd_relu_param  */
-    TAMD_OP_ELTWISE = 6, /* param: tamd_eltwise_param */
+    TAMD_OP_ELTWISE = 6, /* param: tamd_eltwise_param; PROD 0 / SUM 2 / SUB 4 / MAX 6 of two tensors of one shape in every graph type; in
+                          * int8 / uint8 graphs also the channel gate of a Squeeze-and-Excitation block, x (N,C,H,W) op gate (N,C,1,1) for
+                          * PROD / SUM / SUB -- always x op gate, the gate may be listed first at batch 1 (eltwise_ref.c); the output has
+                          * x's dims.  MAX with a gate, a gate of another shape, one-element operands and the scalar / unary types are
+                          * refused by name (tamd_node_supported answers 0) */
     TAMD_OP_CONCAT = 7,  /* param: tamd_concat_param */
     TAMD_OP_DROPOUT = 8, /* identity */
     TAMD_OP_UPSAMPLE = 9,/* param: tamd_upsample_param; nearest, an integer factor >= 1; fp32 / uint8 graphs, and int8 graphs for a 4-D

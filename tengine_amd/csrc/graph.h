@@ -314,6 +314,17 @@ int plan_shuffle_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
 int plan_prelu(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // prelu_refusal (node_rules.h) asked of a node of this graph, payload included: validate_graph and plan_prelu
 const char* prelu_refusal_of(const tamd_graph* g, const HNode& n);
+// eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
+// same-shape form, else which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1)
+const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated);
+// the byte-map node (Sigmoid / Clip / HardSwish / Mish) that produces the gate of the channel-gate Eltwise `e` and can run inside
+// its launch -- the gate has no other reader, is no graph output and no view, TAMD_PIN=gate_lut=0 is not set --, -1: none.  What
+// only a planner knows of its layout (int8: dense / view bookkeeping before the buffers exist) stays with that planner
+int gate_lut_producer(const tamd_graph* g, const HNode& e, int gated);
+// a channel-gate Eltwise of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch: chan_gate_i8 / chan_gate_u8 (chan_gate.hip); with
+// lut_node >= 0 that node's byte table is uploaded and applied to the gate bytes in the same launch (lut_chan_gate_*), its output
+// tensor is fused away
+int plan_chan_gate(tamd_graph* g, HNode& n, int gated, int lut_node, std::vector<Step>* out);
 // output placement of a dense NCHW tensor: elements per image of the buffer it lives in (a concat slice when it is a view; first channel: c_off)
 inline int nchw_out_img(const HTensor& t) { return (t.is_view ? t.cs : t.c) * t.h * t.w; }
 // .. and the small things their node planners share.  A softmax / concat axis (negative: from the back) as [outer][on][inner] of

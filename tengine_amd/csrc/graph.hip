@@ -130,11 +130,15 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         return 1;
     }
     case TAMD_OP_ELTWISE: {
-        const int ty = n->param ? ((const tamd_eltwise_param*)n->param)->type : -1;
-        if (n_in != 2 || !eltwise_type_on_device(ty)) return 0;
-        if (in[0].dim_num != in[1].dim_num) return 0;
-        for (int i = 0; i < in[0].dim_num; i++) if (in[0].dims[i] != in[1].dims[i]) return 0;
-        return in[0].ttype != TAMD_TT_CONST && in[1].ttype != TAMD_TT_CONST;
+        if (n_in != 2 || !in) return 0;
+        int gated = -1;
+        if (eltwise_refusal((const tamd_eltwise_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, in[1].dim_num,
+                            in[1].dims, in[1].ttype == TAMD_TT_CONST, (size_t)in[1].quant_num, (size_t)out[0].quant_num, &gated))
+            return 0;
+        const tamd_tensor_desc& big = in[gated == 1 ? 1 : 0];     // eltwise.c infer_shape: the output has the dims of the operand with more elements
+        if (gated >= 0 && out[0].dim_num != big.dim_num) return 0;
+        for (int i = 0; gated >= 0 && i < big.dim_num; i++) if (out[0].dims[i] != big.dims[i]) return 0;
+        return 1;
     }
     case TAMD_OP_CONCAT: {
         int ax = n->param ? ((const tamd_concat_param*)n->param)->axis : 1;

@@ -208,7 +208,12 @@ int infer_shapes(tamd_graph* g)
             y.dims = {x.dims[0], x.dims[1], pg.oh, pg.ow};
             break;
         }
-        case TAMD_OP_RELU: case TAMD_OP_RELU6: case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT: case TAMD_OP_SOFTMAX:
+        case TAMD_OP_ELTWISE: {           // eltwise.c infer_shape: the dims of the operand with more elements (a channel gate may be listed first)
+            const HTensor& big = n.in.size() > 1 && g->tensors[n.in[1]].elems() > x.elems() ? g->tensors[n.in[1]] : x;
+            y.dims = big.dims;
+            break;
+        }
+        case TAMD_OP_RELU: case TAMD_OP_RELU6: case TAMD_OP_DROPOUT: case TAMD_OP_SOFTMAX:
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
             y.dims = x.dims;
             break;
@@ -328,6 +333,11 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_PRELU) {
             const char* why = prelu_refusal_of(g, n);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_ELTWISE) {
+            int gated = -1;
+            const char* why = eltwise_refusal_of(g, n, &gated);
             if (why) return bad(n, why);
         }
         if (n.op != TAMD_OP_CONV && n.op != TAMD_OP_FC) continue;

@@ -202,6 +202,26 @@ static void plan_split_views(tamd_graph* g, I8Layout& L)
     }
 }
 
+// Byte map -> channel-gate Eltwise as ONE launch (the tail of a Squeeze-and-Excitation block: Sigmoid -> Eltwise PROD(x, gate)): the
+// Eltwise's launch reads the byte map's INPUT and maps the N * C gate bytes through the node's table itself (chan_gate.hip), the byte map
+// has no launch and its output is never written.  Matched BEFORE plan_buffers: the launch runs at the Eltwise's position and reads the
+// byte map's input there, past that tensor's last reader in node order, and plan_buffers keeps it alive until then.  Neither tensor of
+// the byte map may be a concat view, an alias or dense (permuted / flattened) here.  TAMD_PIN=gate_lut=0: two launches
+static void match_gate_lut(tamd_graph* g, I8Layout& L)
+{
+    for (size_t ei = 0; ei < g->nodes.size(); ei++) {
+        const HNode& e = g->nodes[ei];
+        int gated = -1;
+        if (e.op != TAMD_OP_ELTWISE || eltwise_refusal_of(g, e, &gated) || gated < 0) continue;
+        const int pj = gate_lut_producer(g, e, gated);
+        if (pj < 0 || pj >= (int)ei || L.fused[pj]) continue;
+        bool plain = true;
+        for (int t : {g->nodes[pj].in[0], g->nodes[pj].out[0], e.in[gated], e.out[0]}) plain &= L.view_of[t] < 0 && L.alias_of[t] < 0 && !L.dense[t];
+        if (!plain) continue;
+        L.gate_lut[ei] = pj + 1; L.fused[pj] = 1;
+    }
+}
+
 // graph inputs: NCHW staging; first conv with <=4 channels reads NCHW directly
 static int plan_input_staging(tamd_graph* g)
 {
@@ -281,6 +301,9 @@ static int plan_buffers(tamd_graph* g, I8Layout& L)
         if (L.flat_concat[ni])
             for (int i : g->nodes[ni].in)
                 if (L.perm_src[i] >= 0) { const int r = root_of(L.perm_src[i]); death[r] = std::max(death[r], ni); }
+    // the input of a byte map that runs inside its channel-gate Eltwise's launch (match_gate_lut) is read at the ELTWISE's position
+    for (int ni = 0; ni < NN; ni++)
+        if (L.gate_lut[ni]) { const int r = root_of(g->nodes[L.gate_lut[ni] - 1].in[0]); death[r] = std::max(death[r], ni); }
     std::vector<char> pinned(g->tensors.size(), 0);
     for (auto& io : g->inputs) pinned[root_of(io.tensor)] = 1;
     for (auto& io : g->outputs) pinned[root_of(io.tensor)] = 1;
@@ -775,8 +798,15 @@ static int plan_upsample(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>
     return 0;
 }
 
-static int plan_eltwise(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>* out)
+// the same-shape form: eltwise_i8 (+ the ReLU behind it); the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate, with the
+// byte map in front of the gate where match_gate_lut took it.  The ReLU-behind-Eltwise fusion is not extended to the gate form
+static int plan_eltwise(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
+    HNode& n = g->nodes[ni];
+    int gated = -1;
+    const char* why = eltwise_refusal_of(g, n, &gated);
+    if (why) { set_error("eltwise %s: %s", n.name.c_str(), why); return -1; }
+    if (gated >= 0) return plan_chan_gate(g, n, gated, L.gate_lut[ni] - 1, out);
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
     HTensor* y = &g->tensors[n.out[0]];
@@ -826,7 +856,9 @@ int plan_i8(tamd_graph* g)
     if (plan_dense(g, L)) return -1;
     match_cat_shuffle(g, L);
     plan_split_views(g, L);
-    if (plan_concat_views(g, L) || plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
+    if (plan_concat_views(g, L)) return -1;
+    match_gate_lut(g, L);                    // (behind every pass that makes a tensor a view, in front of the one that shares buffers)
+    if (plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
     scan_eltwise_fusion(g, L);
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
@@ -849,7 +881,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n, &out); break;
         case TAMD_OP_RELU: r = plan_relu(g, L, ni, &out); break;
         case TAMD_OP_UPSAMPLE: r = plan_upsample(g, L, n, &out); break;
-        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, n, &out); break;
+        case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, ni, &out); break;
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: r = plan_lut(g, n, &out); break;
         case TAMD_OP_INTERP: r = plan_interp(g, n, &out); break;
         case TAMD_OP_SPLIT: r = plan_split(g, L, n, &out); break;

@@ -18,12 +18,15 @@ namespace tamd {
 // uint8 tensors, dense int8 tensors, NHWC tensors without padding -- is a run of bytes.  A concat view is refused by name, as plan_relu
 // does: neither planner makes one of these nodes' tensors a view (plan_concat_views: slice_capable; plan_u8: in_place), so the error
 // guards a change to those lists.
-int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
+static const char* lut_name(int op) { return op == TAMD_OP_SIGMOID ? "sigmoid" : op == TAMD_OP_CLIP ? "clip" : op == TAMD_OP_HARDSWISH ? "hardswish" : "mish"; }
+
+// the byte table of one of these nodes between its two tensors, uploaded: what plan_lut applies with lut_u8 and plan_chan_gate inside
+// the gate's launch
+static int lut_table_upload(tamd_graph* g, const HNode& n, unsigned** dtable)
 {
-    HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
-    const char* what = n.op == TAMD_OP_SIGMOID ? "sigmoid" : n.op == TAMD_OP_CLIP ? "clip" : n.op == TAMD_OP_HARDSWISH ? "hardswish" : "mish";
-    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    const char* what = lut_name(n.op);
     if (x.scales.empty() || y.scales.empty()) { set_error("%s %s: missing quant params", what, n.name.c_str()); return -1; }
     if (x.dims != y.dims || x.dtype != y.dtype) { set_error("%s %s: output shape / type mismatch", what, n.name.c_str()); return -1; }
     if (!lut_rank_on_device(n.op, (int)x.dims.size())) { set_error("%s %s: only a 4-D tensor runs on the device", what, n.name.c_str()); return -1; }
@@ -33,8 +36,17 @@ int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
         set_error("%s %s: not supported on the device for data type %d", what, n.name.c_str(), x.dtype);
         return -1;
     }
+    return upload(g, table, dtable);
+}
+
+int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    const char* what = lut_name(n.op);
+    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
     unsigned* dtable = nullptr;
-    if (upload(g, table, &dtable)) return -1;
+    if (lut_table_upload(g, n, &dtable)) return -1;
     LutArgs a{};
     a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
     const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
@@ -46,6 +58,80 @@ int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
         a.count = x.elems();
     }
     out->push_back(make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
+const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated)
+{
+    *gated = -1;
+    if (n.in.size() != 2 || n.out.empty()) return "Eltwise runs on the device on two tensors";
+    const HTensor& a = g->tensors[n.in[0]];
+    const HTensor& b = g->tensors[n.in[1]];
+    return eltwise_refusal(&n.p.elt, a.dtype, (int)n.in.size(), (int)a.dims.size(), a.dims.data(), a.ttype == TAMD_TT_CONST, a.scales.size(), (int)b.dims.size(), b.dims.data(),
+                           b.ttype == TAMD_TT_CONST, b.scales.size(), g->tensors[n.out[0]].scales.size(), gated);
+}
+
+int gate_lut_producer(const tamd_graph* g, const HNode& e, int gated)
+{
+    if (gated < 0 || !tamd_pin_int("gate_lut", 1)) return -1;
+    const int gate = e.in[1 - gated];
+    if (g->tensors[gate].is_view || count_consumers(g, gate) != 1) return -1;      // (a graph output counts as a consumer)
+    for (size_t pj = 0; pj < g->nodes.size(); pj++) {
+        const HNode& p = g->nodes[pj];
+        if (p.out.size() != 1 || p.out[0] != gate) continue;
+        if (!is_lut_op(p.op) || p.in.size() != 1) return -1;
+        const HTensor& pre = g->tensors[p.in[0]];
+        if (!lut_op_on_device(p.op, pre.dtype) || pre.ttype == TAMD_TT_CONST || pre.is_view || pre.dims != g->tensors[gate].dims || pre.scales.size() != 1) return -1;
+        return (int)pj;
+    }
+    return -1;
+}
+
+// The channel-gate Eltwise, int8 and uint8 graphs alike (graph_u8.hip calls this too): x is input `gated`, the gate the other one, and
+// the launch computes x op gate whichever is listed first (eltwise_ref.c: run).  No view on any of the three tensors, as in plan_eltwise.
+// lut_node >= 0 (gate_lut_producer; the planner has skipped that node): the launch reads that node's INPUT and maps it through the
+// node's table itself, and the node's own output -- the gate tensor -- is never written.
+int plan_chan_gate(tamd_graph* g, HNode& n, int gated, int lut_node, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[gated]];
+    HTensor& gate = g->tensors[n.in[1 - gated]];
+    HTensor& src = lut_node >= 0 ? g->tensors[g->nodes[lut_node].in[0]] : gate;      // the bytes the launch reads for the gate
+    HTensor& y = g->tensors[n.out[0]];
+    if (x.is_view || gate.is_view || src.is_view || y.is_view) { set_error("eltwise %s: views / broadcast not supported", n.name.c_str()); return -1; }
+    if (y.dims != x.dims || y.dtype != x.dtype || gate.dtype != x.dtype || src.dtype != x.dtype) { set_error("eltwise %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    unsigned* dtable = nullptr;
+    if (lut_node >= 0 && lut_table_upload(g, g->nodes[lut_node], &dtable)) return -1;
+    const int type = n.p.elt.type, N = x.dims[0], C = x.dims[1], HW = x.dims[2] * x.dims[3];
+    const std::string node = lut_node >= 0 ? g->nodes[lut_node].name + "+" + n.name : n.name;
+    const double bytes = 2.0 * (double)x.elems() + (double)gate.elems();
+    if (x.dtype == TAMD_DT_INT8) {
+        if (x.nchw_raw || y.nchw_raw || src.nchw_raw || x.cs <= 0 || x.cs % 16 || x.cs != y.cs || src.cs != x.cs || x.c_off || y.c_off || src.c_off || x.c != C || C > x.cs
+            || src.h * src.w != 1) {
+            set_error("eltwise %s: the operands and the output are not NHWC tensors of one pixel stride", n.name.c_str());
+            return -1;
+        }
+        ChanGateI8Args a{};
+        a.x = (const int8_t*)x.dptr; a.gate = (const int8_t*)src.dptr; a.y = (int8_t*)y.dptr;
+        a.N = N; a.HW = HW; a.C = C; a.cs = x.cs; a.type = type;
+        a.sx = x.scales[0]; a.sg = gate.scales[0]; a.out_scale = y.scales[0]; a.table = dtable;
+        a.iters = tamd_pin_int("gate_iters", 0);        // (tests: the walk of several pixels per lane on a small tensor)
+        out->push_back(make_step(node, lut_node >= 0 ? "lut_chan_gate_i8" : "chan_gate_i8", 0, bytes, [a](hipStream_t s) { return launch_chan_gate_i8(a, s); },
+                                 {access_of(x), access_of(src)}, {access_of(y)}, false));
+    } else {
+        if (!x.nchw_raw || !y.nchw_raw || !src.nchw_raw) { set_error("eltwise %s: the operands and the output are not dense NCHW tensors", n.name.c_str()); return -1; }
+        ChanGateU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.gate = (const uint8_t*)src.dptr; a.y = (uint8_t*)y.dptr;
+        a.planes = (long)N * C; a.HW = HW; a.type = type;
+        a.sx = x.scales[0]; a.sg = gate.scales[0]; a.out_scale = y.scales[0];
+        a.zx = x.zps.empty() ? 0 : x.zps[0]; a.zg = gate.zps.empty() ? 0 : gate.zps[0]; a.out_zp = y.zps.empty() ? 0 : y.zps[0];
+        a.table = dtable;
+        out->push_back(make_step(node, lut_node >= 0 ? "lut_chan_gate_u8" : "chan_gate_u8", 0, bytes, [a](hipStream_t s) { return launch_chan_gate_u8(a, s); },
+                                 {access_of(x), access_of(src)}, {access_of(y)}, false));
+    }
+    if (lut_node >= 0) {
+        if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+        g->fused_away[n.in[1 - gated]] = 1;              // the byte map's output only exists inside the launch
+    }
     return 0;
 }
 

@@ -753,8 +753,14 @@ static int plan_concat_u8(tamd_graph* g, HNode& n, const std::vector<int>& perm_
     return 0;
 }
 
-static int plan_eltwise_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+// the same-shape form: eltwise_u8; the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate (graph_plan_maps.hip), with the
+// byte map in front of the gate (node lut_node, -1: none) inside the launch
+static int plan_eltwise_u8(tamd_graph* g, HNode& n, int lut_node, std::vector<Step>* out)
 {
+    int gated = -1;
+    const char* why = eltwise_refusal_of(g, n, &gated);
+    if (why) { set_error("eltwise %s: %s", n.name.c_str(), why); return -1; }
+    if (gated >= 0) return plan_chan_gate(g, n, gated, lut_node, out);
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
     HTensor& y = g->tensors[n.out[0]];
@@ -871,6 +877,14 @@ int plan_u8(tamd_graph* g)
     std::vector<char> skip_perm;
     const std::vector<int> perm_src = find_permute_concats(g, &skip_perm);
     std::vector<char> fused(g->nodes.size(), 0);          // ReLU / pool nodes that the conv in front of them carries
+    // byte map -> channel-gate Eltwise as one launch (gate_lut_producer): gate_lut[eltwise node] = the byte map's node + 1, which is skipped
+    std::vector<int> gate_lut(g->nodes.size(), 0);
+    for (size_t ei = 0; ei < g->nodes.size(); ei++) {
+        int gated = -1;
+        if (g->nodes[ei].op != TAMD_OP_ELTWISE || eltwise_refusal_of(g, g->nodes[ei], &gated) || gated < 0) continue;
+        const int pj = gate_lut_producer(g, g->nodes[ei], gated);
+        if (pj >= 0 && pj < (int)ei) { gate_lut[ei] = pj + 1; fused[pj] = 1; }
+    }
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (fused[ni]) continue;
@@ -896,7 +910,7 @@ int plan_u8(tamd_graph* g)
             break;
         case TAMD_OP_PRIORBOX: rc = plan_priorbox_u8(g, n, x, y); break;
         case TAMD_OP_CONCAT: rc = plan_concat_u8(g, n, perm_src, &out); break;
-        case TAMD_OP_ELTWISE: rc = plan_eltwise_u8(g, n, &out); break;
+        case TAMD_OP_ELTWISE: rc = plan_eltwise_u8(g, n, gate_lut[ni] - 1, &out); break;
         default:
             set_error("op %d (%s) is not supported on the device for uint8", n.op, n.name.c_str());
             rc = -1;

@@ -366,6 +366,28 @@ struct PreluU8Args {       // dense NCHW uint8: plane p = n * C + c of HW bytes 
     int shared;            // one slope, one table, for every channel
 };
 
+// The channel gate of a Squeeze-and-Excitation block (chan_gate.hip): y = requant(x op gate), x (N, C, H, W), gate (N, C, 1, 1), op PROD 0 |
+// SUM 2 | SUB 4 as x op gate (eltwise_ref.c: the operand with more elements comes first whichever input it is).  table != nullptr: the
+// gate bytes are the INPUT of the byte-map node in front of the gate (Sigmoid, Clip, ..) and go through that node's table first
+struct ChanGateI8Args {    // NHWC int8: x and y N * HW pixels of cs bytes, the gate N pixels of cs bytes; all three 16-byte aligned
+    const int8_t* x; const int8_t* gate; int8_t* y;
+    int N, HW, C, cs;      // cs (a multiple of 16) bytes per pixel, C of them channels; the padding lanes [C, cs) of y are written 0
+    int type;
+    float sx, sg, out_scale;
+    const unsigned* table; // [64]: tamd_lut_table's 256 bytes as they lie, or nullptr
+    int iters;             // pixels a lane walks in turn; 0: the launcher's rule (by the size of the tensor)
+};
+
+struct ChanGateU8Args {    // dense NCHW uint8: plane p = n * C + c of HW bytes has the one gate byte gate[p]
+    const uint8_t* x; const uint8_t* gate; uint8_t* y;      // x and y 16-byte aligned and laid out alike
+    long planes;           // N * C
+    int HW;
+    int type;
+    float sx, sg, out_scale;
+    int zx, zg, out_zp;
+    const unsigned* table; // as above
+};
+
 struct SoftmaxI8Args {     // softmax over ONE axis of an int8 tensor: the channels of an NHWC tensor (a view's channel slice included), or --
                            // round 6 -- any axis of a dense (reference-order) or NHWC tensor
     const int8_t* x; int8_t* y;
@@ -490,6 +512,8 @@ hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
 hipError_t launch_prelu_i8(const PreluI8Args& a, hipStream_t s);
 hipError_t launch_prelu_u8(const PreluU8Args& a, hipStream_t s);
+hipError_t launch_chan_gate_i8(const ChanGateI8Args& a, hipStream_t s);
+hipError_t launch_chan_gate_u8(const ChanGateU8Args& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);
 hipError_t launch_concat_copy_i8(const CatCopyArgs& a, hipStream_t s);
 hipError_t launch_flatcat_i8(const FlatCatI8Args& a, hipStream_t s);

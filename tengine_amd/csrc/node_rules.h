@@ -15,6 +15,53 @@ namespace tamd {
 // Eltwise: the binary forms over two tensors of one shape -- ELT_PROD 0, ELT_SUM 2, ELT_SUB 4, ELT_MAX 6 (eltwise_param.h); the odd
 // values next to them are the tensor-with-scalar forms, 7 and up the unary ones: no device kernel for those
 inline bool eltwise_type_on_device(int type) { return type == 0 || type == 2 || type == 4 || type == 6; }
+// .. and the channel gate of a Squeeze-and-Excitation block: x (N, C, H, W) op gate (N, C, 1, 1), int8 and uint8 graphs (chan_gate.hip).
+// fp32 graphs keep it on the CPU device (their Sigmoid is there anyway)
+inline bool chan_gate_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// One Eltwise node: nullptr when the device runs it, else the reason.  *gated: -1 for the same-shape form, else which input (0 | 1) is
+// x, the operand with more elements; the other one is the gate.  a / b: inputs 0 / 1.
+// eltwise_ref.c: run() makes the operand with more elements in0, whichever input it is, and hands over input_chan = dims[-4] * dims[-3]
+// (N * C), input_hw = H * W and input1_count4 = the smaller operand's element count; the branch input_chan == input1_count4 of
+// ref_eltwise_int8 / _uint8 computes out[i] = in0[i] op in1[i / input_hw] for PROD, SUM and SUB: always x op gate, for SUB too.
+//  - MAX has no such branch: its loop reads in1[i] over the larger count, past the gate's end -- no bytes to equal
+//  - the gate listed first takes input_chan = dims[1] (C, not N * C): at batch > 1 PROD and SUB fail and SUM leaves most of the output
+//    unwritten
+//  - a smaller operand of another shape (2-D, (1, N * C, 1, 1), one element, a row of H * W) takes other branches of the reference, or
+//    the same one with a meaning the device tensors' layout does not carry: each is refused by its own name
+inline const char* eltwise_refusal(const tamd_eltwise_param* p, int dtype, int input_num, int a_dim_num, const int* a_dims, bool a_const, size_t a_quant, int b_dim_num,
+                                   const int* b_dims, bool b_const, size_t b_quant, size_t out_quant, int* gated)
+{
+    *gated = -1;
+    if (!p) return "Eltwise needs its parameter";
+    if (input_num != 2) return "Eltwise runs on the device on two tensors";
+    bool same = a_dim_num == b_dim_num;
+    for (int i = 0; same && i < a_dim_num; i++) same = a_dims[i] == b_dims[i];
+    if (!eltwise_type_on_device(p->type)) return "the scalar and unary Eltwise types do not run on the device";
+    if (a_const || b_const) return "Eltwise: neither operand may be a constant";
+    if (same) return nullptr;                                     // PROD, SUM, SUB, MAX of two tensors of one shape, every graph type
+    auto elems = [](int n, const int* d) { size_t e = 1; for (int i = 0; i < n; i++) e *= (size_t)d[i]; return e; };
+    const size_t ea = elems(a_dim_num, a_dims), eb = elems(b_dim_num, b_dims);
+    const int big = ea >= eb ? 0 : 1;
+    const int xn = big ? b_dim_num : a_dim_num, gn = big ? a_dim_num : b_dim_num;
+    const int* xd = big ? b_dims : a_dims;
+    const int* gd = big ? a_dims : b_dims;
+    const size_t eg = big ? ea : eb;
+    if (!chan_gate_on_device(dtype)) return "Eltwise operands of different shapes run on the device in int8 and uint8 graphs only";
+    if (ea == eb) return "Eltwise operands of one size and different shapes do not run on the device";
+    if (eg == 1) return "an Eltwise with a one-element operand does not run on the device";
+    if (p->type == 6) return "Eltwise MAX has no channel-gate form: the reference reads past the gate's end";
+    if (xn != 4 || (size_t)xd[2] * xd[3] <= 1) return "a gated Eltwise operand must be 4-D (N, C, H, W) with H * W > 1";
+    if (eg != (size_t)xd[0] * xd[1]) {
+        const size_t ghw = gn >= 2 ? (size_t)gd[gn - 2] * gd[gn - 1] : gn == 1 ? (size_t)gd[0] : 0;      // (run(): input_hw_1)
+        if (ghw == (size_t)xd[2] * xd[3]) return "the row form of Eltwise (input_hw == input_hw_1) does not run on the device";
+        return "Eltwise operands of different shapes: the smaller one must be a channel gate (N, C, 1, 1)";
+    }
+    if (gn != 4 || gd[0] != xd[0] || gd[1] != xd[1] || gd[2] != 1 || gd[3] != 1) return "an Eltwise gate must be 4-D with dims exactly (N, C, 1, 1)";
+    if (a_quant != 1 || b_quant != 1 || out_quant != 1) return "a gated Eltwise needs per-tensor quant params on all three tensors";
+    if (big == 1 && xd[0] != 1) return "an Eltwise gate listed first is defined for batch 1 only";
+    *gated = big;
+    return nullptr;
+}
 
 // Permute: NCHW -> NHWC, the one order SSD heads use (Permute -> Flatten -> Concat)
 inline bool permute_order_on_device(const int* o) { return o[0] == 0 && o[1] == 2 && o[2] == 3 && o[3] == 1; }
