@@ -93,6 +93,12 @@ enum {
      * reference widens with its own routine -- not IEEE: every exact power of two (0.25, 1, ...) widens to +0, so such a PReLU is a
      * ReLU (tamd_prelu_slope).  prelu_ref.c:160-384; int8 saturates at +-127.  fp32 graphs keep the node on the CPU device */
     TAMD_OP_PRELU = 25,
+    /* YOLOv4-tiny's routes (darknet "route groups=2 group_id=1") and the x[..., ::2, ::2] of YOLOv5's Focus, uint8 graphs: param
+     * tamd_slice_param.  The onnx form with one output on a 4-D tensor: any axis, any batch, step >= 1 (slice_ref.c:229-291); the
+     * reference dequantises, copies floats and requantises byte to byte (tamd_slice_table), and copies the bytes as they are when the
+     * output has the input's dims.  The caffe, mxnet and tf forms, int8 graphs (no kernel in the reference) and fp32 graphs stay on
+     * the CPU device */
+    TAMD_OP_SLICE = 26,
     TAMD_OP_NUM
 };
 
@@ -136,6 +142,14 @@ typedef struct tamd_interp_param { int resize_type; float width_scale, height_sc
 #define TAMD_SPLIT_MAX 8
 typedef struct tamd_split_param { int axis; int num; int sizes[TAMD_SPLIT_MAX]; } tamd_split_param;
 typedef struct tamd_shufflechannel_param { int group; } tamd_shufflechannel_param;   /* shuffle_channel_param.h */
+/* slice_param.h as the reference's loader and infer_shape leave it: axis normalised into [0, rank) (slice.c:52-53), begin / end / step of
+ * the onnx and mxnet forms (a stored step of 0 means 1), the three form flags.  The three vectors of the caffe and tf forms are not
+ * carried, only their element counts, so that those forms can be refused by name */
+typedef struct tamd_slice_param {
+    int axis, begin, end, step;
+    int iscaffe, ismxnet, isonnx;
+    int slice_point_num, begin_num, size_num;
+} tamd_slice_param;
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */
@@ -238,7 +252,7 @@ TAMD_API const char* tamd_version(void);
 /* 1 if (op, dtype) can run on the device -- what allocator.describe publishes */
 TAMD_API int tamd_op_supported(int op, int dtype);
 /* 1 if this node with these parameters and tensors (descriptors only; the one const payload read, where it is given, is a PReLU's
- * slope: a value that widens to inf or NaN is refused) is one the device
+ * slope: a value that widens to inf or NaN is refused; a Slice needs the scales and zero points of both tensors, for its byte map) is one the device
  * compiles; 0 -> leave it to the CPU device.  Replaces the per-op parameter tests a backend makes while it walks a
  * subgraph (source/device/cuda/cuda_executor.cc:72-134 fails Build() instead; tensorrt: trt_limit.hpp) */
 TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_desc* inputs, int input_num,
@@ -267,6 +281,11 @@ TAMD_API int tamd_interp_indices(int in_extent, int out_extent, float scale, int
  * table.  0, or -1 without a table */
 TAMD_API int tamd_shuffle_sources(int channels, int group, int* src);
 TAMD_API int tamd_split_table(float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
+/* the byte map of a uint8 Slice between tensors of these quantisation parameters (csrc/slice_tables.cc; no GPU needed): table[b] =
+ * round(((float)b - (float)in_zp) * in_scale / out_scale + (float)out_zp) clamped to 0 .. 255 -- every step a float operation of its own,
+ * the rounding the double round() (slice_ref.c:488-505).  0, or -1 when a scale is not finite and positive or one of the 256 values
+ * before the clamp is not finite or lies outside int: the reference's conversion is undefined there and the node is refused */
+TAMD_API int tamd_slice_table(float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
 /* the host truth of a quantised PReLU node (csrc/prelu_tables.cc; no GPU needed).
  * tamd_prelu_slope: the float the reference makes of one fp16 slope (bit pattern), as its fp16_to_fp32 (source/utility/float.c) does
  * on x86: normal halves with a non-zero fraction and infinities as IEEE; a normal half whose fraction is zero -- every exact power of

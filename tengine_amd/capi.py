@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_prelu_slope", "tamd_prelu_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -93,6 +93,7 @@ def lib():
         L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
         L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        L.tamd_slice_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_prelu_slope.argtypes = [C.c_ushort]
         L.tamd_prelu_slope.restype = C.c_float
         L.tamd_prelu_table.argtypes = [ci, C.c_ushort, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
@@ -104,6 +105,19 @@ OP_SIGMOID, OP_CLIP, OP_HARDSWISH, OP_MISH = 16, 17, 18, 19      # TAMD_OP_* of 
 OP_INTERP = 20
 OP_SPLIT, OP_SHUFFLECHANNEL = 22, 23
 OP_PRELU = 25          # (24: reserved, like 21)
+OP_SLICE = 26
+
+
+class SliceParam(C.Structure):        # tamd_slice_param
+    _fields_ = [(k, C.c_int) for k in ("axis", "begin", "end", "step", "iscaffe", "ismxnet", "isonnx", "slice_point_num", "begin_num", "size_num")]
+
+
+def slice_table(in_scale, in_zp, out_scale, out_zp):
+    """tamd_slice_table(): the 256 output bytes of a uint8 Slice between tensors of these quantisation parameters; None where the
+    reference's conversion to int is undefined.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_slice_table(in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 SPLIT_MAX = 8
 
 

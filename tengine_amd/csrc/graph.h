@@ -53,6 +53,7 @@ union NodeParam {
     tamd_interp_param interp;
     tamd_split_param split;
     tamd_shufflechannel_param shuffle;
+    tamd_slice_param slice;
 };
 
 struct HNode {
@@ -314,6 +315,15 @@ int plan_shuffle_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
 int plan_prelu(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // prelu_refusal (node_rules.h) asked of a node of this graph, payload included: validate_graph and plan_prelu
 const char* prelu_refusal_of(const tamd_graph* g, const HNode& n);
+// slice_refusal (node_rules.h) asked of a node of this graph: infer_shapes (check_out false: the output's dims are not made yet),
+// validate_graph and plan_slice_u8.  *geom / table[256] (either may be null): the resolved box and the byte map
+const char* slice_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, SliceGeom* geom, unsigned char* table);
+// the Slice that can run inside the launch of Slice `ni` (a chain of two as one slice_u8 launch): the one reader of its output, which
+// is no graph output; both nodes pass slice_refusal; TAMD_PIN=slice_chain=0 is not set.  Its node index, -1: none
+int slice_chain_next(const tamd_graph* g, size_t ni);
+// a Slice node of a uint8 (NCHW) graph as ONE slice_u8 launch (slice.hip); with next >= 0 that Slice too: boxes and byte maps
+// composed, the tensor between them fused away
+int plan_slice_u8(tamd_graph* g, HNode& n, int next, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
 // same-shape form, else which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1)
 const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated);

@@ -81,6 +81,7 @@ int tamd_op_supported(int op, int dtype)
     if (is_lut_op(op)) return lut_op_on_device(op, dtype);         // byte maps by table: the quantised forms the reference has (which ranks: tamd_node_supported)
     if (op == TAMD_OP_INTERP) return interp_on_device(dtype);      // nearest, int8 / uint8 (which modes, sizes and ranks: tamd_node_supported)
     if (op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL) return chanmap_on_device(dtype);      // byte movers, int8 / uint8 (which forms: tamd_node_supported)
+    if (op == TAMD_OP_SLICE) return slice_on_device(dtype);        // the onnx form, uint8 (which forms and extents: tamd_node_supported)
     if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
@@ -219,6 +220,14 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         for (int i = 0; i < 4; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
         return 1;
     }
+    case TAMD_OP_SLICE: {
+        if (n_in < 1 || !in) return 0;
+        return slice_refusal((const tamd_slice_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                             in[0].quant_num == 1 && in[0].scales ? in[0].scales[0] : 0.f, in[0].quant_num == 1 && in[0].zero_points ? in[0].zero_points[0] : 0, n_out,
+                             (size_t)out[0].quant_num, out[0].quant_num == 1 && out[0].scales ? out[0].scales[0] : 0.f,
+                             out[0].quant_num == 1 && out[0].zero_points ? out[0].zero_points[0] : 0, out[0].dim_num, out[0].dims, nullptr, nullptr)
+               == nullptr;
+    }
     case TAMD_OP_PRELU: {
         if (n_in < 2 || !in) return 0;
         if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
@@ -289,6 +298,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_INTERP: n.p.interp = *(const tamd_interp_param*)d->param; break;
         case TAMD_OP_SPLIT: n.p.split = *(const tamd_split_param*)d->param; break;
         case TAMD_OP_SHUFFLECHANNEL: n.p.shuffle = *(const tamd_shufflechannel_param*)d->param; break;
+        case TAMD_OP_SLICE: n.p.slice = *(const tamd_slice_param*)d->param; break;
         default: break;
         }
     }

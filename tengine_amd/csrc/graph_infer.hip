@@ -247,6 +247,13 @@ int infer_shapes(tamd_graph* g)
             break;
         }
         case TAMD_OP_SHUFFLECHANNEL: y.dims = x.dims; break;
+        case TAMD_OP_SLICE: {             // slice.c:116-156, the onnx form: end clipped to the dimension, end <= 0 counted from the back,
+            SliceGeom sg;                 // (extent - 1) / step + 1.  Every other form is refused HERE, by name (slice_refusal)
+            const char* why = slice_refusal_of(g, n, false, &sg, nullptr);
+            if (why) { set_error("slice %s: %s", n.name.c_str(), why); return -1; }
+            y.dims.assign(sg.out_dims, sg.out_dims + 4);
+            break;
+        }
         case TAMD_OP_PRELU: y.dims = x.dims; y.dtype = x.dtype; break;      // prelu.c: the input's shape; the type is the data's, not the fp16 slope's
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
@@ -329,6 +336,10 @@ int validate_graph(tamd_graph* g)
             const HTensor& x = g->tensors[n.in[0]];
             const char* why = shuffle_refusal(&n.p.shuffle, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(),
                                               g->tensors[n.out[0]].scales.size());
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_SLICE) {
+            const char* why = slice_refusal_of(g, n, true, nullptr, nullptr);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_PRELU) {

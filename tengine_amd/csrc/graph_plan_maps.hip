@@ -1,5 +1,5 @@
 // The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
-// table (plan_lut), PReLU, nearest Interp, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu and plan_interp
+// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu and plan_interp
 // serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
 // graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
 #include "graph.h"
@@ -380,6 +380,81 @@ int plan_cat_shuffle(tamd_graph* g, I8Layout& L, HNode& cat, size_t sj, std::vec
     out->push_back(st);
     L.fused[sj] = 1;
     g->fused_away[cat.out[0]] = 1;
+    return 0;
+}
+
+// ---- Slice of a uint8 graph (slice.hip).  Everything the reference decides for the node is decided by slice_refusal (node_rules.h):
+// the form, the resolved box, the raw copy, the byte map
+const char* slice_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, SliceGeom* geom, unsigned char* table)
+{
+    if (n.in.empty() || n.out.empty()) return "Slice takes one input";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    return slice_refusal(&n.p.slice, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), x.scales.empty() ? 0.f : x.scales[0],
+                         x.zps.empty() ? 0 : x.zps[0], (int)n.out.size(), y.scales.size(), y.scales.empty() ? 0.f : y.scales[0], y.zps.empty() ? 0 : y.zps[0],
+                         (int)y.dims.size(), check_out ? y.dims.data() : nullptr, geom, table);
+}
+
+int slice_chain_next(const tamd_graph* g, size_t ni)
+{
+    const HNode& n = g->nodes[ni];
+    if (!tamd_pin_int("slice_chain", 1) || n.op != TAMD_OP_SLICE || n.out.size() != 1) return -1;
+    const int mid = n.out[0];
+    if (g->tensors[mid].is_view || count_consumers(g, mid) != 1) return -1;      // (a graph output counts as a consumer)
+    for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
+        const HNode& m = g->nodes[nj];
+        if (m.in.empty() || m.in[0] != mid) continue;
+        if (m.op != TAMD_OP_SLICE || m.in.size() != 1 || slice_refusal_of(g, n, true, nullptr, nullptr) || slice_refusal_of(g, m, true, nullptr, nullptr)) return -1;
+        return (int)nj;
+    }
+    return -1;
+}
+
+// One slice_u8 launch for the node, or for the node and the Slice `next` that alone reads it: output position o of the second is
+// position start2 + o * step2 of the first's output, which is position start1 + (..) * step1 of x -- per axis start1 + start2 * step1
+// and step1 * step2 -- and the byte map is table2[table1[b]], exact because both are byte maps (a raw-copy member is the identity).
+// A concat view on either side is refused by name: plan_u8 makes neither tensor one (in_place), which the error guards
+int plan_slice_u8(tamd_graph* g, HNode& n, int next, std::vector<Step>* out)
+{
+    HNode* m = next >= 0 ? &g->nodes[next] : nullptr;
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[(m ? *m : n).out[0]];
+    const std::string node = m ? n.name + "+" + m->name : n.name;
+    SliceGeom sg[2];
+    unsigned char map[2][256];
+    const char* why = slice_refusal_of(g, n, true, &sg[0], map[0]);
+    if (!why && m) why = slice_refusal_of(g, *m, true, &sg[1], map[1]);
+    if (why) { set_error("slice %s: %s", node.c_str(), why); return -1; }
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("slice %s on a concat view is not supported in a uint8 graph", node.c_str()); return -1; }
+    const SliceGeom& last = sg[m ? 1 : 0];
+    if (y.dtype != x.dtype || y.dims.size() != 4 || x.dims.size() != 4) { set_error("slice %s: output shape / type mismatch", node.c_str()); return -1; }
+    SliceU8Args a{};
+    for (int i = 0; i < 4; i++) {
+        a.in_dims[i] = x.dims[i]; a.out_dims[i] = last.out_dims[i]; a.start[i] = 0; a.step[i] = 1;
+        if (y.dims[i] != last.out_dims[i]) { set_error("slice %s: output shape / type mismatch", node.c_str()); return -1; }
+    }
+    a.start[sg[0].axis] = sg[0].start; a.step[sg[0].axis] = sg[0].step;
+    if (m) {
+        a.start[sg[1].axis] += sg[1].start * a.step[sg[1].axis];
+        a.step[sg[1].axis] *= sg[1].step;
+    }
+    std::vector<unsigned> table(64, 0u);
+    unsigned char* tb = (unsigned char*)table.data();
+    a.identity = 1;
+    for (int b = 0; b < 256; b++) {
+        tb[b] = m ? map[1][map[0][b]] : map[0][b];
+        a.identity &= tb[b] == b;
+    }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
+    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+    a.w2 = tamd_pin_int("slice_w2", 1) ? 1 : 0;             // 0: the byte-by-byte path at W step 2 too (A/B runs)
+    out->push_back(make_step(node, "slice_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_slice_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    if (m) {
+        if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+        g->fused_away[n.out[0]] = 1;                        // the tensor between the two only exists inside the launch
+    }
     return 0;
 }
 

@@ -885,6 +885,13 @@ int plan_u8(tamd_graph* g)
         const int pj = gate_lut_producer(g, g->nodes[ei], gated);
         if (pj >= 0 && pj < (int)ei) { gate_lut[ei] = pj + 1; fused[pj] = 1; }
     }
+    // Slice -> Slice as one launch (slice_chain_next): slice_next[first] = the second's node + 1, which is skipped
+    std::vector<int> slice_next(g->nodes.size(), 0);
+    for (size_t si = 0; si < g->nodes.size(); si++) {
+        if (g->nodes[si].op != TAMD_OP_SLICE || fused[si]) continue;
+        const int nj = slice_chain_next(g, si);
+        if (nj > (int)si && !fused[nj]) { slice_next[si] = nj + 1; fused[nj] = 1; }
+    }
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (fused[ni]) continue;
@@ -904,6 +911,7 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_INTERP: rc = plan_interp(g, n, &out); break;
         case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // one chan_map_u8 launch per output
         case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
+        case TAMD_OP_SLICE: rc = plan_slice_u8(g, n, slice_next[ni] - 1, &out); break;      // one slice_u8 launch, the Slice behind it inside
         case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it

@@ -349,6 +349,21 @@ struct ChanMapU8Args {
     int identity;
 };
 
+// Slice of a uint8 graph (slice.hip; the host truth of the byte map: slice_tables.cc), dense NCHW: a strided box of x,
+// y[n][c][h][w] = table[x[start0 + n * step0][start1 + c * step1][start2 + h * step2][start3 + w * step3]].  One Slice node cuts one
+// axis; two in a row compose into one box over two axes
+struct SliceU8Args {
+    const uint8_t* x; uint8_t* y;
+    int in_dims[4], out_dims[4];   // N, C, H, W of either tensor; start[i] + (out_dims[i] - 1) * step[i] < in_dims[i]: launch_slice_u8 checks it
+    int start[4], step[4];         // every step >= 1
+    int out_img, out_c0;           // output image stride (bytes) / channel offset, as in ChanMapU8Args
+    const unsigned* table;         // [64]: the 256 bytes of the map as they lie
+    int identity;                  // the map is the identity (equal parameters, or the reference's raw copy): no table, no LDS
+    int w2;                        // 1: an output row's 16 bytes at W step 2 come from two 16-byte loads and byte permutes; 0: byte by byte
+    int contig;                    // (set by launch_slice_u8) how far consecutive output bytes are consecutive source bytes: 0 nowhere (W
+                                   // step > 1), 1 inside a row, 2 inside a plane (W not cut, H step 1), 3 inside an image (H not cut, C step 1)
+};
+
 // PReLU of a quantised graph (prelu.hip; the host truth: prelu_tables.cc)
 struct PreluI8Args {       // NHWC int8, x and y of one pixel stride: y = requant(x < 0 ? x * slope[c] : x), the chain of relu_i8 per channel
     const int8_t* x; int8_t* y;
@@ -510,6 +525,7 @@ hipError_t launch_interp_u8(const InterpU8Args& a, hipStream_t s);
 hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s);
 hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
+hipError_t launch_slice_u8(const SliceU8Args& a, hipStream_t s);
 hipError_t launch_prelu_i8(const PreluI8Args& a, hipStream_t s);
 hipError_t launch_prelu_u8(const PreluU8Args& a, hipStream_t s);
 hipError_t launch_chan_gate_i8(const ChanGateI8Args& a, hipStream_t s);

@@ -9,6 +9,7 @@
 #include "interp_tables.h"
 #include "lut_tables.h"
 #include "prelu_tables.h"
+#include "slice_tables.h"
 
 namespace tamd {
 
@@ -149,6 +150,69 @@ inline const char* shuffle_refusal(const tamd_shufflechannel_param* p, int dtype
     if (in_dim_num != 4 || in_const) return "ShuffleChannel takes a 4-D tensor that is not a constant";
     if (p->group < 1 || in_dims[1] < 1 || in_dims[1] % p->group != 0) return "ShuffleChannel: the group count must divide the channels";
     if (in_quant != 1 || out_quant != 1) return "ShuffleChannel needs per-tensor quant params on both sides";
+    return nullptr;
+}
+
+// Slice: the onnx form of a uint8 graph (slice_ref.c; slice.hip).  The reference has no int8 kernel (its run fails), and fp32 graphs keep
+// the node on the CPU device
+inline bool slice_on_device(int dtype) { return dtype == TAMD_DT_UINT8; }
+// what slice_refusal resolves for its callers: the strided box along the one axis that is cut, the output's dims, and whether the node
+// is the reference's raw copy (out dims == in dims: a memcpy, no requantisation whatever the parameters, slice_ref.c:440-445)
+struct SliceGeom {
+    int axis, start, stop, step;
+    int out_dims[4];
+    bool raw_copy;
+};
+// One Slice node: nullptr when the device runs it (*geom resolved, table[256]: the byte map between the two tensors, the identity for
+// the raw copy; table may be null), else the reason.  p is what the reference holds AFTER its infer_shape: axis in [0, 4), or as a file
+// stores it (negative: counted from the back, slice.c:52-53).  out_dims: the output's dims where the caller has them (null: not checked).
+//  - caffe form: outputs 1.. get floats written into byte tensors (slice_ref.c:494-505 requantises output 0 only); mxnet: the 4-D
+//    branch copies start_3 - stop_3 bytes, a negative length; tf: its own off-by-one -- no bytes to equal in any of them
+//  - begin >= stop: infer_shape turns an extent of 0 into the input's dimension and a negative one into a negative dimension
+//  - begin < 0, step < 0: the reference indexes in front of the input, or never ends
+inline const char* slice_refusal(const tamd_slice_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, float in_scale, int in_zp,
+                                 int output_num, size_t out_quant, float out_scale, int out_zp, int out_dim_num, const int* out_dims, SliceGeom* geom,
+                                 unsigned char* table)
+{
+    if (!p) return "Slice needs its parameter";
+    if (!slice_on_device(dtype)) return "Slice runs on the device in uint8 graphs only";
+    if (p->iscaffe) return "the caffe form of Slice (slice points, several outputs) does not run on the device";
+    if (p->ismxnet) return "the mxnet form of Slice does not run on the device";
+    if (!p->isonnx) return "the tf form of Slice (begin and size vectors) does not run on the device";
+    if (output_num != 1) return "Slice runs on the device with one output only";
+    if (in_dim_num != 4) return "Slice runs on the device on a 4-D tensor only";
+    if (in_const) return "Slice: the input must not be a constant";
+    if (in_quant != 1 || out_quant != 1) return "Slice needs per-tensor quant params on both sides";
+    for (int i = 0; i < 4; i++)
+        if (in_dims[i] < 1) return "Slice: every input dimension must be at least 1";
+    int axis = p->axis;
+    if (axis < -4 || axis >= 4) return "Slice: the axis is outside the tensor's rank";
+    axis = (axis + 4) % 4;                                        // slice.c:52-53
+    if (p->step < 0) return "Slice: a negative step does not run on the device";
+    if (p->begin < 0) return "Slice: a negative begin does not run on the device";
+    const int dim = in_dims[axis];
+    const int end = p->end > dim ? dim : p->end;                  // slice.c:124-128 clips, and run() reads the clipped value
+    const int stop = end > 0 ? end : dim + end;                   // slice_ref.c:248-251
+    const int step = p->step > 1 ? p->step : 1;
+    if (p->begin >= stop) return "Slice: begin is not below the resolved end (an empty or negative extent)";
+    SliceGeom sg;
+    sg.axis = axis; sg.start = p->begin; sg.stop = stop; sg.step = step;
+    for (int i = 0; i < 4; i++) sg.out_dims[i] = in_dims[i];
+    sg.out_dims[axis] = (stop - p->begin - 1) / step + 1;         // slice.c:131-145, the same count the element loops of onnx_run write
+    sg.raw_copy = sg.out_dims[axis] == dim;
+    if (out_dims) {
+        if (out_dim_num != 4) return "Slice: the output does not have the dims the reference infers";
+        for (int i = 0; i < 4; i++)
+            if (out_dims[i] != sg.out_dims[i]) return "Slice: the output does not have the dims the reference infers";
+    }
+    unsigned char map[256];
+    if (sg.raw_copy) {
+        for (int b = 0; b < 256; b++) map[b] = (unsigned char)b;
+    } else if (tamd_slice_table(in_scale, in_zp, out_scale, out_zp, map)) {
+        return "Slice: the quantisation parameters give a value the reference cannot convert to int";
+    }
+    if (table) for (int b = 0; b < 256; b++) table[b] = map[b];
+    if (geom) *geom = sg;
     return nullptr;
 }
 

@@ -75,6 +75,7 @@ int map_op(uint32_t t)
     case 20: return TAMD_OP_RELU;
     case 21: return TAMD_OP_RELU6;
     case 23: return TAMD_OP_RESHAPE;
+    case 27: return TAMD_OP_SLICE;
     case 28: return TAMD_OP_SOFTMAX;
     case 29: return TAMD_OP_SPLIT;
     case 37: return TAMD_OP_SIGMOID;
@@ -203,6 +204,18 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                     if (!r.ok || sizes.size() > TAMD_SPLIT_MAX) p.split.num = TAMD_SPLIT_MAX + 1;      // refused by count (split_refusal)
                     else { p.split.num = (int)sizes.size(); for (size_t i = 0; i < sizes.size(); i++) p.split.sizes[i] = (int)sizes[i]; }
                 }
+                break;
+            }
+            case TAMD_OP_SLICE: {                              // TM2_SliceParam :607-619 {axis, offset slice_points, offset begins, offset sizes,
+                tamd_slice_param& q = p.slice;                 // iscaffe, ismxnet, isonnx, begin, end, step} (tm2_slice.c:48-92)
+                q.axis = r.i32(po); q.iscaffe = r.i32(po + 16); q.ismxnet = r.i32(po + 20); q.isonnx = r.i32(po + 24);
+                q.begin = r.i32(po + 28); q.end = r.i32(po + 32); q.step = r.i32(po + 36);
+                auto count = [&](uint32_t vo_) { return vo_ ? (int)r.u32(vo_) : 0; };      // TM2_NOT_SET: no vector; the device carries the counts only
+                q.slice_point_num = count(r.u32(po + 4)); q.begin_num = count(r.u32(po + 8)); q.size_num = count(r.u32(po + 12));
+                // slice.c:52-53: a negative axis counts from the back of the input's rank.  Outside the rank the reference's infer_shape
+                // fails; the value stays as it is and slice_refusal names it
+                const int rank = !vi.empty() && vi[0] < g->tensors.size() ? (int)g->tensors[vi[0]].dims.size() : 0;
+                if (rank > 0 && q.axis >= -rank && q.axis < rank) q.axis = (q.axis + rank) % rank;
                 break;
             }
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)

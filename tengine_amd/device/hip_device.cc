@@ -54,6 +54,7 @@ extern "C" {
 #include "pooling_param.h"
 #include "priorbox_param.h"
 #include "shuffle_channel_param.h"
+#include "slice_param.h"
 #include "relu_param.h"
 #include "softmax_param.h"
 #include "split_param.h"
@@ -95,6 +96,9 @@ const OpRow kOps[] = {
     // the activation of the face models (csrc/prelu.hip): the two quantised kernels of the reference; its fp16 slope constant travels
     // like any constant.  An fp32 graph keeps the node on the CPU device (which ranks and slopes: tamd_node_supported)
     {OP_PRELU, TAMD_OP_PRELU, true},
+    // YOLOv4-tiny's routes and Focus's strided picks (csrc/slice.hip): the onnx form in uint8 graphs.  The reference has no int8 kernel, and
+    // an fp32 graph keeps the node on the CPU device -- the caffe Slice of the ShuffleNet benchmark file too (which: tamd_node_supported)
+    {OP_SLICE, TAMD_OP_SLICE, true},
 };
 
 const OpRow* find_op(int op)
@@ -135,7 +139,7 @@ bool translate_priorbox(const struct priorbox_param* p, tamd_priorbox_param* q)
 }
 
 // descriptor of an IR tensor.  with_payload: the constant's bytes and the quantisation values travel too (pre_run); without, shapes
-// and the quantisation form alone (tamd_node_supported looks at nothing else, but for a PReLU's slope).  The pointers stay the IR tensor's own.
+// and the quantisation form alone (tamd_node_supported looks at nothing else, but for a PReLU's slope and a Slice's scales).  The pointers stay the IR tensor's own.
 tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 {
     tamd_tensor_desc d;
@@ -157,7 +161,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -213,6 +217,16 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
         break;
     }
     case TAMD_OP_SHUFFLECHANNEL: s->shuffle.group = ((const struct shuffle_channel_param*)n->op.param_mem)->group; break;
+    case TAMD_OP_SLICE: {            // as infer_shape has left it (slice.c:52-53, 124-128: axis normalised, end clipped); the vectors as counts
+        const struct slice_param* p = (const struct slice_param*)n->op.param_mem;
+        s->slice = tamd_slice_param{};
+        s->slice.axis = p->axis; s->slice.begin = p->begin; s->slice.end = p->end; s->slice.step = p->step;
+        s->slice.iscaffe = p->iscaffe; s->slice.ismxnet = p->ismxnet; s->slice.isonnx = p->isonnx;
+        s->slice.slice_point_num = p->slice_point_ ? get_vector_num(p->slice_point_) : 0;
+        s->slice.begin_num = p->begin_ ? get_vector_num(p->begin_) : 0;
+        s->slice.size_num = p->size_ ? get_vector_num(p->size_) : 0;
+        break;
+    }
     case TAMD_OP_SPLIT: {            // the split_sizes vector inline; num -1: is_caffe, 0: no sizes, above TAMD_SPLIT_MAX: too many (all refused by name)
         const struct split_param* p = (const struct split_param*)n->op.param_mem;
         s->split = tamd_split_param{};
@@ -507,9 +521,11 @@ static bool node_supported(struct graph* ir, struct node* n)
     if (op < 0) return false;
     if (op == TAMD_OP_INPUT || op == TAMD_OP_CONST) return true;
     std::vector<tamd_tensor_desc> in, out;
-    // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device)
-    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), op == TAMD_OP_PRELU && k == 1));
-    for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), false));
+    // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device --
+    // and for a Slice's quantisation values on both sides: a pair whose byte map the reference cannot compute does the same)
+    const bool values = op == TAMD_OP_SLICE;
+    for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), values || (op == TAMD_OP_PRELU && k == 1)));
+    for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), values));
     NodeParams params;
     std::vector<int> ii(in.size()), oi(out.size());
     tamd_node_desc nd;

@@ -28,7 +28,7 @@ LAYOUT_NCHW = 0
 OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
-    "Reshape": 23, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
+    "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Clip": 87, "Mish": 97,
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
@@ -177,6 +177,15 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         n = struct.unpack_from("<I", b, voff)[0] if voff else 0
         return {"axis": axis, "split_dim": split_dim, "is_caffe": is_caffe, "is_onnx": is_onnx,
                 "split_sizes": list(struct.unpack_from("<%di" % n, b, voff + 4)) if n else []}
+    if op == "Slice":           # TM2_SliceParam (tm2_format.h:607-619): {axis, three offsets -> TM2_Vector_dims, iscaffe, ismxnet, isonnx, begin, end, step}
+        axis, vsp, vbg, vsz, iscaffe, ismxnet, isonnx, begin, end, step = struct.unpack_from("<i3I6i", b, off)
+
+        def vi(o):
+            n = struct.unpack_from("<I", b, o)[0] if o else 0
+            return list(struct.unpack_from("<%di" % n, b, o + 4)) if n else []
+
+        return {"axis": axis, "slice_points": vi(vsp), "begins": vi(vbg), "sizes": vi(vsz), "iscaffe": iscaffe, "ismxnet": ismxnet,
+                "isonnx": isonnx, "begin": begin, "end": end, "step": step}
     if op == "Permute":
         v = struct.unpack_from("<5i", b, off)
         return {"flag": v[0], "order": list(v[1:])}
@@ -265,6 +274,11 @@ def write_tm2(g: Graph) -> bytes:
             sizes = q.get("split_sizes", [])     # loader takes `axis` from the file only then (tm2_split.c:61-65)
             pb = struct.pack("<iiBBxxI", q.get("axis", 1), q.get("split_dim", 1), q.get("is_caffe", 0), q.get("is_onnx", 1),
                              bl.vec_i32(sizes) if sizes else 0)
+        elif n.op == "Slice":    # TM2_SliceParam; each of the three vectors is TM2_NOT_SET (0) unless given (tm2_slice.c:62-87 tests for it).
+            q = n.params         # isonnx defaults to 1, step to 1: the form the darknet and ONNX converters write
+            vecs = [bl.vec_i32(q[k]) if q.get(k) else 0 for k in ("slice_points", "begins", "sizes")]
+            pb = struct.pack("<i3I6i", q.get("axis", 1), vecs[0], vecs[1], vecs[2], q.get("iscaffe", 0), q.get("ismxnet", 0), q.get("isonnx", 1),
+                             q.get("begin", 0), q.get("end", 0), q.get("step", 1))
         elif n.op == "PriorBox":  # TM2_PriorBoxParam; the loader dereferences all four vector offsets (tm2_priorbox.c:49-52): empty
             q = n.params        # vectors are written as {v_num = 0}
             pb = struct.pack("<4I5i3f2i", bl.vec_f32(q["min_size"]), bl.vec_f32(q.get("max_size", [])),
