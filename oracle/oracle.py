@@ -411,6 +411,17 @@ def run_graph(g, x, keep_all=False, teacher=None, report=None):
             y = np.concatenate([vals[i] for i in n.inputs], axis=p.get("axis", 1))
         elif op == "Upsample" and dt == DT_UINT8:
             y = upsample_uint8(a, int(p.get("scale", 2)), qp(i0), qp(o0))
+        elif op == "Upsample" and dt == DT_FP32:
+            # upsample_ref.c:39-72: out[h][w] = in[(int)(h / scale)][(int)(w / scale)] with a float scale -- for the integer scales a
+            # graph can carry here that is each input element repeated scale x scale times, no arithmetic on the values
+            s = int(p.get("scale", 2))
+            y = np.repeat(np.repeat(a, s, axis=2), s, axis=3)
+        elif op == "ReLU6" and dt == DT_FP32:
+            # relu6_ref.c:95-123: copy, then "> 6 -> 6", then "< 0 -> 0" (two comparisons, no arithmetic: -0.0 and values inside
+            # [0, 6] pass unchanged).  The reference's loop runs over the channels of image 0 only and leaves the other images of a
+            # batch unwritten; the node's meaning, and what is restated here, is the clamp of every element
+            y = np.where(a > 6, np.float32(6), a)
+            y = np.where(y < 0, np.float32(0), y).astype(np.float32)
         elif op == "Softmax" and dt == DT_FP32:
             ax = p.get("axis", 1)
             e = np.exp(a - a.max(axis=ax, keepdims=True))

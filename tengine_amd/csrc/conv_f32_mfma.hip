@@ -258,8 +258,8 @@ static int region_dw(int wd) { return (32 / (64 / wd)) * (wd == 16 ? 64 : 80); }
 
 int conv_f32_mfma_pick(const F32ConvArgs& a)
 {
-    static const char* e = exp_env("TAMD_F32_CFG");
-    if (e && *e) return atoi(e) % 5;
+    const int pin = tamd_pin_int("f32_cfg", -1);        // tests / fuzzing: pin one tile shape (read at every prerun; any shape is
+    if (pin >= 0 && pin <= 4) return pin;               // legal in any of the five); a value outside 0..4: not pinned
     const int OHW = a.OH * a.OW, N8 = a.tail_split ? (OHW & ~7) : OHW;
     auto blocks = [&](int bm, int bn) { return (long)((N8 + bn - 1) / bn + (OHW != N8 ? 1 : 0)) * ((a.cout + bm - 1) / bm) * a.N; };
     if (OHW <= 16 && a.cout > 32) return 4;            // 1x1 .. 4x4 maps: 64 channels x 16 pixels

@@ -170,6 +170,15 @@ def i8_unary_graph(seed, op, dims, out_scale=None, **params):
     return g, rng.integers(-127, 128, size=dims).astype(np.int8)
 
 
+def f32_unary_graph(op, dims, out_dims=None, **params):
+    """one fp32 node `op` on an input of `dims` (the caller draws the input: what matters differs from op to op)"""
+    g = Graph(name="f32_%s_case" % op)
+    x = g.add_input("data", list(dims), tm2.DT_FP32, None, None)
+    y = g.add_tensor("out", list(out_dims or dims), tm2.DT_FP32, tm2.TT_VAR, None, None, None)
+    g.output_nodes = [g.add_node(op.lower(), op, [x], [y], **params)]
+    return g
+
+
 def _u8q(rng, lo=0.01, hi=0.05):
     # zero points near mid-range keep the accumulators centred (a random zp pair saturates every output);
     # extreme zero points are exercised through the explicit in_zp / w_zp / out_zp arguments

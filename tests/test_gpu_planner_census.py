@@ -28,8 +28,8 @@ NO_FORM = {"u8_patch": 0, "u8_pw": 0, "u8_c3": 0}          # the GEMM family alo
 def glue_graph(dtype, seed=7, n=2, c=8, h=8, w=8):
     """data -> ReLU r (written in place into the Concat); data -> max-pool 2x2 -> Upsample x2 -> u; Eltwise SUM(u, data) -> e (copied into
     the Concat); Concat([r, e], channels) -> Softmax over the channels.  uint8: r carries the Concat's quantisation (the in-place rule).
-    fp32: u is a leaky ReLU of data instead -- the oracle has no fp32 Upsample, and upsample_f32 is planned by the function that plans
-    relu_f32 (plan_map_f32); pool_f32 has a case of its own"""
+    fp32: u is a leaky ReLU of data instead -- upsample_f32 is planned by the function that plans relu_f32 (plan_map_f32) and is compared
+    with the oracle in test_gpu_f32_glue.py; pool_f32 has a case of its own"""
     rng = np.random.default_rng(seed)
     u8 = dtype == DT_UINT8
     g = Graph(name="glue_case")

@@ -36,6 +36,10 @@ CASES = [
     (1, 32, 12, 12, 32, 3, 1, 1, 32, 0, True, 1),      # depthwise -> conv_ref
     (2, 24, 13, 13, 24, 3, 2, 1, 24, 6, True, 1),
     (1, 16, 9, 9, 32, 3, 1, 1, 4, 1, True, 1),
+    # K = 29187 / 29205, past the LDS limit of the device's tap table: two of the shapes test_gpu_f32_mfma.py runs on the LDS-DMA form
+    (2, 3243, 3, 5, 70, 3, 1, 1, 1, 0, True, 1),       # K % 4 == 3, 8 main + 7 tail pixels, rows 68 and 69 outside the row blocks
+    (1, 3245, 2, 2, 13, 3, 1, 1, 1, -1, True, 1),      # K % 4 == 1, tail pixels only, 8-block + 4-block + one single row
+    (1, 3246, 1, 9, 15, 3, 1, 1, 1, -1, True, 1),      # K % 4 == 2 with a tail pixel and three single rows
 ]
 
 

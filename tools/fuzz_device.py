@@ -1,7 +1,7 @@
 """Randomised device-vs-oracle campaign (runs ON THE GPU BOX; the oracle is the checker, nothing under test uses it).
 
 Same random single-op graphs as tools/fuzz_oracle.py, run through the C ABI on the GPU with a randomly pinned member
-of the kernel family (TAMD_FORCE_GEMM and the TAMD_PIN keys u8_cfg / u8_patch / u8_patch_cfg / u8_c3 / u8_dw_th / first_rows / dw_form) and compared byte for byte with
+of the kernel family (TAMD_FORCE_GEMM and the TAMD_PIN keys u8_cfg / u8_patch / u8_patch_cfg / u8_c3 / u8_dw_th / f32_cfg / first_rows / dw_form) and compared byte for byte with
 oracle/tg_oracle.c (itself pinned to the real reference by fuzz_oracle.py).
 
     python tools/fuzz_device.py --dtype uint8 --seconds 50 --seed 1"""
@@ -58,6 +58,9 @@ def main():
                 pins["u8_c3"] = str(int(rng.integers(2)))
             if rng.random() < 0.7:
                 pins["u8_dw_th"] = str(rng.choice(["1", "2", "4"]))
+            # the tile shape of the LDS-DMA form (conv_f32_mfma), taken whenever a random graph's K is past the LDS tap table
+            if rng.random() < 0.8:
+                pins["f32_cfg"] = str(int(rng.integers(5)))
         if pins:
             os.environ["TAMD_PIN"] = ",".join("%s=%s" % kv for kv in pins.items())
         else:
