@@ -167,12 +167,23 @@ struct IOBind {
     void* host_out = nullptr;
     size_t bytes = 0;
     void* stage = nullptr;           // device buffer in the reference's NCHW order
-    void* pinned = nullptr;          // pinned host bounce buffer (slot 0 of the asynchronous runs)
-    void* pinned2 = nullptr;         // slot 1: tamd_graph_run_async keeps two runs in flight
+    void* pinned[2] = {nullptr, nullptr};   // pinned host bounce buffers, one per I/O slot (IoSlot); allocated in tamd_graph_prerun
+};
+
+// One I/O slot of the host-to-host runs (tamd_graph_run: I/O slot 0; tamd_graph_run_async keeps two runs in flight, one per I/O slot):
+// the launch list with the input upload in front and the output download behind it as copy KERNELS on the device-mapped pinned
+// buffers IOBind::pinned[this slot].  Not the pass slots of graph_slots.hip, which is what "slot" alone means in this layer
+struct IoSlot {
+    DirectProgram* direct = nullptr; // that list as AQL packets on the HSA queue of tamd_graph::direct; nullptr: the hipGraph below
+    bool zero_copy = false;          // .. and it stores the graph outputs straight into the pinned host buffers (no download launch)
+    hipGraph_t hgraph = nullptr;     // the list as a captured graph, two instances launched round-robin (tamd_graph::hexecs says why)
+    hipGraphExec_t hexec[2] = {nullptr, nullptr};
+    int next_exec = 0;
+    hipEvent_t done = nullptr;       // completion of an asynchronous run on the hipGraph path
 };
 
 struct Inflight {                    // one tamd_graph_run_async() that tamd_graph_wait() has not collected yet
-    int slot = 0;
+    int io_slot = 0;
     std::vector<void*> host_out;     // where the caller wants this run's outputs (set_output at submit time)
     hipEvent_t done = nullptr;       // hipGraph path
     bool direct = false;             // direct path: the run is burst `burst` of the graph's HSA queue (direct.cc)
@@ -222,18 +233,11 @@ struct tamd_graph {
     // independent instances the next replay's packets are already in the queue (profiles/r02_*replay*)
     hipGraphExec_t hexecs[4] = {nullptr, nullptr, nullptr, nullptr};
     int nexec = 0, next_exec = 0;
-    // host-to-host runs (tamd_graph_run / _run_async): the same launch list with the input upload in front and the output
-    // download behind it as copy KERNELS on the device-mapped pinned buffers of I/O slot 0 | 1, two instances per slot
-    hipGraph_t hgraph_io[2] = {nullptr, nullptr};
-    hipGraphExec_t hexec_io[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    int next_io[2] = {0, 0};
+    tamd::IoSlot io[2];                        // host-to-host runs (tamd_graph_run / _run_async): the two I/O slots
+    int next_io_slot = 0;                      // the I/O slot of the next tamd_graph_run_async
     std::vector<tamd::Inflight> inflight;      // FIFO, at most 2
-    hipEvent_t slot_done[2] = {nullptr, nullptr};
-    int next_slot = 0;
     tamd::DirectProgram* direct = nullptr;     // tamd_options.direct_dispatch: the launch list as AQL packets (direct.cc)
-    tamd::DirectProgram* direct_io = nullptr;  // .. the host-to-host list of I/O slot 0 (tamd_graph_run), same HSA queue
-    tamd::DirectProgram* direct_io2 = nullptr; // .. of I/O slot 1 (the second asynchronous run in flight)
-    // two slots (graph_slots.hip): a second program of the SAME launch list on an HSA queue of its own, its written buffers re-pointed
+    // two pass slots (graph_slots.hip): a second program of the SAME launch list on an HSA queue of its own, its written buffers re-pointed
     // at a private copy (slot_block); tamd_graph_launch alternates between the two, so two passes are in flight.  nullptr: one list
     tamd::DirectProgram* direct1 = nullptr;
     void* slot_block = nullptr;                // slot 1's copy of everything a pass writes (one allocation)
@@ -246,10 +250,8 @@ struct tamd_graph {
     bool direct_busy = false;                  // passes submitted since the last wait
     bool stream_dirty = true;                  // something may be pending on `stream` (uploads, eager launches): drain it before a direct burst
     bool stream_exposed = false;               // tamd_graph_stream() handed the stream out: the caller may queue work this library cannot see
-    bool io_zero_copy = false;                 // the host-to-host lists store graph outputs straight into the pinned host buffers
-    bool io_zero_copy2 = false;                //   .. the list of I/O slot 1 does
-    int out_fresh_in = 0;                      // 0: the outputs' device staging buffers hold the last pass; 1 / 2: only pinned slot 0 / 1 does
-                                               // (a zero-copy host-to-host run): stage_from_pinned() before anything reads the device copy
+    int out_fresh_in = -1;                     // -1: the outputs' device staging buffers hold the last pass; 0 / 1: only the pinned buffers of that
+                                               // I/O slot do (a zero-copy host-to-host run): stage_from_pinned() before anything reads the device copy
     // TAMD_H2H_TRACE=1: where a blocking tamd_graph_run spends its time on the host (ns): copy in, stream drain, submit, wait, copy out
     long long h2h_ns[5] = {0, 0, 0, 0, 0};
     long long h2h_runs = 0;

@@ -329,14 +329,9 @@ int tamd_graph_set_batch(tamd_graph* g, int batch)
     return 0;
 }
 
-int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
+// the options of a prerun: the caller's blob (may be null), then what the environment says
+static tamd_options resolve_options(const tamd_options* opt)
 {
-    TAMD_ONE_THREAD(g);
-    if (!g) return -1;
-    if (g->prepared) return 0;
-    // a batched graph of batch-wise independent operators: two half-batch device graphs side by side (graph_pair.hip)
-    if (const int pr = pair_try_prerun(g, opt)) return pr < 0 ? -1 : 0;
-    std::lock_guard<std::mutex> lk(g_capture_mutex);
     tamd_options o{};
     o.dev_name = "HIP"; o.size = (int)sizeof(tamd_options); o.gpu_index = 0; o.use_hip_graph = 1; o.profile = 0;
     if (opt) {             // options may be NULL (scheduler.c:49-59); only the fields the caller's blob really holds are read
@@ -362,6 +357,81 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
         if (getenv("HSA_TOOLS_LIB") || getenv("ROCP_TOOL_LIBRARIES") || getenv("ROCPROFILER_LIBRARY") || (pre && strstr(pre, "rocprof"))) o.direct_dispatch = 0;
     }
     if (const char* dt = getenv("TG_DEBUG_TIME")) { if (atoi(dt) == 1) o.profile = 1; }     // cpu_define.h:41-43
+    return o;
+}
+
+// one pass of run_steps for I/O slot `io_slot` (-1: the launch list alone) captured into *out
+static int capture_pass(tamd_graph* g, int io_slot, hipGraph_t* out)
+{
+    HIPCHK(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = run_steps(g, g->stream, io_slot);
+    const hipError_t e = hipStreamEndCapture(g->stream, out);
+    if (rc) return -1;
+    HIPCHK(e);
+    return 0;
+}
+
+// the launch list as hipGraph executables: g->hexecs, and the host-to-host variants of the two I/O slots (g->io[].hexec)
+static int capture_graphs(tamd_graph* g)
+{
+    // one warm eager pass (module load), then capture compute + output layout launches
+    if (run_steps(g, g->stream)) return -1;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (capture_pass(g, -1, &g->hgraph)) return -1;
+    const char* ne = exp_env("TAMD_GRAPH_EXECS");
+    g->nexec = ne ? std::max(1, std::min(4, atoi(ne))) : 3;
+    for (int i = 0; i < g->nexec; i++) HIPCHK(hipGraphInstantiate(&g->hexecs[i], g->hgraph, nullptr, nullptr, 0));
+    g->hexec = g->hexecs[0];
+    const char* ioenv = exp_env("TAMD_IO_GRAPH");
+    for (int io_slot = 0; io_slot < 2 && !(ioenv && atoi(ioenv) == 0); io_slot++) {      // the host-to-host variants (upload / download as launches)
+        IoSlot& s = g->io[io_slot];
+        if (capture_pass(g, io_slot, &s.hgraph)) return -1;
+        for (auto& e : s.hexec) HIPCHK(hipGraphInstantiate(&e, s.hgraph, nullptr, nullptr, 0));
+    }
+    return 0;
+}
+
+// the direct path (tamd_options.direct_dispatch): the launch list, the host-to-host lists of the two I/O slots and the second pass
+// slot as AQL packets.  Whatever is in the way leaves the hipGraph executables; -1: a HIP error
+static int build_direct_programs(tamd_graph* g)
+{
+    // one more eager pass with the launch recorder on (launch_rec.h), then the list as AQL packets (direct.cc); every
+    // module of the list has launched by now, so its code object is loaded and its kernel descriptors resolve
+    std::vector<LaunchRec> recs;
+    if (record_pass(g, -1, &recs)) return -1;
+    const char* why = "";
+    g->direct = direct_build(g->gpu, g->stream, recs, &why);
+    if (!g->direct) fprintf(stderr, "tengine_amd: direct dispatch not used (hipGraph replay instead): %s\n", why);
+    // the packets carry hand-built argument segments (hidden arguments at the code-object-v5 offsets) and hand-picked
+    // fence scopes: ONE direct pass must reproduce the eager pass byte for byte on a non-trivial input, or the graph
+    // keeps its hipGraph (a different ROCm, a renamed kernel, a stale line would otherwise be silently wrong outputs)
+    if (g->direct && !exp_env("TAMD_EXP_NOFENCE") && direct_selfcheck(g)) {
+        fprintf(stderr, "tengine_amd: direct dispatch DISABLED for this graph: %s (hipGraph replay instead)\n", last_error());
+        direct_destroy(g->direct);
+        g->direct = nullptr;
+    }
+    if (!g->direct) return 0;
+    for (int io_slot = 0; io_slot < 2 && g->io[io_slot].hexec[0]; io_slot++)
+        if (build_io_program(g, io_slot)) return -1;
+    // I/O slot 1's program only if I/O slot 0 has one: the asynchronous pair alternates between them
+    if (!g->io[0].direct && g->io[1].direct) { direct_destroy(g->io[1].direct); g->io[1].direct = nullptr; }
+    // two passes in flight: the same list once more on a second queue, its written buffers re-pointed (graph_slots.hip).  Never
+    // an error: whatever is in the way leaves the graph one launch list
+    if (g->opt.split_batch != 1) slots_try_build(g, recs, g->opt.split_batch);
+    if (getenv("TAMD_DEBUG") && g->io[0].direct)
+        fprintf(stderr, "[tamd] host-to-host list: %d packets%s\n", direct_packets(g->io[0].direct), g->io[0].zero_copy ? ", outputs stored straight into the pinned host buffers" : "");
+    return 0;
+}
+
+int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
+{
+    TAMD_ONE_THREAD(g);
+    if (!g) return -1;
+    if (g->prepared) return 0;
+    // a batched graph of batch-wise independent operators: two half-batch device graphs side by side (graph_pair.hip)
+    if (const int pr = pair_try_prerun(g, opt)) return pr < 0 ? -1 : 0;
+    std::lock_guard<std::mutex> lk(g_capture_mutex);
+    tamd_options o = resolve_options(opt);
     const auto prerun_t0 = std::chrono::steady_clock::now();
     g->opt = o;
     if (infer_shapes(g) || validate_graph(g)) return -1;       // a malformed graph is refused before the device is touched
@@ -381,91 +451,13 @@ int tamd_graph_prerun(tamd_graph* g, const tamd_options* opt)
     for (auto& st : g->steps)
         if (st.once) { HIPCHK(st.fn(g->stream)); g->had_once = true; }
     g->steps.erase(std::remove_if(g->steps.begin(), g->steps.end(), [](const Step& st) { return st.once; }), g->steps.end());
+    // the pinned bounce buffers of both I/O slots (no planner reads them)
     for (auto* v : {&g->inputs, &g->outputs})
-        for (auto& io : *v) HIPCHK(hipHostMalloc(&io.pinned2, std::max<size_t>(io.bytes, 16), hipHostMallocDefault));
+        for (auto& io : *v)
+            for (int s = 0; s < 2; s++) HIPCHK(hipHostMalloc(&io.pinned[s], std::max<size_t>(io.bytes, 16), hipHostMallocDefault));
     HIPCHK(hipDeviceSynchronize());
-    if (o.use_hip_graph) {
-        // one warm eager pass (module load), then capture compute + output layout launches
-        if (run_steps(g, g->stream)) return -1;
-        HIPCHK(hipStreamSynchronize(g->stream));
-        HIPCHK(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-        int rc = run_steps(g, g->stream);
-        hipError_t e = hipStreamEndCapture(g->stream, &g->hgraph);
-        if (rc) return -1;
-        HIPCHK(e);
-        const char* ne = exp_env("TAMD_GRAPH_EXECS");
-        g->nexec = ne ? std::max(1, std::min(4, atoi(ne))) : 3;
-        for (int i = 0; i < g->nexec; i++) HIPCHK(hipGraphInstantiate(&g->hexecs[i], g->hgraph, nullptr, nullptr, 0));
-        g->hexec = g->hexecs[0];
-        const char* ioenv = exp_env("TAMD_IO_GRAPH");
-        for (int slot = 0; slot < 2 && !(ioenv && atoi(ioenv) == 0); slot++) {      // the host-to-host variants (upload / download as launches)
-            HIPCHK(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-            rc = run_steps(g, g->stream, slot);
-            e = hipStreamEndCapture(g->stream, &g->hgraph_io[slot]);
-            if (rc) return -1;
-            HIPCHK(e);
-            for (int i = 0; i < 2; i++) HIPCHK(hipGraphInstantiate(&g->hexec_io[slot][i], g->hgraph_io[slot], nullptr, nullptr, 0));
-        }
-        if (o.direct_dispatch) {
-            // one more eager pass with the launch recorder on (launch_rec.h), then the list as AQL packets (direct.cc); every
-            // module of the list has launched by now, so its code object is loaded and its kernel descriptors resolve
-            std::vector<LaunchRec> recs;
-            g_launch_rec = &recs;
-            rc = run_steps(g, g->stream);
-            g_launch_rec = nullptr;
-            if (rc) return -1;
-            HIPCHK(hipStreamSynchronize(g->stream));
-            const char* why = "";
-            g->direct = direct_build(g->gpu, g->stream, recs, &why);
-            if (!g->direct) fprintf(stderr, "tengine_amd: direct dispatch not used (hipGraph replay instead): %s\n", why);
-            // the packets carry hand-built argument segments (hidden arguments at the code-object-v5 offsets) and hand-picked
-            // fence scopes: ONE direct pass must reproduce the eager pass byte for byte on a non-trivial input, or the graph
-            // keeps its hipGraph (a different ROCm, a renamed kernel, a stale line would otherwise be silently wrong outputs)
-            if (g->direct && !exp_env("TAMD_EXP_NOFENCE") && direct_selfcheck(g)) {
-                fprintf(stderr, "tengine_amd: direct dispatch DISABLED for this graph: %s (hipGraph replay instead)\n", last_error());
-                direct_destroy(g->direct);
-                g->direct = nullptr;
-            }
-            const std::vector<LaunchRec> pass_recs = recs;
-            for (int slot = 0; slot < 2 && g->direct && g->hexec_io[slot][0]; slot++) {
-                // the host-to-host list of I/O slot 0 | 1 (upload launch, compute, download launch) on the same queue:
-                // tamd_graph_run and the asynchronous pair
-                recs.clear();
-                g_launch_rec = &recs;
-                rc = run_steps(g, g->stream, slot);
-                g_launch_rec = nullptr;
-                if (rc) return -1;
-                HIPCHK(hipStreamSynchronize(g->stream));
-                // outputs straight into the pinned host buffers (no download launch) where the list allows it
-                std::vector<LaunchRec> with_downloads = recs;
-                bool zc = io_zero_copy_wanted() && zero_copy_outputs(g, recs, slot);
-                if (zero_copy_inputs(g, recs, slot)) zc = true;        // (a failed self-check below falls back to the full list)
-                DirectProgram* pio = direct_build(g->gpu, g->stream, recs, &why, g->direct);
-                bool zc_ok = zc && pio;
-                if (pio && direct_io_selfcheck(g, pio, slot)) {
-                    if (zc) fprintf(stderr, "tengine_amd: zero-copy outputs DISABLED for this graph: %s\n", last_error());
-                    direct_destroy(pio);
-                    pio = nullptr; zc_ok = false; why = last_error();
-                    if (zc) {                                // once more with the download launches
-                        pio = direct_build(g->gpu, g->stream, with_downloads, &why, g->direct);
-                        if (pio && direct_io_selfcheck(g, pio, slot)) { direct_destroy(pio); pio = nullptr; why = last_error(); }
-                    }
-                }
-                if (slot == 0) g->io_zero_copy = zc_ok;
-                else g->io_zero_copy2 = zc_ok;
-                if (!pio) fprintf(stderr, "tengine_amd: direct dispatch not used for host-to-host runs (slot %d): %s\n", slot, why);
-                (slot ? g->direct_io2 : g->direct_io) = pio;
-            }
-            if (!g->direct_io || !g->direct_io2) {          // both or none: the asynchronous pair alternates between them
-                if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
-            }
-            // two passes in flight: the same list once more on a second queue, its written buffers re-pointed (graph_slots.hip).  Never
-            // an error: whatever is in the way leaves the graph one launch list
-            if (g->direct && o.split_batch != 1) slots_try_build(g, pass_recs, o.split_batch);
-            if (getenv("TAMD_DEBUG") && g->direct_io)
-                fprintf(stderr, "[tamd] host-to-host list: %d packets%s\n", direct_packets(g->direct_io), g->io_zero_copy ? ", outputs stored straight into the pinned host buffers" : "");
-        }
-    }
+    if (o.use_hip_graph && capture_graphs(g)) return -1;
+    if (o.use_hip_graph && o.direct_dispatch && build_direct_programs(g)) return -1;
     plan_cache_flush();
     g->prerun_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - prerun_t0).count();
     g->prepared = true;
@@ -534,7 +526,7 @@ int tamd_graph_profile(tamd_graph* g, int iters, tamd_kernel_info* out, int max_
     if (g->half[0]) return pair_profile(g, iters, out, max_out);
     if (!g->inflight.empty()) { set_error("tamd_graph_profile while asynchronous runs are in flight: collect them with tamd_graph_wait first"); return -1; }
     if (direct_drain(g)) return -1;
-    g->out_fresh_in = 0;                       // the launches below (and the closing pass) write the staging buffers themselves
+    g->out_fresh_in = -1;                      // the launches below (and the closing pass) write the staging buffers themselves
     int n = std::min((int)g->steps.size(), max_out);
     std::vector<hipEvent_t> ev(2 * g->steps.size());
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
@@ -600,7 +592,7 @@ int tamd_graph_read_tensor(tamd_graph* g, int idx, void* host, size_t bytes)
     }
     size_t need = t.elems() * esize(t.dtype);
     if (bytes != need) { set_error("read_tensor: %zu bytes given, %zu needed", bytes, need); return -1; }
-    if (g->out_fresh_in)                       // an output whose staging buffer is the tensor itself (1x1 map): see stage_from_pinned
+    if (g->out_fresh_in >= 0)                  // an output whose staging buffer is the tensor itself (1x1 map): see stage_from_pinned
         for (auto& io : g->outputs)
             if (io.tensor == idx && io.stage == t.dptr && stage_from_pinned(g)) return -1;
     if (direct_drain(g)) return -1;
@@ -643,20 +635,18 @@ void tamd_graph_destroy(tamd_graph* g)
     g->inflight.clear();
     if (g->stream) hipStreamSynchronize(g->stream);
     std::lock_guard<std::mutex> lk(g_capture_mutex);      // hipFree is device-synchronous: not while another thread captures
-    if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
-    if (g->direct_io) { direct_destroy(g->direct_io); g->direct_io = nullptr; }
-    slots_destroy(g);
-    if (g->direct) { direct_destroy(g->direct); g->direct = nullptr; }
+    direct_teardown(g);
     for (int i = 0; i < g->nexec; i++) if (g->hexecs[i]) hipGraphExecDestroy(g->hexecs[i]);
-    for (int slot = 0; slot < 2; slot++) {
-        for (int i = 0; i < 2; i++) if (g->hexec_io[slot][i]) hipGraphExecDestroy(g->hexec_io[slot][i]);
-        if (g->hgraph_io[slot]) hipGraphDestroy(g->hgraph_io[slot]);
+    for (auto& s : g->io) {
+        for (auto& e : s.hexec) if (e) hipGraphExecDestroy(e);
+        if (s.hgraph) hipGraphDestroy(s.hgraph);
     }
     if (g->hgraph) hipGraphDestroy(g->hgraph);
     for (void* p : g->dev_allocs) hipFree(p);
     for (auto* v : {&g->inputs, &g->outputs})
-        for (auto& io : *v) { if (io.pinned) hipHostFree(io.pinned); if (io.pinned2) hipHostFree(io.pinned2); }
-    for (auto& e : g->slot_done) if (e) hipEventDestroy(e);
+        for (auto& io : *v)
+            for (void* p : io.pinned) if (p) hipHostFree(p);
+    for (auto& s : g->io) if (s.done) hipEventDestroy(s.done);
     if (g->stream) hipStreamDestroy(g->stream);
     delete g;
 }

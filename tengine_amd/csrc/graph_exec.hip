@@ -5,20 +5,11 @@
 #include "graph_internal.h"
 #include "env.h"
 
-#include <stdarg.h>
-#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
-#include <cmath>
-#include <mutex>
-
-#include "epilogue.h"
 
 namespace tamd {
 
@@ -26,7 +17,7 @@ int run_steps(tamd_graph* g, hipStream_t s, int io_slot)
 {
     if (io_slot >= 0)
         for (auto& io : g->inputs) {
-            hipError_t e = launch_copy_bytes(io.stage, io_slot ? io.pinned2 : io.pinned, io.bytes, s);
+            hipError_t e = launch_copy_bytes(io.stage, io.pinned[io_slot], io.bytes, s);
             if (e != hipSuccess) { set_error("input upload launch failed: %s", hipGetErrorString(e)); return -1; }
         }
     // while the launch list is being recorded for the direct path: a step that provably touches nothing its predecessors since
@@ -70,91 +61,102 @@ int run_steps(tamd_graph* g, hipStream_t s, int io_slot)
         (*g_launch_rec)[rec0].wrap = true;
     if (io_slot >= 0)
         for (auto& io : g->outputs) {
-            hipError_t e = launch_copy_bytes(io_slot ? io.pinned2 : io.pinned, io.stage, io.bytes, s);
+            hipError_t e = launch_copy_bytes(io.pinned[io_slot], io.stage, io.bytes, s);
             if (e != hipSuccess) { set_error("output download launch failed: %s", hipGetErrorString(e)); return -1; }
         }
     return 0;
 }
 
-// one launch of the host-to-host list of I/O slot `slot` on the graph's stream
-int launch_io(tamd_graph* g, int slot)
+// one launch of the host-to-host list of I/O slot `io_slot` on the graph's stream
+static int launch_io(tamd_graph* g, int io_slot)
 {
-    if (g->hexec_io[slot][0]) {
-        hipGraphExec_t e = g->hexec_io[slot][g->next_io[slot]];
-        g->next_io[slot] ^= 1;
+    IoSlot& s = g->io[io_slot];
+    if (s.hexec[0]) {
+        hipGraphExec_t e = s.hexec[s.next_exec];
+        s.next_exec ^= 1;
         HIPCHK(hipGraphLaunch(e, g->stream));
         return 0;
     }
-    return run_steps(g, g->stream, slot);
+    return run_steps(g, g->stream, io_slot);
 }
 
+int record_pass(tamd_graph* g, int io_slot, std::vector<LaunchRec>* recs)
+{
+    recs->clear();
+    g_launch_rec = recs;
+    const int rc = run_steps(g, g->stream, io_slot);
+    g_launch_rec = nullptr;
+    if (rc) return -1;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+
+// ---- what the self-checks share (graph_internal.h) -------------------------------------------------------------------------------
+int selfcheck_fill_inputs(tamd_graph* g, unsigned seed, int io_slot)
+{
+    std::vector<unsigned char> noise;
+    unsigned lcg = seed;
+    for (auto& io : g->inputs) {
+        noise.resize(io.bytes);
+        if (g->tensors[io.tensor].dtype == TAMD_DT_FP32) {           // finite, moderate floats
+            float* f = (float*)noise.data();
+            for (size_t i = 0; i < io.bytes / 4; i++) { lcg = lcg * 1664525u + 1013904223u; f[i] = (float)((int)(lcg >> 20) - 2048) / 1024.f; }
+        } else
+            for (size_t i = 0; i < io.bytes; i++) { lcg = lcg * 1664525u + 1013904223u; noise[i] = (unsigned char)(lcg >> 24); }
+        if (io_slot >= 0) memcpy(io.pinned[io_slot], noise.data(), io.bytes);
+        else HIPCHK(hipMemcpy(io.stage, noise.data(), io.bytes, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+int selfcheck_snapshot(const tamd_graph* g, OutputBytes* dst, int io_slot, const std::vector<SlotSpan>* spans)
+{
+    dst->clear();
+    for (auto& io : g->outputs) {
+        dst->emplace_back(io.bytes);
+        if (io_slot >= 0) { memcpy(dst->back().data(), io.pinned[io_slot], io.bytes); continue; }
+        const void* src = spans ? (const void*)slot_moved(*spans, (uintptr_t)io.stage) : io.stage;
+        HIPCHK(hipMemcpy(dst->back().data(), src, io.bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int selfcheck_same(const OutputBytes& want, const OutputBytes& got, const char* fmt)
+{
+    for (size_t i = 0; i < want.size(); i++)
+        if (want[i] != got[i]) { set_error(fmt, i); return -1; }
+    return 0;
+}
 
 // One direct pass against the eager pass of the same launch list, every graph output compared byte for byte.  Two pseudo-random
 // inputs: eager(A) -> want; eager(B) leaves B's results in every buffer; direct(A) must bring want back -- a pass that writes
 // nothing, or the wrong thing, shows up, and outputs that are prerun constants (PriorBox) are the same in all three.  0: identical.
-void selfcheck_noise(const tamd_graph* g, const IOBind& io, unsigned* lcg_state, std::vector<unsigned char>* noise)
-{
-    unsigned lcg = *lcg_state;
-    noise->resize(io.bytes);
-    if (g->tensors[io.tensor].dtype == TAMD_DT_FP32) {           // finite, moderate floats
-        float* f = (float*)noise->data();
-        for (size_t i = 0; i < io.bytes / 4; i++) { lcg = lcg * 1664525u + 1013904223u; f[i] = (float)((int)(lcg >> 20) - 2048) / 1024.f; }
-    } else
-        for (size_t i = 0; i < io.bytes; i++) { lcg = lcg * 1664525u + 1013904223u; (*noise)[i] = (unsigned char)(lcg >> 24); }
-    *lcg_state = lcg;
-}
-
 int direct_selfcheck(tamd_graph* g)
 {
-    std::vector<std::vector<unsigned char>> want, got;
-    auto fill_inputs = [&](unsigned seed) -> int {
-        std::vector<unsigned char> noise;
-        unsigned lcg = seed;
-        for (auto& io : g->inputs) {
-            selfcheck_noise(g, io, &lcg, &noise);
-            HIPCHK(hipMemcpy(io.stage, noise.data(), io.bytes, hipMemcpyHostToDevice));
-        }
-        return 0;
-    };
-    auto snapshot = [&](std::vector<std::vector<unsigned char>>& dst) -> int {
-        dst.clear();
-        for (auto& io : g->outputs) {
-            dst.emplace_back(io.bytes);
-            HIPCHK(hipMemcpy(dst.back().data(), io.stage, io.bytes, hipMemcpyDeviceToHost));
-        }
-        return 0;
-    };
-    if (fill_inputs(0x5EED1234u) || run_steps(g, g->stream)) return -1;
+    OutputBytes want, got;
+    if (selfcheck_fill_inputs(g, 0x5EED1234u) || run_steps(g, g->stream)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (snapshot(want)) return -1;
-    if (fill_inputs(0x0BADF00Du) || run_steps(g, g->stream)) return -1;
+    if (selfcheck_snapshot(g, &want)) return -1;
+    if (selfcheck_fill_inputs(g, 0x0BADF00Du) || run_steps(g, g->stream)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (fill_inputs(0x5EED1234u)) return -1;
+    if (selfcheck_fill_inputs(g, 0x5EED1234u)) return -1;
     HIPCHK(hipDeviceSynchronize());
     if (direct_submit(g->direct) || direct_wait(g->direct)) { set_error("direct pass failed: %s", direct_last_error()); return -1; }
-    if (snapshot(got)) return -1;
+    if (selfcheck_snapshot(g, &got)) return -1;
     for (auto& io : g->inputs) HIPCHK(hipMemset(io.stage, 0, io.bytes));
     HIPCHK(hipDeviceSynchronize());
-    for (size_t i = 0; i < want.size(); i++)
-        if (want[i] != got[i]) { set_error("the direct pass does not reproduce the eager pass (output %zu differs)", i); return -1; }
-    return 0;
+    return selfcheck_same(want, got, "the direct pass does not reproduce the eager pass (output %zu differs)");
 }
 
 // ---- host-to-host lists: graph outputs stored straight into the pinned host buffers ---------------------------------------------
 // A blocking run_graph is upload kernel -> launch list -> download kernel -> closing packet.  The download kernel copies a few
 // hundred bytes (MobileNet: 1000) that the last compute launch has just written; it costs a launch boundary, a kernel and an
 // HBM round trip for nothing.  In the RECORDED list of an I/O slot every kernel argument that holds an output's device staging
-// address is re-pointed at the slot's pinned host buffer (device-mapped: the download kernel already writes there), and the
+// address is re-pointed at that slot's pinned host buffer (device-mapped: the download kernel already writes there), and the
 // download launch is dropped; the closing packet's system-scope release makes the stores visible to the host as before.  Only
 // outputs nobody else reads on the device qualify (a consumer would otherwise read host memory), and only when at least one
 // argument matched; the patched program must then reproduce the eager list byte for byte (direct_io_selfcheck) or it is rebuilt
-// with its download launches.
-bool io_zero_copy_wanted()
-{
-    const char* e = getenv("TAMD_IO_ZERO_COPY");
-    return !(e && atoi(e) == 0);
-}
-
+// with its download launches.  TAMD_IO_ZERO_COPY=0 keeps them.
 static int patch_pointer(std::vector<LaunchRec>& recs, size_t nrecs, const void* from, const void* to)
 {
     int hits = 0;
@@ -167,12 +169,13 @@ static int patch_pointer(std::vector<LaunchRec>& recs, size_t nrecs, const void*
     return hits;
 }
 
-// recs = the recorded host-to-host list of `slot`: [uploads][in_steps, steps, out_steps][one download launch per output].
+// recs = the recorded host-to-host list of I/O slot `io_slot`: [uploads][in_steps, steps, out_steps][one download launch per output].
 // Returns true when every download launch could be dropped.
-bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot)
+static bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int io_slot)
 {
+    const char* e = getenv("TAMD_IO_ZERO_COPY");
     const size_t nout = g->outputs.size();
-    if (nout == 0 || recs.size() <= nout + g->inputs.size()) return false;
+    if ((e && atoi(e) == 0) || nout == 0 || recs.size() <= nout + g->inputs.size()) return false;
     const size_t body = recs.size() - nout;
     std::vector<LaunchRec> trial(recs.begin(), recs.begin() + body);
     for (auto& io : g->outputs) {
@@ -180,7 +183,7 @@ bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot)
         if (io.stage == t.dptr && count_consumers(g, io.tensor) != 1) return false;      // read again on the device
         if (t.prerun_const) return false;                                                  // written once at prerun, not by the list
         void* dev = nullptr;
-        if (hipHostGetDevicePointer(&dev, slot ? io.pinned2 : io.pinned, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (hipHostGetDevicePointer(&dev, io.pinned[io_slot], 0) != hipSuccess) { (void)hipGetLastError(); return false; }
         if (patch_pointer(trial, body, io.stage, dev) < 1) return false;
     }
     recs.swap(trial);
@@ -188,9 +191,9 @@ bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot)
 }
 
 // The mirror image for graph inputs (TAMD_IO_ZERO_COPY_IN=1; off by default until it measures faster): the first compute launch
-// reads the slot's pinned host buffer itself (device-mapped, uncached on the device side) and the upload launches are dropped.
+// reads the I/O slot's pinned host buffer itself (device-mapped, uncached on the device side) and the upload launches are dropped.
 // recs = [one upload launch per input][the rest]; every later argument that holds an input's staging address is re-pointed.
-bool zero_copy_inputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot)
+static bool zero_copy_inputs(tamd_graph* g, std::vector<LaunchRec>& recs, int io_slot)
 {
     const char* e = exp_env("TAMD_IO_ZERO_COPY_IN");
     const size_t nin = g->inputs.size();
@@ -198,39 +201,52 @@ bool zero_copy_inputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot)
     std::vector<LaunchRec> trial(recs.begin() + nin, recs.end());
     for (auto& io : g->inputs) {
         void* dev = nullptr;
-        if (hipHostGetDevicePointer(&dev, slot ? io.pinned2 : io.pinned, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (hipHostGetDevicePointer(&dev, io.pinned[io_slot], 0) != hipSuccess) { (void)hipGetLastError(); return false; }
         if (patch_pointer(trial, trial.size(), io.stage, dev) < 1) return false;
     }
     recs.swap(trial);
     return true;
 }
 
-// the host-to-host program of `slot` against the eager list of the same slot (upload and download launches included), every
-// pinned output compared byte for byte.  0: identical.
-int direct_io_selfcheck(tamd_graph* g, DirectProgram* pio, int slot)
+// the host-to-host program of I/O slot `io_slot` against the eager list of the same I/O slot (upload and download launches included),
+// every pinned output compared byte for byte.  0: identical.
+static int direct_io_selfcheck(tamd_graph* g, DirectProgram* pio, int io_slot)
 {
-    std::vector<unsigned char> noise;
-    std::vector<std::vector<unsigned char>> want;
-    unsigned lcg = 0xC0FFEE11u + (unsigned)slot;
-    for (auto& io : g->inputs) {
-        selfcheck_noise(g, io, &lcg, &noise);
-        memcpy(slot ? io.pinned2 : io.pinned, noise.data(), io.bytes);
-    }
-    if (run_steps(g, g->stream, slot)) return -1;
+    OutputBytes want, got;
+    if (selfcheck_fill_inputs(g, 0xC0FFEE11u + (unsigned)io_slot, io_slot) || run_steps(g, g->stream, io_slot)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
-    for (auto& io : g->outputs) {
-        unsigned char* pin = (unsigned char*)(slot ? io.pinned2 : io.pinned);
-        want.emplace_back(pin, pin + io.bytes);
-        memset(pin, 0xA5, io.bytes);
-    }
+    if (selfcheck_snapshot(g, &want, io_slot)) return -1;
+    for (auto& io : g->outputs) memset(io.pinned[io_slot], 0xA5, io.bytes);
     HIPCHK(hipDeviceSynchronize());
     unsigned long long b = 0;
     if (direct_submit(pio, true, &b) || direct_wait_burst(pio, b)) { set_error("direct host-to-host pass failed: %s", direct_last_error()); return -1; }
-    for (size_t i = 0; i < g->outputs.size(); i++)
-        if (memcmp(want[i].data(), slot ? g->outputs[i].pinned2 : g->outputs[i].pinned, g->outputs[i].bytes) != 0) {
-            set_error("the direct host-to-host pass does not reproduce the eager list (output %zu differs)", i);
-            return -1;
-        }
+    if (selfcheck_snapshot(g, &got, io_slot)) return -1;
+    return selfcheck_same(want, got, "the direct host-to-host pass does not reproduce the eager list (output %zu differs)");
+}
+
+// the host-to-host list of I/O slot 0 | 1 (upload launch, compute, download launch) on the queue of g->direct: tamd_graph_run and
+// the asynchronous pair
+int build_io_program(tamd_graph* g, int io_slot)
+{
+    std::vector<LaunchRec> recs;
+    if (record_pass(g, io_slot, &recs)) return -1;
+    // outputs straight into the pinned host buffers (no download launch) where the list allows it
+    const std::vector<LaunchRec> with_downloads = recs;
+    bool zc = zero_copy_outputs(g, recs, io_slot);
+    if (zero_copy_inputs(g, recs, io_slot)) zc = true;        // (a failed self-check below falls back to the full list)
+    const char* why = "";
+    DirectProgram* pio = direct_build(g->gpu, g->stream, recs, &why, g->direct);
+    if (pio && direct_io_selfcheck(g, pio, io_slot)) {
+        if (zc) fprintf(stderr, "tengine_amd: zero-copy outputs DISABLED for this graph: %s\n", last_error());
+        direct_destroy(pio);
+        why = last_error();
+        pio = zc ? direct_build(g->gpu, g->stream, with_downloads, &why, g->direct) : nullptr;      // once more with the download launches
+        zc = false;
+        if (pio && direct_io_selfcheck(g, pio, io_slot)) { direct_destroy(pio); pio = nullptr; why = last_error(); }
+    }
+    if (!pio) fprintf(stderr, "tengine_amd: direct dispatch not used for host-to-host runs (slot %d): %s\n", io_slot, why);
+    g->io[io_slot].direct = pio;
+    g->io[io_slot].zero_copy = zc && pio;
     return 0;
 }
 
@@ -250,26 +266,33 @@ int bind_device(tamd_graph* g)
 int direct_drain(tamd_graph* g)
 {
     if (g->direct && g->direct_busy) {
-        // both slots' queues (graph_slots.hip); a queue with nothing open returns at once
+        // both pass slots' queues (graph_slots.hip); a queue with nothing open returns at once
         if (direct_wait(g->direct) || (g->direct1 && direct_wait(g->direct1))) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
         g->direct_busy = false;
     }
-    g->slot_turn = 0;          // slot 0 runs first after every drain: its buffers are the ones everybody reads
+    g->slot_turn = 0;          // pass slot 0 runs first after every drain: its buffers are the ones everybody reads
     return 0;
 }
 
-// the direct path of this graph is unusable (queue fault, a burst that never completed): forget the runs in flight -- their
-// results are lost, the caller has been told -- and go back to the hipGraph executables, which every entry point still has
-void direct_abandon(tamd_graph* g, const char* why)
+// direct_destroy waits for what is still running unless the queue has faulted; a hung burst is bounded by TAMD_DIRECT_TIMEOUT_S
+void direct_teardown(tamd_graph* g)
 {
-    fprintf(stderr, "tengine_amd: direct dispatch abandoned for this graph (%s): hipGraph replay from here on\n", why);
-    g->inflight.erase(std::remove_if(g->inflight.begin(), g->inflight.end(), [](const Inflight& f) { return f.direct; }), g->inflight.end());
-    // direct_destroy waits for what is still running unless the queue has faulted; a hung burst is bounded by TAMD_DIRECT_TIMEOUT_S
-    if (g->direct_io2) { direct_destroy(g->direct_io2); g->direct_io2 = nullptr; }
-    if (g->direct_io) { direct_destroy(g->direct_io); g->direct_io = nullptr; }
+    for (int s = 1; s >= 0; s--)
+        if (g->io[s].direct) { direct_destroy(g->io[s].direct); g->io[s].direct = nullptr; }
     slots_destroy(g);
     if (g->direct) { direct_destroy(g->direct); g->direct = nullptr; }
+}
+
+// the direct path of this graph is unusable (queue fault, a burst that never completed): forget the runs in flight -- their
+// results are lost, the caller is told (the error is set, -1) -- and go back to the hipGraph executables, which every entry point still has
+static int direct_abandon(tamd_graph* g)
+{
+    set_error("direct dispatch: %s", direct_last_error());
+    fprintf(stderr, "tengine_amd: direct dispatch abandoned for this graph (%s): hipGraph replay from here on\n", last_error());
+    g->inflight.erase(std::remove_if(g->inflight.begin(), g->inflight.end(), [](const Inflight& f) { return f.direct; }), g->inflight.end());
+    direct_teardown(g);
     g->direct_busy = false;
+    return -1;
 }
 
 static inline long long now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -279,18 +302,32 @@ static bool close_on_last_packet()
     return !(e && atoi(e) == 0);
 }
 
+// one program as a closed burst: closed by the list's last packet, or by a barrier packet behind it.  *burst: what direct_wait_burst takes
+static int submit_burst(DirectProgram* p, unsigned long long* burst)
+{
+    return close_on_last_packet() ? direct_submit(p, true, burst) : (direct_submit(p) || direct_close(p, burst));
+}
+
+// The graph's HIP stream is drained only when something may be pending on it: what a host-to-host burst reads was either written by
+// the burst itself (the upload launch) or by stream work this library knows about -- unless the caller holds the stream
+static int drain_stream_if_pending(tamd_graph* g)
+{
+    if (g->stream_dirty || g->stream_exposed) { HIPCHK(hipStreamSynchronize(g->stream)); g->stream_dirty = false; }
+    return 0;
+}
+
 // A zero-copy host-to-host run leaves its outputs in the pinned host buffers ONLY (the launch that would have written the device
 // staging buffer was re-pointed): whoever reads the device copy next -- tamd_graph_output_device (the RCCL gather),
-// tamd_graph_read_tensor of a 1x1-map output -- gets it refreshed from the pinned slot first.
+// tamd_graph_read_tensor of a 1x1-map output -- gets it refreshed from the pinned buffers of that I/O slot first.
 int stage_from_pinned(tamd_graph* g)
 {
-    if (!g->out_fresh_in) return 0;
+    if (g->out_fresh_in < 0) return 0;
     if (!g->inflight.empty()) { set_error("the outputs of the last host-to-host run live in a pinned buffer that a run in flight may overwrite: tamd_graph_wait first"); return -1; }
     if (direct_drain(g)) return -1;
     for (auto& io : g->outputs)
-        HIPCHK(hipMemcpyAsync(io.stage, g->out_fresh_in == 2 ? io.pinned2 : io.pinned, io.bytes, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipMemcpyAsync(io.stage, io.pinned[g->out_fresh_in], io.bytes, hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
-    g->out_fresh_in = 0;
+    g->out_fresh_in = -1;
     return 0;
 }
 
@@ -310,8 +347,8 @@ int tamd_graph_upload_inputs(tamd_graph* g)
     if (!g->prepared) { set_error("graph not prepared"); return -1; }
     for (auto& io : g->inputs) {
         if (!io.host_in) { set_error("input buffer not set"); return -1; }
-        memcpy(io.pinned, io.host_in, io.bytes);
-        HIPCHK(hipMemcpyAsync(io.stage, io.pinned, io.bytes, hipMemcpyHostToDevice, g->stream));
+        memcpy(io.pinned[0], io.host_in, io.bytes);
+        HIPCHK(hipMemcpyAsync(io.stage, io.pinned[0], io.bytes, hipMemcpyHostToDevice, g->stream));
     }
     g->stream_dirty = true;
     return 0;
@@ -323,7 +360,7 @@ int tamd_graph_launch(tamd_graph* g)
     if (bind_device(g)) return -1;
     if (!g->prepared) { set_error("graph not prepared"); return -1; }
     if (g->half[0]) return pair_both(g, tamd_graph_launch);
-    g->out_fresh_in = 0;                       // the pass writes the staging buffers itself
+    g->out_fresh_in = -1;                      // the pass writes the staging buffers itself
     if (g->direct) {
         // the pass reads what the stream wrote (uploaded inputs): drain it before the first packet of a burst
         if (!g->direct_busy) { HIPCHK(hipStreamSynchronize(g->stream)); g->stream_dirty = false; }
@@ -360,7 +397,7 @@ int tamd_graph_direct_timestamps(tamd_graph* g, int passes, double* dur_us, doub
     if (direct_drain(g)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
     g->stream_dirty = false;
-    g->out_fresh_in = 0;                       // the passes write the staging buffers themselves
+    g->out_fresh_in = -1;                      // the passes write the staging buffers themselves
     const int n = direct_timestamps(g->direct, passes, dur_us, gap_us);
     if (n < 0) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
     return n;
@@ -375,7 +412,7 @@ int tamd_graph_slot_timestamps(tamd_graph* g, int passes, double* start_us, doub
     if (direct_drain(g)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
     g->stream_dirty = false;
-    g->out_fresh_in = 0;                       // the passes write the staging buffers themselves
+    g->out_fresh_in = -1;                      // the passes write the staging buffers themselves
     return slots_timestamps(g, passes, start_us, end_us, max_stamps);
 }
 double tamd_graph_prerun_ms(const tamd_graph* g) { return g ? g->prerun_ms : 0.0; }
@@ -386,9 +423,9 @@ int tamd_graph_sync(tamd_graph* g)
     if (bind_device(g)) return -1;
     if (g->half[0]) return pair_both(g, tamd_graph_sync);
     if (direct_drain(g)) return -1;
-    // asynchronous runs that were submitted and not collected yet are device work too (their outputs stay in the pinned slots
-    // until tamd_graph_wait delivers them)
-    if (g->direct_io && !g->inflight.empty() && direct_wait_all(g->direct_io)) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
+    // asynchronous runs that were submitted and not collected yet are device work too (their outputs stay in the pinned buffers of
+    // their I/O slots until tamd_graph_wait delivers them; both I/O slots' programs share one queue)
+    if (g->io[0].direct && !g->inflight.empty() && direct_wait_all(g->io[0].direct)) { set_error("direct dispatch: %s", direct_last_error()); return -1; }
     HIPCHK(hipStreamSynchronize(g->stream));
     g->stream_dirty = false;
     return 0;
@@ -401,15 +438,15 @@ int tamd_graph_download_outputs(tamd_graph* g)
     if (g->half[0]) return pair_both(g, tamd_graph_download_outputs);
     if (!g->inflight.empty()) { set_error("tamd_graph_download_outputs while asynchronous runs are in flight (they own the pinned buffers): collect them with tamd_graph_wait first"); return -1; }
     if (direct_drain(g)) return -1;
-    if (g->out_fresh_in) {                     // the last pass was a zero-copy host-to-host run: its pinned slot IS the newest copy
+    if (g->out_fresh_in >= 0) {                // the last pass was a zero-copy host-to-host run: its I/O slot's pinned buffers ARE the newest copy
         for (auto& io : g->outputs)
-            if (io.host_out) memcpy(io.host_out, g->out_fresh_in == 2 ? io.pinned2 : io.pinned, io.bytes);
+            if (io.host_out) memcpy(io.host_out, io.pinned[g->out_fresh_in], io.bytes);
         return 0;
     }
-    for (auto& io : g->outputs) HIPCHK(hipMemcpyAsync(io.pinned, io.stage, io.bytes, hipMemcpyDeviceToHost, g->stream));
+    for (auto& io : g->outputs) HIPCHK(hipMemcpyAsync(io.pinned[0], io.stage, io.bytes, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     for (auto& io : g->outputs)
-        if (io.host_out) memcpy(io.host_out, io.pinned, io.bytes);
+        if (io.host_out) memcpy(io.host_out, io.pinned[0], io.bytes);
     return 0;
 }
 
@@ -426,33 +463,28 @@ int tamd_graph_run(tamd_graph* g)
     if (trace) t[0] = now_ns();
     for (auto& io : g->inputs) {
         if (!io.host_in) { set_error("input buffer not set"); return -1; }
-        memcpy(io.pinned, io.host_in, io.bytes);
+        memcpy(io.pinned[0], io.host_in, io.bytes);
     }
     if (trace) t[1] = now_ns();
-    if (g->direct_io) {
+    IoSlot& s = g->io[0];                      // a blocking run is I/O slot 0
+    if (s.direct) {
         // the same list as AQL packets: system-scope acquire in front; the burst is closed by the list's last packet (or a barrier
-        // packet behind it).  The graph's HIP stream is drained only when something may be pending on it: what the pass reads was
-        // either written by the pass itself (the upload launch) or by stream work this library knows about
-        if (g->stream_dirty || g->stream_exposed) { HIPCHK(hipStreamSynchronize(g->stream)); g->stream_dirty = false; }
+        // packet behind it)
+        if (drain_stream_if_pending(g)) return -1;
         if (trace) t[2] = now_ns();
         unsigned long long b = 0;
-        int rc = close_on_last_packet() ? direct_submit(g->direct_io, true, &b) : (direct_submit(g->direct_io) || direct_close(g->direct_io, &b));
+        const int rc = submit_burst(s.direct, &b);
         if (trace) t[3] = now_ns();
-        if (!rc) rc = direct_wait_burst(g->direct_io, b);
-        if (rc) {
-            set_error("direct dispatch: %s", direct_last_error());
-            direct_abandon(g, last_error());
-            return -1;
-        }
+        if (rc || direct_wait_burst(s.direct, b)) return direct_abandon(g);
     } else {
         if (trace) t[2] = t[3] = now_ns();
         if (launch_io(g, 0)) return -1;
         HIPCHK(hipStreamSynchronize(g->stream));
     }
     if (trace) t[4] = now_ns();
-    g->out_fresh_in = (g->direct_io && g->io_zero_copy) ? 1 : 0;
+    g->out_fresh_in = (s.direct && s.zero_copy) ? 0 : -1;
     for (auto& io : g->outputs)
-        if (io.host_out) memcpy(io.host_out, io.pinned, io.bytes);
+        if (io.host_out) memcpy(io.host_out, io.pinned[0], io.bytes);
     if (trace) {
         t[5] = now_ns();
         for (int i = 0; i < 5; i++) g->h2h_ns[i] += t[i + 1] - t[i];
@@ -474,38 +506,32 @@ int tamd_graph_run_async(tamd_graph* g)
     if (g->half[0]) return pair_run_async(g);
     if (g->inflight.size() >= 2) { set_error("two runs are already in flight: call tamd_graph_wait first"); return -1; }
     if (direct_drain(g)) return -1;
-    const int slot = g->next_slot;
+    Inflight f;
+    f.io_slot = g->next_io_slot;
+    IoSlot& s = g->io[f.io_slot];
     for (auto& io : g->inputs) {
         if (!io.host_in) { set_error("input buffer not set"); return -1; }
-        memcpy(slot ? io.pinned2 : io.pinned, io.host_in, io.bytes);
+        memcpy(io.pinned[f.io_slot], io.host_in, io.bytes);
     }
-    Inflight f;
-    f.slot = slot;
     for (auto& io : g->outputs) f.host_out.push_back(io.host_out);
-    if (g->direct_io && g->direct_io2) {
-        // the run is ONE burst on the graph's own HSA queue: the slot's host-to-host list (system-scope acquire in front: the
+    if (g->io[0].direct && g->io[1].direct) {
+        // the run is ONE burst on the graph's own HSA queue: the I/O slot's host-to-host list (system-scope acquire in front: the
         // pinned input was just written by the host), closed by a barrier packet that releases at system scope and counts the
         // queue's completion signal down.  The second run's packets queue behind the first one's closing packet (barrier bit on
         // every packet): the device goes from run k's download straight into run k+1's upload, the host is never in between.
-        DirectProgram* p = slot ? g->direct_io2 : g->direct_io;
-        if (g->inflight.empty() && (g->stream_dirty || g->stream_exposed)) { HIPCHK(hipStreamSynchronize(g->stream)); g->stream_dirty = false; }
-        const int rc = close_on_last_packet() ? direct_submit(p, true, &f.burst) : (direct_submit(p) || direct_close(p, &f.burst));
-        if (rc) {
-            // packets may be in the ring without a closing packet: the queue cannot be trusted any more
-            set_error("direct dispatch: %s", direct_last_error());
-            direct_abandon(g, last_error());
-            return -1;
-        }
+        if (g->inflight.empty() && drain_stream_if_pending(g)) return -1;
+        // (a failed submit: packets may be in the ring without a closing packet, the queue cannot be trusted any more)
+        if (submit_burst(s.direct, &f.burst)) return direct_abandon(g);
         f.direct = true;
     } else {
-        if (!g->slot_done[slot]) HIPCHK(hipEventCreateWithFlags(&g->slot_done[slot], hipEventDisableTiming));
+        if (!s.done) HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         g->stream_dirty = true;
-        if (launch_io(g, slot)) return -1;
-        f.done = g->slot_done[slot];
+        if (launch_io(g, f.io_slot)) return -1;
+        f.done = s.done;
         HIPCHK(hipEventRecord(f.done, g->stream));
     }
     g->inflight.push_back(f);
-    g->next_slot ^= 1;
+    g->next_io_slot ^= 1;
     return 0;
 }
 
@@ -518,18 +544,14 @@ int tamd_graph_wait(tamd_graph* g)
     if (bind_device(g)) return -1;
     const Inflight f = g->inflight.front();
     if (f.direct) {
-        if (direct_wait_burst(g->direct_io, f.burst)) {
-            // the run is lost; so is everything queued behind it.  Drop the bookkeeping (the graph would otherwise refuse every
-            // entry point with "runs in flight" until it is destroyed) and leave the direct path
-            set_error("direct dispatch: %s", direct_last_error());
-            direct_abandon(g, last_error());
-            return -1;
-        }
+        // a failed wait: the run is lost; so is everything queued behind it.  Drop the bookkeeping (the graph would otherwise refuse
+        // every entry point with "runs in flight" until it is destroyed) and leave the direct path
+        if (direct_wait_burst(g->io[0].direct, f.burst)) return direct_abandon(g);      // (both I/O slots' programs share one queue)
     } else
         HIPCHK(hipEventSynchronize(f.done));
     for (size_t i = 0; i < g->outputs.size(); i++)
-        if (f.host_out[i]) memcpy(f.host_out[i], f.slot ? g->outputs[i].pinned2 : g->outputs[i].pinned, g->outputs[i].bytes);
-    g->out_fresh_in = (f.direct && (f.slot ? g->io_zero_copy2 : g->io_zero_copy)) ? 1 + f.slot : 0;
+        if (f.host_out[i]) memcpy(f.host_out[i], g->outputs[i].pinned[f.io_slot], g->outputs[i].bytes);
+    g->out_fresh_in = (f.direct && g->io[f.io_slot].zero_copy) ? f.io_slot : -1;
     g->inflight.erase(g->inflight.begin());
     return 0;
 }
@@ -542,7 +564,7 @@ int tamd_graph_output_device(tamd_graph* g, int idx, void** dptr, size_t* bytes)
     TAMD_ONE_THREAD(g);
     if (idx < 0 || idx >= (int)g->outputs.size() || !g->prepared) return -1;
     if (g->half[0]) return pair_output_device(g, idx, dptr, bytes);
-    if (g->out_fresh_in && (bind_device(g) || stage_from_pinned(g))) return -1;
+    if (g->out_fresh_in >= 0 && (bind_device(g) || stage_from_pinned(g))) return -1;
     *dptr = g->outputs[idx].stage;
     *bytes = g->outputs[idx].bytes;
     return 0;

@@ -37,16 +37,24 @@ void plan_cache_flush();                     // plan_cache.hip
 
 // graph_exec.hip
 int run_steps(tamd_graph* g, hipStream_t s, int io_slot = -1);
-int launch_io(tamd_graph* g, int slot);
+// one eager pass of run_steps for I/O slot `io_slot` (-1: the launch list alone) with the launch recorder on (launch_rec.h), into *recs
+int record_pass(tamd_graph* g, int io_slot, std::vector<LaunchRec>* recs);
 int direct_selfcheck(tamd_graph* g);
-void selfcheck_noise(const tamd_graph* g, const IOBind& io, unsigned* lcg_state, std::vector<unsigned char>* noise);   // pseudo-random bytes (finite floats) for one graph input
-bool io_zero_copy_wanted();
-bool zero_copy_outputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot);
-bool zero_copy_inputs(tamd_graph* g, std::vector<LaunchRec>& recs, int slot);
-int direct_io_selfcheck(tamd_graph* g, DirectProgram* pio, int slot);
+// what the self-checks share (direct_selfcheck, direct_io_selfcheck; slots_selfcheck of graph_slots.hip).  Seeded pseudo-random bytes
+// (finite floats) into every graph input: its device staging buffer, or with io_slot >= 0 that I/O slot's pinned buffer
+int selfcheck_fill_inputs(tamd_graph* g, unsigned seed, int io_slot = -1);
+// a copy of every graph output: from its staging buffer, from where the pass-slot span map `spans` moved that buffer, or with
+// io_slot >= 0 from that I/O slot's pinned buffer
+typedef std::vector<std::vector<unsigned char>> OutputBytes;
+int selfcheck_snapshot(const tamd_graph* g, OutputBytes* dst, int io_slot = -1, const std::vector<SlotSpan>* spans = nullptr);
+// -1 and the error `fmt` (which takes the output's index as its one %zu) at the first output whose bytes differ
+int selfcheck_same(const OutputBytes& want, const OutputBytes& got, const char* fmt);
+// g->io[io_slot].direct / .zero_copy: the host-to-host list of that I/O slot as a program on g->direct's queue, outputs stored straight
+// into the pinned buffers where the list allows it and the program proves itself.  -1: a HIP error; no program is no error
+int build_io_program(tamd_graph* g, int io_slot);
 int bind_device(tamd_graph* g);
 int direct_drain(tamd_graph* g);
-void direct_abandon(tamd_graph* g, const char* why);
+void direct_teardown(tamd_graph* g);         // the I/O slots' programs, the second pass slot, g->direct: waits for what still runs (direct.cc)
 int stage_from_pinned(tamd_graph* g);
 
 // graph_slots.hip: two passes in flight on two HSA queues behind one handle (tamd_options.split_batch)

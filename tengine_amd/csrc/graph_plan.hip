@@ -229,7 +229,6 @@ static int plan_input_staging(tamd_graph* g)
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esize(t.dtype);
         if (dev_alloc(g, &io.stage, io.bytes + 64, true)) return -1;     // slack: the first-layer kernel over-reads the last row by < 8 bytes
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
         bool direct = (t.dims.size() == 4 && t.c <= 4 && count_consumers(g, io.tensor) == 1);
         if (direct) {
             for (auto& n : g->nodes)
@@ -836,7 +835,6 @@ static int plan_outputs(tamd_graph* g)
     for (auto& io : g->outputs) {
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esize(t.dtype);
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
         if (t.nchw_raw) { io.stage = t.dptr; continue; }                 // dense tensors are the reference's element order already
         if (t.h * t.w == 1 && t.cs == t.c && t.c_off == 0) { io.stage = t.dptr; continue; }
         if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;

@@ -68,7 +68,6 @@ int plan_nchw_buffers(tamd_graph* g, size_t esz, const std::function<bool(const 
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esz;
         if (dev_alloc(g, &io.stage, io.bytes, true)) return -1;
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
         t.dptr = io.stage;
     }
     std::vector<int> view_of(g->tensors.size(), -1), view_off(g->tensors.size(), 0);
@@ -112,7 +111,6 @@ int plan_nchw_outputs(tamd_graph* g, size_t esz)
     for (auto& io : g->outputs) {
         HTensor& t = g->tensors[io.tensor];
         io.bytes = t.elems() * esz;
-        HIPCHK(hipHostMalloc(&io.pinned, io.bytes, hipHostMallocDefault));
         io.stage = t.dptr;
     }
     return 0;

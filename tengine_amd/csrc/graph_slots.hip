@@ -40,57 +40,32 @@ void say(const char* why)
 
 void add_access(std::vector<SlotRange>& r, const Access& a) { r.push_back(slot_range_of(a)); }
 
-int snapshot(const tamd_graph* g, const std::vector<SlotSpan>* spans, std::vector<std::vector<unsigned char>>& dst)
-{
-    dst.clear();
-    for (auto& io : g->outputs) {
-        dst.emplace_back(io.bytes);
-        const void* src = spans ? (const void*)slot_moved(*spans, (uintptr_t)io.stage) : io.stage;
-        HIPCHK(hipMemcpy(dst.back().data(), src, io.bytes, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-int fill_inputs(tamd_graph* g, unsigned seed)
-{
-    std::vector<unsigned char> noise;
-    unsigned lcg = seed;
-    for (auto& io : g->inputs) {
-        selfcheck_noise(g, io, &lcg, &noise);
-        HIPCHK(hipMemcpy(io.stage, noise.data(), io.bytes, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
 // The proof, in the scheme of direct_selfcheck.  (a) slot 1 ALONE reproduces the eager pass of input A byte for byte in its own output
 // copies while slot 0's buffers hold input B's results -- a read pointer that was not moved shows as B's bytes, a write pointer that
 // was not moved as A's bytes in slot 0.  (b) one burst of 8 alternating passes leaves A's results in both slots' outputs.
 int slots_selfcheck(tamd_graph* g)
 {
-    std::vector<std::vector<unsigned char>> want, other, got;
-    if (fill_inputs(g, 0x51075A11u) || run_steps(g, g->stream)) return -1;
+    OutputBytes want, other, got;
+    if (selfcheck_fill_inputs(g, 0x51075A11u) || run_steps(g, g->stream)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (snapshot(g, nullptr, want)) return -1;
-    if (fill_inputs(g, 0x0DDBA11Au) || run_steps(g, g->stream)) return -1;
+    if (selfcheck_snapshot(g, &want)) return -1;
+    if (selfcheck_fill_inputs(g, 0x0DDBA11Au) || run_steps(g, g->stream)) return -1;
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (snapshot(g, nullptr, other)) return -1;
-    if (fill_inputs(g, 0x51075A11u)) return -1;
+    if (selfcheck_snapshot(g, &other)) return -1;
+    if (selfcheck_fill_inputs(g, 0x51075A11u)) return -1;
     HIPCHK(hipDeviceSynchronize());
     if (direct_submit(g->direct1) || direct_wait(g->direct1)) { set_error("the pass of slot 1 failed: %s", direct_last_error()); return -1; }
-    if (snapshot(g, &g->slot_spans, got)) return -1;
-    for (size_t i = 0; i < want.size(); i++)
-        if (want[i] != got[i]) { set_error("slot 1 alone does not reproduce the eager pass (output %zu differs)", i); return -1; }
-    if (snapshot(g, nullptr, got)) return -1;
-    for (size_t i = 0; i < other.size(); i++)
-        if (other[i] != got[i]) { set_error("the pass of slot 1 changed slot 0's output %zu", i); return -1; }
+    if (selfcheck_snapshot(g, &got, -1, &g->slot_spans)) return -1;
+    if (selfcheck_same(want, got, "slot 1 alone does not reproduce the eager pass (output %zu differs)")) return -1;
+    if (selfcheck_snapshot(g, &got)) return -1;
+    if (selfcheck_same(other, got, "the pass of slot 1 changed slot 0's output %zu")) return -1;
     for (int k = 0; k < 8; k++)
         if (direct_submit((k & 1) ? g->direct1 : g->direct)) { set_error("the alternating burst failed: %s", direct_last_error()); return -1; }
     if (direct_wait(g->direct) || direct_wait(g->direct1)) { set_error("the alternating burst failed: %s", direct_last_error()); return -1; }
-    for (int slot = 0; slot < 2; slot++) {
-        if (snapshot(g, slot ? &g->slot_spans : nullptr, got)) return -1;
-        for (size_t i = 0; i < want.size(); i++)
-            if (want[i] != got[i]) { set_error("a burst of alternating passes leaves other bytes in slot %d (output %zu differs)", slot, i); return -1; }
-    }
+    if (selfcheck_snapshot(g, &got)) return -1;
+    if (selfcheck_same(want, got, "a burst of alternating passes leaves other bytes in slot 0 (output %zu differs)")) return -1;
+    if (selfcheck_snapshot(g, &got, -1, &g->slot_spans)) return -1;
+    if (selfcheck_same(want, got, "a burst of alternating passes leaves other bytes in slot 1 (output %zu differs)")) return -1;
     for (auto& io : g->inputs) HIPCHK(hipMemset(io.stage, 0, io.bytes));
     HIPCHK(hipDeviceSynchronize());
     return 0;

@@ -182,13 +182,18 @@ def test_device_copy_of_the_outputs_after_a_zero_copy_run(name, dtype, batch):
     capi.lib()
     import torch  # noqa: F401
     hip = hip_runtime_of_the_library()
-    for i, want in enumerate(got):
-        p, n = gr.output_device(i)
-        assert n == want.nbytes
-        host = np.empty_like(want)
-        assert hip.hipMemcpy(host.ctypes.data, p, n, 2) == 0      # hipMemcpyDeviceToHost
-        assert np.array_equal(host, want), "output %d: the device copy is not the last run's" % i
-    # the asynchronous pair: the newest run decides
+
+    def device_copy_is(wants):
+        for i, want in enumerate(wants):
+            p, n = gr.output_device(i)
+            assert n == want.nbytes
+            host = np.empty_like(want)
+            assert hip.hipMemcpy(host.ctypes.data, p, n, 2) == 0      # hipMemcpyDeviceToHost
+            assert np.array_equal(host, want), "output %d: the device copy is not the last run's" % i
+
+    device_copy_is(got)
+    # the asynchronous pair: the newest run decides.  It sat in I/O slot 1 (x1's run in I/O slot 0), and both the host copy and the
+    # device copy are refreshed from THAT slot's pinned buffers
     gr.set_input(x1)
     gr.run_async()
     gr.set_input(x2)
@@ -197,6 +202,12 @@ def test_device_copy_of_the_outputs_after_a_zero_copy_run(name, dtype, batch):
     gr.wait()
     for a, c in zip(got, gr.download()):
         assert np.array_equal(a, c)
+    device_copy_is(got)
+    # ... and one more asynchronous run is in I/O slot 0 again
+    gr.set_input(x1)
+    gr.run_async()
+    gr.wait()
+    device_copy_is(first)
     gr.close()
 
 
