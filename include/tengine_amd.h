@@ -99,6 +99,13 @@ enum {
      * output has the input's dims.  The caffe, mxnet and tf forms, int8 graphs (no kernel in the reference) and fp32 graphs stay on
      * the CPU device */
     TAMD_OP_SLICE = 26,
+    /* every ONNX Transpose -- the Detect head of the YOLOv5 family ((0,1,3,4,2) behind a Reshape), torch's channel shuffle ((0,2,1,3,4)),
+     * the SSD head permute of an ONNX export, pixel shuffle (6-D) --, int8 / uint8 graphs: param tamd_transpose_param.  Rank 2 .. 6, the
+     * order a permutation of 0 .. rank - 1 (transpose_ref.c:436-473 has one loop nest per rank and nothing for any other).  The reference
+     * dequantises, moves floats and requantises EVERY element, the identity order included, so a byte of the output is one byte of the
+     * input through tamd_transpose_table (int8 saturates at +-127: -128 never comes out).  fp32 graphs keep the node on the CPU device */
+    /* 27: reserved, never supported (like 21 and 24: tests/test_slice_cpu.py holds the code to that answer) */
+    TAMD_OP_TRANSPOSE = 28,
     TAMD_OP_NUM
 };
 
@@ -150,6 +157,9 @@ typedef struct tamd_slice_param {
     int iscaffe, ismxnet, isonnx;
     int slice_point_num, begin_num, size_num;
 } tamd_slice_param;
+/* transpose_param.h: the tr_shape vector inline.  dim_num: its length as the file stores it (any value: a length the device does not
+ * run is refused by name; only the first 8 entries are carried); out.dims[i] = in.dims[order[i]] (transpose.c:35-54) */
+typedef struct tamd_transpose_param { int dim_num; int order[8]; } tamd_transpose_param;
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */
@@ -252,7 +262,7 @@ TAMD_API const char* tamd_version(void);
 /* 1 if (op, dtype) can run on the device -- what allocator.describe publishes */
 TAMD_API int tamd_op_supported(int op, int dtype);
 /* 1 if this node with these parameters and tensors (descriptors only; the one const payload read, where it is given, is a PReLU's
- * slope: a value that widens to inf or NaN is refused; a Slice needs the scales and zero points of both tensors, for its byte map) is one the device
+ * slope: a value that widens to inf or NaN is refused; a Slice and a Transpose need the scales and zero points of both tensors, for their byte maps) is one the device
  * compiles; 0 -> leave it to the CPU device.  Replaces the per-op parameter tests a backend makes while it walks a
  * subgraph (source/device/cuda/cuda_executor.cc:72-134 fails Build() instead; tensorrt: trt_limit.hpp) */
 TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_desc* inputs, int input_num,
@@ -286,6 +296,13 @@ TAMD_API int tamd_split_table(float in_scale, int in_zp, float out_scale, int ou
  * the rounding the double round() (slice_ref.c:488-505).  0, or -1 when a scale is not finite and positive or one of the 256 values
  * before the clamp is not finite or lies outside int: the reference's conversion is undefined there and the node is refused */
 TAMD_API int tamd_slice_table(float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
+/* the byte map of a Transpose between tensors of these quantisation parameters (csrc/transpose_tables.cc; no GPU needed), dtype
+ * TAMD_DT_INT8 | TAMD_DT_UINT8: table[raw input byte] = the raw output byte (int8 in two's complement) --
+ * round(((float)q - (float)in_zp) * in_scale / out_scale + (float)out_zp), every step a float operation of its own, the rounding the
+ * double round(), clamped to -127 .. 127 | 0 .. 255 (transpose_ref.c:290, :317-322 | :348, :375-380).  0, or -1 for another dtype and
+ * when one of the 256 values before the clamp is not finite or lies outside int: the reference's conversion is undefined there and
+ * the node is refused */
+TAMD_API int tamd_transpose_table(int dtype, float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
 /* the host truth of a quantised PReLU node (csrc/prelu_tables.cc; no GPU needed).
  * tamd_prelu_slope: the float the reference makes of one fp16 slope (bit pattern), as its fp16_to_fp32 (source/utility/float.c) does
  * on x86: normal halves with a non-zero fraction and infinities as IEEE; a normal half whose fraction is zero -- every exact power of

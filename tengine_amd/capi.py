@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_prelu_slope", "tamd_prelu_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -94,6 +94,7 @@ def lib():
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
         L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_slice_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        L.tamd_transpose_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_prelu_slope.argtypes = [C.c_ushort]
         L.tamd_prelu_slope.restype = C.c_float
         L.tamd_prelu_table.argtypes = [ci, C.c_ushort, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
@@ -118,6 +119,22 @@ def slice_table(in_scale, in_zp, out_scale, out_zp):
     tab = (C.c_ubyte * 256)()
     rc = lib().tamd_slice_table(in_scale, in_zp, out_scale, out_zp, tab)
     return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
+OP_TRANSPOSE = 28        # (27: reserved, like 21 and 24)
+
+
+class TransposeParam(C.Structure):    # tamd_transpose_param
+    _fields_ = [("dim_num", C.c_int), ("order", C.c_int * 8)]
+
+
+def transpose_table(dtype, in_scale, in_zp, out_scale, out_zp):
+    """tamd_transpose_table(): the 256 output bytes of a Transpose (dtype 2: int8, 3: uint8) between tensors of these quantisation
+    parameters, indexed by the raw input byte; the dtype's numpy type (int8: two's complement), so that table[x.view(np.uint8)] are the
+    output's values.  None where the reference's conversion to int is undefined.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_transpose_table(dtype, in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy().view(np.int8 if dtype == 2 else np.uint8)
+
+
 SPLIT_MAX = 8
 
 

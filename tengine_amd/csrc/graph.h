@@ -54,6 +54,7 @@ union NodeParam {
     tamd_split_param split;
     tamd_shufflechannel_param shuffle;
     tamd_slice_param slice;
+    tamd_transpose_param transpose;
 };
 
 struct HNode {
@@ -326,6 +327,13 @@ int slice_chain_next(const tamd_graph* g, size_t ni);
 // a Slice node of a uint8 (NCHW) graph as ONE slice_u8 launch (slice.hip); with next >= 0 that Slice too: boxes and byte maps
 // composed, the tensor between them fused away
 int plan_slice_u8(tamd_graph* g, HNode& n, int next, std::vector<Step>* out);
+// transpose_refusal (node_rules.h) asked of a node of this graph: infer_shapes (check_out false: the output's dims are not made yet),
+// validate_graph and plan_transpose.  *geom / table[256] (either may be null): the canonical geometry for a dense input and the byte map
+const char* transpose_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, TransposeGeom* geom, unsigned char* table);
+// the strides under which `dims` index the convolution-stack NHWC buffer of s, where every axis factors one of s's N, C, H * W ranges
+bool nhwc_view_strides(const HTensor& s, const std::vector<int>& dims, long* strides);
+// a Transpose node of an int8 or uint8 graph as ONE launch (transpose.hip); view_src >= 0: read through the Reshape in front of it
+int plan_transpose(tamd_graph* g, HNode& n, int view_src, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
 // same-shape form, else which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1)
 const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated);

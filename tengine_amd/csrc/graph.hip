@@ -82,6 +82,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_INTERP) return interp_on_device(dtype);      // nearest, int8 / uint8 (which modes, sizes and ranks: tamd_node_supported)
     if (op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL) return chanmap_on_device(dtype);      // byte movers, int8 / uint8 (which forms: tamd_node_supported)
     if (op == TAMD_OP_SLICE) return slice_on_device(dtype);        // the onnx form, uint8 (which forms and extents: tamd_node_supported)
+    if (op == TAMD_OP_TRANSPOSE) return transpose_on_device(dtype);      // int8 / uint8 (which ranks and orders: tamd_node_supported)
     if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
@@ -228,6 +229,14 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
                              out[0].quant_num == 1 && out[0].zero_points ? out[0].zero_points[0] : 0, out[0].dim_num, out[0].dims, nullptr, nullptr)
                == nullptr;
     }
+    case TAMD_OP_TRANSPOSE: {
+        if (n_in < 1 || !in) return 0;
+        return transpose_refusal((const tamd_transpose_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                                 in[0].quant_num == 1 && in[0].scales ? in[0].scales[0] : 0.f, in[0].quant_num == 1 && in[0].zero_points ? in[0].zero_points[0] : 0,
+                                 (size_t)out[0].quant_num, out[0].quant_num == 1 && out[0].scales ? out[0].scales[0] : 0.f,
+                                 out[0].quant_num == 1 && out[0].zero_points ? out[0].zero_points[0] : 0, out[0].dim_num, out[0].dims, nullptr, nullptr)
+               == nullptr;
+    }
     case TAMD_OP_PRELU: {
         if (n_in < 2 || !in) return 0;
         if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
@@ -299,6 +308,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_SPLIT: n.p.split = *(const tamd_split_param*)d->param; break;
         case TAMD_OP_SHUFFLECHANNEL: n.p.shuffle = *(const tamd_shufflechannel_param*)d->param; break;
         case TAMD_OP_SLICE: n.p.slice = *(const tamd_slice_param*)d->param; break;
+        case TAMD_OP_TRANSPOSE: n.p.transpose = *(const tamd_transpose_param*)d->param; break;
         default: break;
         }
     }

@@ -43,6 +43,8 @@ static bool ops_allow_split(const tamd_graph* g)
         case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
         case TAMD_OP_ELTWISE: case TAMD_OP_DROPOUT: case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH:
             break;
+        case TAMD_OP_TRANSPOSE: return false;              // order[0] != 0 moves the batch axis: the images are not independent (and the Reshapes
+                                                           // around every Transpose of the supported graphs are not on this list either)
         case TAMD_OP_CONCAT: if (n.p.concat.axis < 1) return false; break;
         case TAMD_OP_SOFTMAX: if (n.p.softmax.axis < 1) return false; break;
         default: return false;

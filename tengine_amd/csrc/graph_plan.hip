@@ -55,6 +55,8 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
             }
             break;
         case TAMD_OP_SOFTMAX: if (L.dense[n.in[0]]) L.dense[yo] = 1; break;
+        // the result of a Transpose is dense, whatever it reads: a dense tensor, or a convolution-stack tensor where it lies (plan_transpose)
+        case TAMD_OP_TRANSPOSE: L.dense[yo] = 1; break;
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: if (L.dense[n.in[0]]) L.dense[yo] = 1; break;       // a byte map keeps the element order it finds
         case TAMD_OP_CONCAT: {
             HTensor& y = g->tensors[yo];
@@ -74,11 +76,31 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
                 }
         }
     }
+    // Reshape -> Transpose of a convolution-stack tensor as ONE launch and no reshape_i8 copy: the Reshape's only reader is the Transpose,
+    // it is no graph output, and every axis of the reshaped tensor factors exactly one of the source's N, C, H * W index ranges
+    // (nhwc_view_strides) -- the Transpose then reads the source's buffer under the strides that follow from (H * W * cs, 1, cs).  A
+    // Reshape that mixes C with H or W keeps its copy.  TAMD_PIN=transpose_view=0: the copy always (A/B runs; the bytes are the same)
+    std::vector<char> viewed(NT, 0);
+    for (size_t ti = 0; ti < g->nodes.size() && tamd_pin_int("transpose_view", 1); ti++) {
+        const HNode& t = g->nodes[ti];
+        if (t.op != TAMD_OP_TRANSPOSE || t.in.empty()) continue;
+        const int mid = t.in[0];
+        if (count_consumers(g, mid) != 1 || L.alias_of[mid] >= 0) continue;                 // (a graph output counts as a consumer)
+        for (size_t ri = 0; ri < ti; ri++) {
+            const HNode& r = g->nodes[ri];
+            if (r.op != TAMD_OP_RESHAPE || r.out.empty() || r.out[0] != mid || L.dense[r.in[0]] || g->tensors[r.in[0]].ttype == TAMD_TT_CONST) continue;
+            HTensor s = g->tensors[r.in[0]];
+            long strides[8];
+            s.cs = rup(s.c, 16);                                                            // (any padding: only the factoring is asked here)
+            if (!nhwc_view_strides(s, g->tensors[mid].dims, strides)) continue;
+            L.tview[ti] = (int)ri + 1; L.fused[ri] = 1; viewed[mid] = 1;
+        }
+    }
     // who needs the bytes of a dense tensor in memory: everything but the flat Concat of a lazily permuted tensor (and its views)
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         const HNode& n = g->nodes[ni];
         for (int i : n.in) {
-            if (g->tensors[i].ttype == TAMD_TT_CONST || !L.dense[i]) continue;
+            if (g->tensors[i].ttype == TAMD_TT_CONST || !L.dense[i] || viewed[i]) continue;
             const bool is_alias_op = !n.out.empty() && L.alias_of[n.out[0]] == i;
             if (is_alias_op) continue;
             if (!(L.flat_concat[ni] && L.perm_src[i] >= 0)) need_buf[root(i)] = 1;
@@ -95,7 +117,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
         HTensor& d = g->tensors[t];
         if (!L.dense[t] || L.alias_of[t] >= 0) continue;
         if (d.dtype != TAMD_DT_INT8) { set_error("tensor %s: dtype %d not supported on the device yet", d.name.c_str(), d.dtype); return -1; }
-        if (L.perm_src[t] >= 0) continue;                             // never written: read through its NHWC source
+        if (L.perm_src[t] >= 0 || viewed[t]) continue;                // never written: read through its NHWC source
         if (dev_alloc(g, &d.dptr, d.elems(), true)) return -1;
     }
     return 0;
@@ -112,7 +134,8 @@ static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_F
 // -128 where their input holds it, and the reference's Concat of several inputs turns that byte into 127 even between equal scales
 // (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not.  Upsample holds that byte too and IS written in
 // place: its launch stores 127 for it, where the Concat is its only reader (plan_concat_views, plan_upsample)
-static bool reads_slices(int op) { return slice_capable(op) || op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL; }
+// A Transpose reads its source through strides (plan_transpose): a channel slice is the same read from another base
+static bool reads_slices(int op) { return slice_capable(op) || op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL || op == TAMD_OP_TRANSPOSE; }
 
 static int plan_concat_views(tamd_graph* g, I8Layout& L)
 {
@@ -303,6 +326,9 @@ static int plan_buffers(tamd_graph* g, I8Layout& L)
     // the input of a byte map that runs inside its channel-gate Eltwise's launch (match_gate_lut) is read at the ELTWISE's position
     for (int ni = 0; ni < NN; ni++)
         if (L.gate_lut[ni]) { const int r = root_of(g->nodes[L.gate_lut[ni] - 1].in[0]); death[r] = std::max(death[r], ni); }
+    // the source of a Reshape that its Transpose reads through (plan_dense: tview) is read at the TRANSPOSE's position
+    for (int ni = 0; ni < NN; ni++)
+        if (L.tview[ni]) { const int r = root_of(g->nodes[L.tview[ni] - 1].in[0]); death[r] = std::max(death[r], ni); }
     std::vector<char> pinned(g->tensors.size(), 0);
     for (auto& io : g->inputs) pinned[root_of(io.tensor)] = 1;
     for (auto& io : g->outputs) pinned[root_of(io.tensor)] = 1;
@@ -885,6 +911,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_SPLIT: r = plan_split(g, L, n, &out); break;
         case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n, &out); break;
         case TAMD_OP_PRELU: r = plan_prelu(g, n, &out); break;
+        case TAMD_OP_TRANSPOSE: r = plan_transpose(g, n, L.tview[ni] ? g->nodes[L.tview[ni] - 1].in[0] : -1, &out); break;
         default:
             set_error("op %d (%s) is not supported on the device", n.op, n.name.c_str());
             return -1;

@@ -1,6 +1,6 @@
 // The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
-// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu and plan_interp
-// serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
+// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
+// plan_interp and plan_transpose serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
 // graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
 #include "graph.h"
 #include "graph_internal.h"
@@ -455,6 +455,90 @@ int plan_slice_u8(tamd_graph* g, HNode& n, int next, std::vector<Step>* out)
         if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
         g->fused_away[n.out[0]] = 1;                        // the tensor between the two only exists inside the launch
     }
+    return 0;
+}
+
+// ---- Transpose of a quantised graph (transpose.hip), both types.  Everything the reference decides for the node is decided by
+// transpose_refusal (node_rules.h): the ranks, the order vector, the output's dims, the byte map
+const char* transpose_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, TransposeGeom* geom, unsigned char* table)
+{
+    if (n.in.empty() || n.out.empty()) return "Transpose takes one input";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    return transpose_refusal(&n.p.transpose, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), x.scales.empty() ? 0.f : x.scales[0],
+                             x.zps.empty() ? 0 : x.zps[0], y.scales.size(), y.scales.empty() ? 0.f : y.scales[0], y.zps.empty() ? 0 : y.zps[0], (int)y.dims.size(),
+                             check_out ? y.dims.data() : nullptr, geom, table);
+}
+
+// The strides (bytes per step of every axis) under which `dims` index the convolution-stack NHWC buffer that s lives in -- element
+// (n, c, p) of s lies at n * H * W * cs + p * cs + c behind its first channel --, where every axis of dims factors exactly ONE of the
+// three index ranges N, C, H * W of s: (N, 255, H, W) seen as (N, 3, 85, H, W) does, C splits into 3 x 85, and so does s's own shape.
+// false: an axis mixes two ranges (C with H, say), and no strides exist.  A size-1 axis factors anything (stride 0)
+bool nhwc_view_strides(const HTensor& s, const std::vector<int>& dims, long* strides)
+{
+    size_t want = 1;
+    for (int d : dims) want *= (size_t)d;
+    if (dims.size() > 8 || want != (size_t)s.n * s.c * s.h * s.w) return false;
+    const long range[3] = {s.n, s.c, (long)s.h * s.w}, unit[3] = {(long)s.h * s.w * s.cs, 1, s.cs};
+    int gi = 0;
+    long acc = 1;
+    for (size_t d = 0; d < dims.size(); d++) {
+        const long e = dims[d];
+        if (e == 1) { strides[d] = 0; continue; }
+        while (gi < 3 && acc == range[gi]) { gi++; acc = 1; }          // the range is used up: the next one
+        if (gi >= 3 || range[gi] % (acc * e) != 0) return false;
+        acc *= e;
+        strides[d] = range[gi] / acc * unit[gi];
+    }
+    return true;
+}
+
+// One launch.  view_src >= 0 (int8 graphs): the node reads tensor view_src, a convolution-stack tensor, THROUGH the Reshape in front of
+// it (nhwc_view_strides; plan_dense matched it and the Reshape has no launch); else its own input -- a dense tensor, or in an int8
+// graph a convolution-stack tensor read where it lies, a concat or Split view included.  The form: TAMD_PIN=transpose_form where that
+// form is legal for the geometry, else transpose_default_form
+int plan_transpose(tamd_graph* g, HNode& n, int view_src, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    TransposeGeom tg;
+    std::vector<unsigned> table(64, 0u);
+    unsigned char* tb = (unsigned char*)table.data();
+    const char* why = transpose_refusal_of(g, n, true, &tg, tb);
+    if (why) { set_error("transpose %s: %s", n.name.c_str(), why); return -1; }
+    if (y.is_view || !(y.nchw_raw || y.cs <= 0) || y.dtype != x.dtype) { set_error("transpose %s: the output must be a dense tensor of the input's type", n.name.c_str()); return -1; }
+    const HTensor& s = view_src >= 0 ? g->tensors[view_src] : x;
+    std::string node = n.name;
+    TransposeArgs a{};
+    if (s.nchw_raw || s.cs <= 0) {                               // dense: the canonical geometry as transpose_refusal resolved it
+        if (view_src >= 0 || s.is_view) { set_error("transpose %s on a concat view is not supported in a uint8 graph", n.name.c_str()); return -1; }
+        a.x = (const uint8_t*)s.dptr; a.src_bytes = (unsigned)s.elems();
+    } else {                                                     // a convolution-stack buffer: the same thing with other strides
+        long strides[8];
+        if (!nhwc_view_strides(s, x.dims, strides)) { set_error("transpose %s: the input's shape mixes the channel and the spatial axes of %s", n.name.c_str(), s.name.c_str()); return -1; }
+        const size_t bytes = (size_t)s.n * s.h * s.w * s.cs;
+        if (bytes > 0x7fffffffu) { set_error("transpose %s: the source buffer has more than 2^31 bytes", n.name.c_str()); return -1; }
+        transpose_canon((int)x.dims.size(), x.dims.data(), strides, n.p.transpose.order, &tg);
+        a.x = (const uint8_t*)s.dptr + s.c_off; a.src_bytes = (unsigned)(bytes - (size_t)s.c_off);
+        if (view_src >= 0) {
+            for (auto& m : g->nodes) if (!m.out.empty() && m.out[0] == n.in[0]) node = m.name + "+" + n.name;
+            if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+            g->fused_away[n.in[0]] = 1;                          // the reshaped tensor is never written
+        }
+    }
+    a.y = (uint8_t*)y.dptr; a.nd = tg.nd; a.unit = tg.unit; a.total = (unsigned)y.elems();
+    for (int d = 0; d < 6; d++) { a.extent[d] = tg.extent[d]; a.stride[d] = (int)tg.stride[d]; }
+    a.identity = 1;
+    for (int b = 0; b < 256; b++) a.identity &= tb[b] == b;
+    if (!a.identity) {
+        unsigned* dtable = nullptr;
+        if (upload(g, table, &dtable)) return -1;
+        a.table = dtable;
+    }
+    const int pin = tamd_pin_int("transpose_form", -1);
+    a.form = pin >= 0 && transpose_form_legal(a, pin) ? pin : transpose_default_form(a);
+    out->push_back(make_step(node, transpose_kernel_name(a.form), 0, 2.0 * (double)y.elems(), [a](hipStream_t st) { return launch_transpose(a, st); }, {access_of(s)},
+                             {access_of(y)}, false));
     return 0;
 }
 

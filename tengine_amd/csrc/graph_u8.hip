@@ -912,6 +912,7 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // one chan_map_u8 launch per output
         case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
         case TAMD_OP_SLICE: rc = plan_slice_u8(g, n, slice_next[ni] - 1, &out); break;      // one slice_u8 launch, the Slice behind it inside
+        case TAMD_OP_TRANSPOSE: rc = plan_transpose(g, n, -1, &out); break;      // one launch; the Reshapes around it are views
         case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it

@@ -364,6 +364,23 @@ struct SliceU8Args {
                                    // step > 1), 1 inside a row, 2 inside a plane (W not cut, H step 1), 3 inside an image (H not cut, C step 1)
 };
 
+// Transpose of a quantised graph (transpose.hip; the host truth of the byte map: transpose_tables.cc), both types:
+// y[o] = table[x[sum_d i_d * stride[d]]] with o decomposed over extent[] as a dense row-major index, axis nd - 1 innermost.  The pairs are
+// the canonical geometry of transpose_canon (node_rules.h), LEFT-aligned as it makes them (axes nd .. 5: extent 1, stride 0).  x is a
+// dense tensor or a convolution-stack NHWC buffer (the same thing with other strides, base + c_off); y is dense
+struct TransposeArgs {
+    const uint8_t* x; uint8_t* y;
+    int nd;                        // 1 .. 6
+    int extent[6], stride[6];      // every extent >= 1; the largest source offset stays below src_bytes: launch_transpose checks it
+    int unit;                      // which axis has stride 1 (-1: none)
+    unsigned total;                // output bytes, the product of the extents
+    unsigned src_bytes;            // bytes of the buffer x points into, from x on
+    const unsigned* table;         // [64]: the 256 bytes of the map as they lie
+    int identity;                  // the map is the identity: no table, no LDS map
+    int form;                      // kTransposeGather | kTransposeRows | kTransposeTile
+};
+enum { kTransposeGather = 0, kTransposeRows = 1, kTransposeTile = 2 };
+
 // PReLU of a quantised graph (prelu.hip; the host truth: prelu_tables.cc)
 struct PreluI8Args {       // NHWC int8, x and y of one pixel stride: y = requant(x < 0 ? x * slope[c] : x), the chain of relu_i8 per channel
     const int8_t* x; int8_t* y;
@@ -526,6 +543,11 @@ hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s);
 hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
 hipError_t launch_slice_u8(const SliceU8Args& a, hipStream_t s);
+// which forms a geometry is legal in, and the default among them (transpose.hip: the one place it is decided)
+bool transpose_form_legal(const TransposeArgs& a, int form);
+int transpose_default_form(const TransposeArgs& a);
+const char* transpose_kernel_name(int form);
+hipError_t launch_transpose(const TransposeArgs& a, hipStream_t s);
 hipError_t launch_prelu_i8(const PreluI8Args& a, hipStream_t s);
 hipError_t launch_prelu_u8(const PreluU8Args& a, hipStream_t s);
 hipError_t launch_chan_gate_i8(const ChanGateI8Args& a, hipStream_t s);

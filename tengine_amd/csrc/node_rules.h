@@ -10,6 +10,7 @@
 #include "lut_tables.h"
 #include "prelu_tables.h"
 #include "slice_tables.h"
+#include "transpose_tables.h"
 
 namespace tamd {
 
@@ -213,6 +214,88 @@ inline const char* slice_refusal(const tamd_slice_param* p, int dtype, int in_di
     }
     if (table) for (int b = 0; b < 256; b++) table[b] = map[b];
     if (geom) *geom = sg;
+    return nullptr;
+}
+
+// Transpose: the two quantised kernels of the reference (transpose_ref.c; transpose.hip).  fp32 graphs keep the node on the CPU device
+inline bool transpose_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// what transpose_refusal resolves for its callers: the output's dims as the reference infers them (out_dims[i] = in_dims[order[i]]) and
+// the CANONICAL geometry of the move -- nd (extent, input stride) pairs in output order, outermost first: axes of size 1 are dropped,
+// and output axes that are neighbours in the input too (stride[i] == extent[i + 1] * stride[i + 1]) are merged into one.  unit: which of
+// them carries input stride 1, -1: none (a source whose innermost axis is padded and of size 1).  One element: nd 1, extent 1
+struct TransposeGeom {
+    int rank;
+    int out_dims[8];
+    int nd;
+    int extent[6];
+    long stride[6];
+    int unit;
+};
+// the canonical geometry of reading a tensor of `rank` axes (in_dims, in_strides: elements per step of every INPUT axis, any layout) in
+// the order `order`.  The dense strides give what transpose_refusal resolves; the int8 planner calls it again with the strides of a
+// convolution-stack buffer (n: H * W * cs, c: 1, h: W * cs, w: cs)
+inline void transpose_canon(int rank, const int* in_dims, const long* in_strides, const int* order, TransposeGeom* g)
+{
+    int nd = 0;
+    for (int i = 0; i < rank; i++) {
+        const int e = in_dims[order[i]];
+        const long s = in_strides[order[i]];
+        if (e == 1) continue;
+        if (nd > 0 && g->stride[nd - 1] == (long)e * s) { g->extent[nd - 1] *= e; g->stride[nd - 1] = s; }
+        else { g->extent[nd] = e; g->stride[nd] = s; nd++; }
+    }
+    if (nd == 0) { g->extent[0] = 1; g->stride[0] = 1; nd = 1; }
+    g->nd = nd; g->unit = -1;
+    for (int i = 0; i < nd; i++) if (g->stride[i] == 1) g->unit = i;
+    for (int i = nd; i < 6; i++) { g->extent[i] = 1; g->stride[i] = 0; }
+}
+// One Transpose node: nullptr when the device runs it (*geom resolved for a dense input, table[256]: the byte map between the two
+// tensors; either may be null), else the reason.  out_dims: the output's dims where the caller has them (null: not checked).
+//  - rank 2 .. 6: run() switches on the INPUT's rank and has a loop nest for these five; for any other the output is quantised from
+//    memory nobody wrote
+//  - a tr_shape of another length: infer_shape gives the output tr_shape_size dims while the loops index permute[0 .. rank - 1] -- past
+//    the vector, or short of the tensor
+//  - a repeated or out-of-range entry: the loops read outside the input or leave output elements unwritten
+inline const char* transpose_refusal(const tamd_transpose_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, float in_scale,
+                                     int in_zp, size_t out_quant, float out_scale, int out_zp, int out_dim_num, const int* out_dims, TransposeGeom* geom,
+                                     unsigned char* table)
+{
+    if (!p) return "Transpose needs its parameter";
+    if (!transpose_on_device(dtype)) return "Transpose runs on the device in int8 and uint8 graphs only";
+    if (in_dim_num == 1) return "a Transpose of a 1-D tensor does not run on the device (the reference has no loop for rank 1)";
+    if (in_dim_num > 6) return "a Transpose of a tensor of more than 6 dimensions does not run on the device (the reference has no loop above rank 6)";
+    if (in_dim_num < 1) return "Transpose: the input has no shape";
+    if (p->dim_num != in_dim_num) return "Transpose: tr_shape must have one entry per input dimension";
+    unsigned seen = 0;
+    for (int i = 0; i < in_dim_num; i++) {
+        if (p->order[i] < 0 || p->order[i] >= in_dim_num) return "Transpose: a tr_shape entry is outside the tensor's rank";
+        if (seen & 1u << p->order[i]) return "Transpose: tr_shape repeats an axis (it is not a permutation)";
+        seen |= 1u << p->order[i];
+    }
+    if (in_const) return "Transpose: the input must not be a constant";
+    if (in_quant != 1 || out_quant != 1) return "Transpose needs per-tensor quant params on both sides";
+    size_t elems = 1;
+    for (int i = 0; i < in_dim_num; i++) {
+        if (in_dims[i] < 1) return "Transpose: every input dimension must be at least 1";
+        elems *= (size_t)in_dims[i];
+        if (elems > 0x7fffffffu - 64) return "Transpose: the tensor has more than 2^31 elements";      // 32-bit positions in the kernels
+    }
+    TransposeGeom tg;
+    tg.rank = in_dim_num;
+    for (int i = 0; i < 8; i++) tg.out_dims[i] = i < in_dim_num ? in_dims[p->order[i]] : 0;        // transpose.c:45-48
+    if (out_dims) {
+        if (out_dim_num != in_dim_num) return "Transpose: the output does not have the dims the reference infers";
+        for (int i = 0; i < in_dim_num; i++)
+            if (out_dims[i] != tg.out_dims[i]) return "Transpose: the output does not have the dims the reference infers";
+    }
+    long strides[8];
+    long s = 1;
+    for (int i = in_dim_num - 1; i >= 0; i--) { strides[i] = s; s *= in_dims[i]; }
+    transpose_canon(in_dim_num, in_dims, strides, p->order, &tg);
+    unsigned char map[256];
+    if (tamd_transpose_table(dtype, in_scale, in_zp, out_scale, out_zp, map)) return "Transpose: the quantisation parameters give a value the reference cannot convert to int";
+    if (table) for (int b = 0; b < 256; b++) table[b] = map[b];
+    if (geom) *geom = tg;
     return nullptr;
 }
 

@@ -83,6 +83,7 @@ int map_op(uint32_t t)
     case 55: return TAMD_OP_SHUFFLECHANNEL;
     case 70: return TAMD_OP_HARDSWISH;
     case 71: return TAMD_OP_INTERP;
+    case 77: return TAMD_OP_TRANSPOSE;
     case 87: return TAMD_OP_CLIP;
     case 97: return TAMD_OP_MISH;
     default: return -1;
@@ -218,6 +219,15 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 if (rank > 0 && q.axis >= -rank && q.axis < rank) q.axis = (q.axis + rank) % rank;
                 break;
             }
+            case TAMD_OP_TRANSPOSE: {                          // TM2_TransposeParam :929-932 {offset_tr_shape -> TM2_Vector_dims} (tm2_transpose.c)
+                const uint32_t vs = r.u32(po);
+                if (!vs) return fail("transpose without its tr_shape vector");
+                const std::vector<uint32_t> order = r.vec(vs);
+                if (!r.ok) break;
+                p.transpose.dim_num = (int)order.size();       // any length travels: transpose_refusal names the ones that do not run
+                for (size_t i = 0; i < order.size() && i < 8; i++) p.transpose.order[i] = (int)order[i];
+                break;
+            }
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)
                 tamd_priorbox_param& q = p.priorbox;
                 auto floats = [&](uint32_t vo_, float* dst, int cap, int* num) {      // TM2_Vector_floats {v_num, data[]}
@@ -242,6 +252,7 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
             default: break;
             }
         }
+        if (op == TAMD_OP_TRANSPOSE && !po) return fail("transpose without its tr_shape vector");
         if (!r.ok) return fail("corrupt operator params");
         std::vector<int> ins(vi.begin(), vi.end()), outs(vo.begin(), vo.end());
         tamd_node_desc d{};

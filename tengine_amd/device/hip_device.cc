@@ -58,6 +58,7 @@ extern "C" {
 #include "relu_param.h"
 #include "softmax_param.h"
 #include "split_param.h"
+#include "transpose_param.h"
 #include "upsample_param.h"
 }
 
@@ -99,6 +100,10 @@ const OpRow kOps[] = {
     // YOLOv4-tiny's routes and Focus's strided picks (csrc/slice.hip): the onnx form in uint8 graphs.  The reference has no int8 kernel, and
     // an fp32 graph keeps the node on the CPU device -- the caffe Slice of the ShuffleNet benchmark file too (which: tamd_node_supported)
     {OP_SLICE, TAMD_OP_SLICE, true},
+    // every ONNX Transpose (csrc/transpose.hip): the Detect head of the YOLOv5 family, torch's channel shuffle, the ONNX form of the SSD
+    // head permute -- the two quantised kernels of the reference, rank 2 .. 6.  An fp32 graph keeps the node on the CPU device (which
+    // orders: tamd_node_supported)
+    {OP_TRANSPOSE, TAMD_OP_TRANSPOSE, true},
 };
 
 const OpRow* find_op(int op)
@@ -139,7 +144,7 @@ bool translate_priorbox(const struct priorbox_param* p, tamd_priorbox_param* q)
 }
 
 // descriptor of an IR tensor.  with_payload: the constant's bytes and the quantisation values travel too (pre_run); without, shapes
-// and the quantisation form alone (tamd_node_supported looks at nothing else, but for a PReLU's slope and a Slice's scales).  The pointers stay the IR tensor's own.
+// and the quantisation form alone (tamd_node_supported looks at nothing else, but for a PReLU's slope and the scales of a Slice or a Transpose).  The pointers stay the IR tensor's own.
 tamd_tensor_desc describe_tensor(struct tensor* t, bool with_payload)
 {
     tamd_tensor_desc d;
@@ -161,7 +166,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle; tamd_slice_param slice;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_transpose_param transpose;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -225,6 +230,13 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
         s->slice.slice_point_num = p->slice_point_ ? get_vector_num(p->slice_point_) : 0;
         s->slice.begin_num = p->begin_ ? get_vector_num(p->begin_) : 0;
         s->slice.size_num = p->size_ ? get_vector_num(p->size_) : 0;
+        break;
+    }
+    case TAMD_OP_TRANSPOSE: {        // the tr_shape vector inline; its length as it is (the first 8 entries: transpose_refusal names the lengths that do not run)
+        const struct transpose_param* p = (const struct transpose_param*)n->op.param_mem;
+        s->transpose = tamd_transpose_param{};
+        s->transpose.dim_num = p->tr_shape ? p->tr_shape_size : 0;
+        for (int i = 0; i < s->transpose.dim_num && i < 8; i++) s->transpose.order[i] = p->tr_shape[i];
         break;
     }
     case TAMD_OP_SPLIT: {            // the split_sizes vector inline; num -1: is_caffe, 0: no sizes, above TAMD_SPLIT_MAX: too many (all refused by name)
@@ -522,8 +534,8 @@ static bool node_supported(struct graph* ir, struct node* n)
     if (op == TAMD_OP_INPUT || op == TAMD_OP_CONST) return true;
     std::vector<tamd_tensor_desc> in, out;
     // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device --
-    // and for a Slice's quantisation values on both sides: a pair whose byte map the reference cannot compute does the same)
-    const bool values = op == TAMD_OP_SLICE;
+    // and for the quantisation values on both sides of a Slice or a Transpose: a pair whose byte map the reference cannot compute does the same)
+    const bool values = op == TAMD_OP_SLICE || op == TAMD_OP_TRANSPOSE;
     for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), values || (op == TAMD_OP_PRELU && k == 1)));
     for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), values));
     NodeParams params;
@@ -540,8 +552,8 @@ static bool node_supported(struct graph* ir, struct node* n)
 // last asked of the backend itself (tamd_node_supported: the planners' conditions), so that the splitter and pre_run cannot
 // disagree.  (Round 2 also kept two leftover guards here -- Concat axis != 1, Permute order -- from before the backend learnt
 // them; the Concat one silently sent the whole of MobileNet-SSD-with-priors to the CPU device.  They are gone.)
-// int8 graphs (round 6): what a Permute / PriorBox produces -- and every Flatten / Reshape / Dropout / Concat / Softmax result that is only a
-// re-reading of it -- lives in the reference's DENSE element order on the device (csrc/graph_plan.hip "dense tensors"), not in the NHWC
+// int8 graphs (round 6): what a Permute / Transpose / PriorBox produces -- and every Flatten / Reshape / Dropout / Concat / Softmax /
+// Sigmoid / Clip result that is only a re-reading or a byte map of it -- lives in the reference's DENSE element order on the device (csrc/graph_plan.hip "dense tensors"), not in the NHWC
 // layout the convolution stack reads.  Only those re-reading operators may consume such a tensor there; anything else (an FC behind
 // Permute -> Flatten, say) is left to the CPU device here, so that the splitter and the planner cannot disagree (the planner would
 // refuse the graph by name at pre_run otherwise).
@@ -550,8 +562,8 @@ bool int8_tensor_is_dense_on_device(struct graph* ir, struct tensor* t, int dept
     if (!t || t->producer < 0 || depth > 16) return false;
     struct node* pn = get_ir_graph_node(ir, t->producer);
     switch (pn->op.type) {
-    case OP_PERMUTE: case OP_PRIORBOX: case OP_RESHAPE: return true;
-    case OP_FLATTEN: case OP_DROPOUT: case OP_SOFTMAX:
+    case OP_PERMUTE: case OP_PRIORBOX: case OP_RESHAPE: case OP_TRANSPOSE: return true;
+    case OP_FLATTEN: case OP_DROPOUT: case OP_SOFTMAX: case OP_SIGMOID: case OP_CLIP:      // (a byte map keeps the element order it finds)
         return pn->input_num >= 1 && int8_tensor_is_dense_on_device(ir, get_ir_graph_tensor(ir, pn->input_tensors[0]), depth + 1);
     case OP_CONCAT:
         for (int i = 0; i < pn->input_num; i++)
@@ -587,7 +599,7 @@ bool node_runs_on_device(struct graph* ir, struct node* n)
         }
     }
     if (out_dt == TENGINE_DT_INT8 && n->op.type != OP_FLATTEN && n->op.type != OP_RESHAPE && n->op.type != OP_DROPOUT && n->op.type != OP_CONCAT
-        && n->op.type != OP_SOFTMAX && n->op.type != OP_PRIORBOX)
+        && n->op.type != OP_SOFTMAX && n->op.type != OP_PRIORBOX && n->op.type != OP_TRANSPOSE && n->op.type != OP_SIGMOID && n->op.type != OP_CLIP)
         for (int i = 0; i < n->input_num; i++) {
             struct tensor* t = get_ir_graph_tensor(ir, n->input_tensors[i]);
             if (t->tensor_type != TENSOR_TYPE_CONST && int8_tensor_is_dense_on_device(ir, t)) return false;

@@ -29,7 +29,7 @@ OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
-    "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Clip": 87, "Mish": 97,
+    "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "Clip": 87, "Mish": 97,
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
@@ -186,6 +186,10 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
 
         return {"axis": axis, "slice_points": vi(vsp), "begins": vi(vbg), "sizes": vi(vsz), "iscaffe": iscaffe, "ismxnet": ismxnet,
                 "isonnx": isonnx, "begin": begin, "end": end, "step": step}
+    if op == "Transpose":       # TM2_TransposeParam (tm2_format.h:929-932): {offset_tr_shape -> TM2_Vector_dims}
+        voff = struct.unpack_from("<I", b, off)[0]
+        n = struct.unpack_from("<I", b, voff)[0] if voff else 0
+        return {"tr_shape": list(struct.unpack_from("<%di" % n, b, voff + 4)) if voff else None}
     if op == "Permute":
         v = struct.unpack_from("<5i", b, off)
         return {"flag": v[0], "order": list(v[1:])}
@@ -279,6 +283,9 @@ def write_tm2(g: Graph) -> bytes:
             vecs = [bl.vec_i32(q[k]) if q.get(k) else 0 for k in ("slice_points", "begins", "sizes")]
             pb = struct.pack("<i3I6i", q.get("axis", 1), vecs[0], vecs[1], vecs[2], q.get("iscaffe", 0), q.get("ismxnet", 0), q.get("isonnx", 1),
                              q.get("begin", 0), q.get("end", 0), q.get("step", 1))
+        elif n.op == "Transpose":  # TM2_TransposeParam {offset_tr_shape -> TM2_Vector_dims}; tr_shape None: TM2_NOT_SET, a node no loader accepts
+            order = n.params.get("tr_shape")
+            pb = struct.pack("<I", bl.vec_i32(order) if order is not None else 0)
         elif n.op == "PriorBox":  # TM2_PriorBoxParam; the loader dereferences all four vector offsets (tm2_priorbox.c:49-52): empty
             q = n.params        # vectors are written as {v_num = 0}
             pb = struct.pack("<4I5i3f2i", bl.vec_f32(q["min_size"]), bl.vec_f32(q.get("max_size", [])),
