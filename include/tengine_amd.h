@@ -106,6 +106,15 @@ enum {
      * input through tamd_transpose_table (int8 saturates at +-127: -128 never comes out).  fp32 graphs keep the node on the CPU device */
     /* 27: reserved, never supported (like 21 and 24: tests/test_slice_cpu.py holds the code to that answer) */
     TAMD_OP_TRANSPOSE = 28,
+    /* 29: reserved, never supported (like 21, 24 and 27: tests/test_transpose_cpu.py holds the code to that answer) */
+    /* the cut of RetinaFace's top-down pyramid (the x2 map of a 240 / 32 = 7.5 -> 8 row level is one row too tall for its lateral), uint8
+     * graphs: param tamd_crop_param; inputs [data, like], of `like` only the shape is read.  The output has N, C, H, W of `like`
+     * (crop.c:34-78) and is a box of the data's RAW bytes: ref_crop_uint8 (crop_ref.c:147-253) reads no quantisation parameter of either
+     * tensor.  The caffe form (flag 0) with axis 1 (box start offset_c, offset_h, offset_w) or axis 2 (0, offset_h, offset_w) and the
+     * MXNet form (flag 1) with num_args 2 (0, offset_h, offset_w).  The centre crop (num_args 1), every other flag / axis, a negative
+     * offset and a box that leaves the data tensor are refused by name; int8 graphs (no kernel in the reference) and fp32 graphs keep
+     * the node on the CPU device */
+    TAMD_OP_CROP = 30,
     TAMD_OP_NUM
 };
 
@@ -160,6 +169,8 @@ typedef struct tamd_slice_param {
 /* transpose_param.h: the tr_shape vector inline.  dim_num: its length as the file stores it (any value: a length the device does not
  * run is refused by name; only the first 8 entries are carried); out.dims[i] = in.dims[order[i]] (transpose.c:35-54) */
 typedef struct tamd_transpose_param { int dim_num; int order[8]; } tamd_transpose_param;
+/* crop_param.h, field for field */
+typedef struct tamd_crop_param { int num_args, offset_c, offset_h, offset_w, crop_h, crop_w, center_crop, axis, flag; } tamd_crop_param;
 
 /* == struct priorbox_param (source/operator/prototype/priorbox_param.h:28-52) with the float vectors inline; num_priors /
  * out_dim are re-derived as priorbox.c:37-64 does.  inputs: [0] feature map, [1] the image ("data") -- shapes only */

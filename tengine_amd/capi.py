@@ -120,6 +120,11 @@ def slice_table(in_scale, in_zp, out_scale, out_zp):
     rc = lib().tamd_slice_table(in_scale, in_zp, out_scale, out_zp, tab)
     return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 OP_TRANSPOSE = 28        # (27: reserved, like 21 and 24)
+OP_CROP = 30             # (29: reserved too)
+
+
+class CropParam(C.Structure):         # tamd_crop_param
+    _fields_ = [(k, C.c_int) for k in ("num_args", "offset_c", "offset_h", "offset_w", "crop_h", "crop_w", "center_crop", "axis", "flag")]
 
 
 class TransposeParam(C.Structure):    # tamd_transpose_param

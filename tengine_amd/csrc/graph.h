@@ -55,6 +55,7 @@ union NodeParam {
     tamd_shufflechannel_param shuffle;
     tamd_slice_param slice;
     tamd_transpose_param transpose;
+    tamd_crop_param crop;
 };
 
 struct HNode {
@@ -308,7 +309,9 @@ int plan_nchw_outputs(tamd_graph* g, size_t esz);
 int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // a nearest Interp node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch: index vectors and byte map uploaded,
 // interp_nearest_i8 / interp_nearest_u8; reads and writes channel slices (concat views)
-int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// crop (uint8 graphs; crop_interp_producer): the Crop that alone reads the Interp runs inside the launch -- the index vectors shifted and
+// cut by its box, the Crop's output written, the Interp's own output never
+int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out, const HNode* crop = nullptr);
 // Split / ShuffleChannel of a uint8 (NCHW) graph: one chan_map_u8 launch per output tensor, the plane map and the
 // Split's byte map uploaded.  The int8 forms are declared in graph_plan.h
 int plan_split_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
@@ -334,6 +337,22 @@ const char* transpose_refusal_of(const tamd_graph* g, const HNode& n, bool check
 bool nhwc_view_strides(const HTensor& s, const std::vector<int>& dims, long* strides);
 // a Transpose node of an int8 or uint8 graph as ONE launch (transpose.hip); view_src >= 0: read through the Reshape in front of it
 int plan_transpose(tamd_graph* g, HNode& n, int view_src, std::vector<Step>* out);
+// crop_refusal (node_rules.h) asked of a node of this graph: infer_shapes (check_out false: the output's dims are not made yet),
+// validate_graph and the planners.  *geom (may be null): the resolved box
+const char* crop_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, CropGeom* geom);
+// the nearest Interp that can run inside the launch of Crop `ci` (Interp -> Crop as one interp_nearest_u8 launch): it makes the Crop's
+// data input, which nothing else reads and which is no graph output or view; it passes interp_refusal, the Crop passes crop_refusal and
+// its box cuts no channels; TAMD_PIN=crop_chain=0 is not set.  Its node index, -1: none
+int crop_interp_producer(const tamd_graph* g, size_t ci);
+// the same-shape Eltwise (PROD, SUM, SUB, MAX) that can take the Interp -> Crop chain of Crop `ci` into ITS launch (topdown_u8): the one
+// reader of the Crop's output, which is no graph output; its other operand a dense tensor of the output's dims;
+// crop_interp_producer(ci) >= 0 and TAMD_PIN=topdown=1 is set (opt-in: measured level with or behind the two launches it replaces,
+// profiles/crop_topdown.txt).  Its node index, -1: none
+int crop_topdown_next(const tamd_graph* g, size_t ci);
+// a Crop node of a uint8 (NCHW) graph alone: ONE slice_u8 launch over the box in its identity form (raw bytes, step 1)
+int plan_crop_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// Interp `in` -> Crop `cn` -> Eltwise `n` as ONE topdown_u8 launch (topdown.hip), planned at the Eltwise's position
+int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
 // same-shape form, else which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1)
 const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated);

@@ -83,6 +83,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL) return chanmap_on_device(dtype);      // byte movers, int8 / uint8 (which forms: tamd_node_supported)
     if (op == TAMD_OP_SLICE) return slice_on_device(dtype);        // the onnx form, uint8 (which forms and extents: tamd_node_supported)
     if (op == TAMD_OP_TRANSPOSE) return transpose_on_device(dtype);      // int8 / uint8 (which ranks and orders: tamd_node_supported)
+    if (op == TAMD_OP_CROP) return crop_on_device(dtype);          // a box of raw bytes, uint8 (which forms and boxes: tamd_node_supported)
     if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
@@ -237,6 +238,12 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
                                  out[0].quant_num == 1 && out[0].zero_points ? out[0].zero_points[0] : 0, out[0].dim_num, out[0].dims, nullptr, nullptr)
                == nullptr;
     }
+    case TAMD_OP_CROP: {
+        if (n_in != 2 || !in) return 0;
+        return crop_refusal((const tamd_crop_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, in[1].dim_num,
+                            in[1].dims, (size_t)out[0].quant_num, out[0].dim_num, out[0].dims, nullptr)
+               == nullptr;
+    }
     case TAMD_OP_PRELU: {
         if (n_in < 2 || !in) return 0;
         if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
@@ -309,6 +316,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_SHUFFLECHANNEL: n.p.shuffle = *(const tamd_shufflechannel_param*)d->param; break;
         case TAMD_OP_SLICE: n.p.slice = *(const tamd_slice_param*)d->param; break;
         case TAMD_OP_TRANSPOSE: n.p.transpose = *(const tamd_transpose_param*)d->param; break;
+        case TAMD_OP_CROP: n.p.crop = *(const tamd_crop_param*)d->param; break;
         default: break;
         }
     }

@@ -261,6 +261,13 @@ int infer_shapes(tamd_graph* g)
             y.dims.assign(tg.out_dims, tg.out_dims + tg.rank);
             break;
         }
+        case TAMD_OP_CROP: {              // crop.c:34-78: N, C, H, W of INPUT 1.  What the device does not run is refused HERE, by name (crop_refusal)
+            CropGeom cg;
+            const char* why = crop_refusal_of(g, n, false, &cg);
+            if (why) { set_error("crop %s: %s", n.name.c_str(), why); return -1; }
+            y.dims.assign(cg.out_dims, cg.out_dims + 4);
+            break;
+        }
         case TAMD_OP_PRELU: y.dims = x.dims; y.dtype = x.dtype; break;      // prelu.c: the input's shape; the type is the data's, not the fp16 slope's
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
@@ -347,6 +354,10 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_SLICE) {
             const char* why = slice_refusal_of(g, n, true, nullptr, nullptr);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_CROP) {
+            const char* why = crop_refusal_of(g, n, true, nullptr);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_TRANSPOSE) {

@@ -1,5 +1,5 @@
 // The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
-// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
+// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, the uint8 Crop (alone, inside the Interp's launch, or with both inside the Eltwise's), Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
 // plan_interp and plan_transpose serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
 // graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
 #include "graph.h"
@@ -200,18 +200,33 @@ int plan_prelu(tamd_graph* g, HNode& n, std::vector<Step>* out)
 // output column (tamd_interp_indices), the byte map between the two tensors' quantisation parameters (tamd_interp_table) -- uploaded,
 // and one launch of interp.hip looks them up.  int8: NHWC with padded channel stride, reads a channel slice, writes one (a concat
 // view), like plan_upsample.  uint8: dense NCHW; writes a channel range of a concat buffer (out_img / out_c0), like plan_map_u8.
-int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out)
+// With `crop` (uint8; crop_interp_producer) the launch writes the CROP's output: the Crop copies raw bytes, so it only shifts and cuts the
+// two index vectors by its box; the byte map stays the Interp's own, between x and the Interp's own output tensor
+int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out, const HNode* crop)
 {
     HTensor& x = g->tensors[n.in[0]];
-    HTensor& y = g->tensors[n.out[0]];
+    HTensor& mid = g->tensors[n.out[0]];
+    HTensor& y = crop ? g->tensors[crop->out[0]] : mid;
+    const std::string name = crop ? n.name + "+" + crop->name : n.name;
     InterpGeom geom;
     std::vector<int> iy, ix;
-    const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), &geom, &iy, &ix);
-    if (why) { set_error("interp %s: %s", n.name.c_str(), why); return -1; }
-    if (y.dtype != x.dtype || y.n != x.n || y.c != x.c || y.h != geom.out_h || y.w != geom.out_w) { set_error("interp %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const char* why = interp_refusal(&n.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), mid.scales.size(), &geom, &iy, &ix);
+    if (why) { set_error("interp %s: %s", name.c_str(), why); return -1; }
+    if (mid.dtype != x.dtype || mid.n != x.n || mid.c != x.c || mid.h != geom.out_h || mid.w != geom.out_w) { set_error("interp %s: output shape / type mismatch", name.c_str()); return -1; }
+    if (crop) {
+        CropGeom cg;
+        why = crop_refusal_of(g, *crop, true, &cg);
+        if (why) { set_error("interp %s: %s", name.c_str(), why); return -1; }
+        if (x.dtype != TAMD_DT_UINT8 || crop->in[0] != n.out[0] || cg.start[1] != 0 || cg.out_dims[1] != x.c || y.is_view || y.dtype != x.dtype) {
+            set_error("interp %s: this Crop does not run inside the Interp's launch", name.c_str());
+            return -1;
+        }
+        iy = std::vector<int>(iy.begin() + cg.start[2], iy.begin() + cg.start[2] + cg.out_dims[2]);      // (inside the vectors: crop_refusal's box check)
+        ix = std::vector<int>(ix.begin() + cg.start[3], ix.begin() + cg.start[3] + cg.out_dims[3]);
+    }
     std::vector<unsigned> table(64);
-    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], (unsigned char*)table.data())) {
-        set_error("interp %s: not supported on the device for data type %d", n.name.c_str(), x.dtype);
+    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], mid.scales[0], mid.zps.empty() ? 0 : mid.zps[0], (unsigned char*)table.data())) {
+        set_error("interp %s: not supported on the device for data type %d", name.c_str(), x.dtype);
         return -1;
     }
     int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
@@ -239,7 +254,11 @@ int plan_interp(tamd_graph* g, HNode& n, std::vector<Step>* out)
         a.iy = diy; a.ix = dix; a.table = dtable;
         a.identity = 1;
         for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
-        out->push_back(make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+        out->push_back(make_step(name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    }
+    if (crop) {
+        if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+        g->fused_away[n.out[0]] = 1;                         // the up-sampled map only exists inside the launch
     }
     return 0;
 }
@@ -539,6 +558,135 @@ int plan_transpose(tamd_graph* g, HNode& n, int view_src, std::vector<Step>* out
     a.form = pin >= 0 && transpose_form_legal(a, pin) ? pin : transpose_default_form(a);
     out->push_back(make_step(node, transpose_kernel_name(a.form), 0, 2.0 * (double)y.elems(), [a](hipStream_t st) { return launch_transpose(a, st); }, {access_of(s)},
                              {access_of(y)}, false));
+    return 0;
+}
+
+// ---- Crop of a uint8 graph.  Everything the reference decides for the node is decided by crop_refusal (node_rules.h): the form and
+// the box.  The output is a box of the data's RAW bytes (crop_ref.c:147-253 reads no quantisation parameter), so the node alone is the
+// identity form of slice_u8; behind a nearest Interp it is a shift of that launch's index vectors (plan_interp); and in front of a
+// same-shape Eltwise the three nodes are one topdown_u8 launch.  Input 1 gives its shape and nothing else: no launch reads it
+const char* crop_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, CropGeom* geom)
+{
+    if (n.in.size() != 2 || n.out.empty()) return "Crop takes two inputs: the data and the tensor whose shape it takes";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& like = g->tensors[n.in[1]];
+    const HTensor& y = g->tensors[n.out[0]];
+    return crop_refusal(&n.p.crop, x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), (int)like.dims.size(),
+                        like.dims.data(), y.scales.size(), (int)y.dims.size(), check_out ? y.dims.data() : nullptr, geom);
+}
+
+int crop_interp_producer(const tamd_graph* g, size_t ci)
+{
+    const HNode& c = g->nodes[ci];
+    CropGeom cg;
+    if (!tamd_pin_int("crop_chain", 1) || c.op != TAMD_OP_CROP || crop_refusal_of(g, c, true, &cg)) return -1;
+    const int mid = c.in[0];
+    const HTensor& t = g->tensors[mid];
+    if (t.is_view || count_consumers(g, mid) != 1) return -1;      // (a graph output counts as a consumer)
+    if (cg.start[1] != 0 || cg.out_dims[1] != t.dims[1] || g->tensors[c.out[0]].is_view) return -1;      // the box cuts no channels
+    for (size_t pj = 0; pj < ci; pj++) {
+        const HNode& p = g->nodes[pj];
+        if (p.out.size() != 1 || p.out[0] != mid) continue;
+        if (p.op != TAMD_OP_INTERP || p.in.empty()) return -1;
+        const HTensor& x = g->tensors[p.in[0]];
+        InterpGeom geom;
+        std::vector<int> iy, ix;
+        if (x.is_view || interp_refusal(&p.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), t.scales.size(), &geom, &iy, &ix)) return -1;
+        if (t.dims.size() != 4 || t.dims[0] != x.dims[0] || t.dims[1] != x.dims[1] || t.dims[2] != geom.out_h || t.dims[3] != geom.out_w) return -1;
+        return (int)pj;
+    }
+    return -1;
+}
+
+int crop_topdown_next(const tamd_graph* g, size_t ci)
+{
+    const HNode& c = g->nodes[ci];
+    if (!tamd_pin_int("topdown", 0) || crop_interp_producer(g, ci) < 0) return -1;      // opt-in: it did not beat the chain + eltwise_u8 (profiles/crop_topdown.txt)
+    const int cut = c.out[0];
+    if (count_consumers(g, cut) != 1) return -1;                   // (a graph output counts as a consumer)
+    for (size_t ej = ci + 1; ej < g->nodes.size(); ej++) {
+        const HNode& e = g->nodes[ej];
+        bool reads = false;
+        for (int i : e.in) reads = reads || i == cut;
+        if (!reads) continue;
+        int gated = -1;
+        if (e.op != TAMD_OP_ELTWISE || e.out.size() != 1 || eltwise_refusal_of(g, e, &gated) || gated >= 0) return -1;
+        const HTensor& lat = g->tensors[e.in[e.in[0] == cut ? 1 : 0]];
+        const HTensor& y = g->tensors[e.out[0]];
+        if (lat.is_view || y.is_view || lat.dims != g->tensors[cut].dims || y.dims != lat.dims || lat.scales.size() != 1 || y.scales.size() != 1) return -1;
+        return (int)ej;
+    }
+    return -1;
+}
+
+int plan_crop_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    CropGeom cg;
+    const char* why = crop_refusal_of(g, n, true, &cg);
+    if (why) { set_error("crop %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("crop %s on a concat view is not supported in a uint8 graph", n.name.c_str()); return -1; }
+    if (y.dtype != x.dtype) { set_error("crop %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    SliceU8Args a{};
+    for (int i = 0; i < 4; i++) { a.in_dims[i] = x.dims[i]; a.out_dims[i] = cg.out_dims[i]; a.start[i] = cg.start[i]; a.step[i] = 1; }
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = nullptr;
+    a.identity = 1;                                          // raw bytes, whatever the two tensors' parameters
+    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+    a.w2 = 0;
+    out->push_back(make_step(n.name, "slice_u8", 0, 2.0 * (double)y.elems(), [a](hipStream_t s) { return launch_slice_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
+int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out)
+{
+    const std::string node = in.name + "+" + cn.name + "+" + n.name;
+    HTensor& x = g->tensors[in.in[0]];
+    HTensor& mid = g->tensors[in.out[0]];
+    HTensor& cut = g->tensors[cn.out[0]];
+    const int u_first = n.in[0] == cn.out[0] ? 1 : 0;
+    HTensor& lat = g->tensors[n.in[u_first ? 1 : 0]];
+    HTensor& y = g->tensors[n.out[0]];
+    InterpGeom geom;
+    std::vector<int> iy, ix;
+    CropGeom cg;
+    int gated = -1;
+    const char* why = interp_refusal(&in.p.interp, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), mid.scales.size(), &geom, &iy, &ix);
+    if (!why) why = crop_refusal_of(g, cn, true, &cg);
+    if (!why) why = eltwise_refusal_of(g, n, &gated);
+    if (why) { set_error("topdown %s: %s", node.c_str(), why); return -1; }
+    if (x.dtype != TAMD_DT_UINT8 || gated >= 0 || cn.in[0] != in.out[0] || mid.dims.size() != 4 || mid.dims[2] != geom.out_h || mid.dims[3] != geom.out_w || cg.start[1] != 0
+        || cg.out_dims[1] != x.dims[1] || cg.out_dims[0] != x.dims[0] || lat.dims != cut.dims || y.dims != cut.dims || x.is_view || lat.is_view || y.is_view || !x.nchw_raw
+        || !lat.nchw_raw || !y.nchw_raw || lat.dtype != x.dtype || y.dtype != x.dtype) {
+        set_error("topdown %s: the three nodes do not run as one launch", node.c_str());
+        return -1;
+    }
+    iy = std::vector<int>(iy.begin() + cg.start[2], iy.begin() + cg.start[2] + cg.out_dims[2]);          // (inside the vectors: crop_refusal's box check)
+    ix = std::vector<int>(ix.begin() + cg.start[3], ix.begin() + cg.start[3] + cg.out_dims[3]);
+    for (int v : iy) if (v < 0 || v >= x.dims[2]) { set_error("topdown %s: a source row leaves the input", node.c_str()); return -1; }
+    for (int v : ix) if (v < 0 || v >= x.dims[3]) { set_error("topdown %s: a source column leaves the input", node.c_str()); return -1; }
+    std::vector<unsigned> table(64);
+    if (tamd_interp_table(x.dtype, x.scales[0], x.zps.empty() ? 0 : x.zps[0], mid.scales[0], mid.zps.empty() ? 0 : mid.zps[0], (unsigned char*)table.data())) {
+        set_error("topdown %s: not supported on the device for data type %d", node.c_str(), x.dtype);
+        return -1;
+    }
+    int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, iy, &diy) || upload(g, ix, &dix) || upload(g, table, &dtable)) return -1;
+    TopdownU8Args a{};
+    a.small = (const uint8_t*)x.dptr; a.lat = (const uint8_t*)lat.dptr; a.y = (uint8_t*)y.dptr;
+    a.planes = (long)x.dims[0] * x.dims[1]; a.H = x.dims[2]; a.W = x.dims[3]; a.OH = cg.out_dims[2]; a.OW = cg.out_dims[3];
+    a.iy = diy; a.ix = dix; a.table = dtable;
+    a.identity = 1;
+    for (int b = 0; b < 256; b++) a.identity &= ((const unsigned char*)table.data())[b] == b;
+    a.type = n.p.elt.type; a.u_first = u_first;
+    a.su = cut.scales[0]; a.zu = cut.zps.empty() ? 0 : cut.zps[0];                 // the Eltwise reads the Crop's output tensor: ITS parameters
+    a.sl = lat.scales[0]; a.zl = lat.zps.empty() ? 0 : lat.zps[0];
+    a.out_scale = y.scales[0]; a.out_zp = y.zps.empty() ? 0 : y.zps[0];
+    out->push_back(make_step(node, "topdown_u8", 0, 2.0 * (double)y.elems() + (double)x.elems(), [a](hipStream_t s) { return launch_topdown_u8(a, s); },
+                             {access_of(x), access_of(lat)}, {access_of(y)}, false));
+    if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+    g->fused_away[in.out[0]] = 1;                            // neither the up-sampled map nor its cut is ever written
+    g->fused_away[cn.out[0]] = 1;
     return 0;
 }
 

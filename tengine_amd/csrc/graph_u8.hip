@@ -892,6 +892,18 @@ int plan_u8(tamd_graph* g)
         const int nj = slice_chain_next(g, si);
         if (nj > (int)si && !fused[nj]) { slice_next[si] = nj + 1; fused[nj] = 1; }
     }
+    // Interp -> Crop as one launch at the Crop's position (crop_interp_producer): crop_interp[crop] = the Interp's node + 1, which is skipped;
+    // and, with TAMD_PIN=topdown=1, that chain -> Eltwise as one launch at the ELTWISE's position, where its other operand is made (crop_topdown_next):
+    // topdown[eltwise] = the Crop's node + 1, which is skipped too
+    std::vector<int> crop_interp(g->nodes.size(), 0), topdown(g->nodes.size(), 0);
+    for (size_t ci = 0; ci < g->nodes.size(); ci++) {
+        if (g->nodes[ci].op != TAMD_OP_CROP || fused[ci]) continue;
+        const int pj = crop_interp_producer(g, ci);
+        if (pj < 0 || fused[pj]) continue;
+        crop_interp[ci] = pj + 1; fused[pj] = 1;
+        const int ej = crop_topdown_next(g, ci);
+        if (ej > (int)ci && !fused[ej] && !gate_lut[ej] && !topdown[ej]) { topdown[ej] = (int)ci + 1; fused[ci] = 1; }
+    }
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (fused[ni]) continue;
@@ -913,13 +925,23 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
         case TAMD_OP_SLICE: rc = plan_slice_u8(g, n, slice_next[ni] - 1, &out); break;      // one slice_u8 launch, the Slice behind it inside
         case TAMD_OP_TRANSPOSE: rc = plan_transpose(g, n, -1, &out); break;      // one launch; the Reshapes around it are views
+        case TAMD_OP_CROP:                                      // alone: slice_u8 over the box; behind a nearest Interp: that launch, shifted
+            rc = crop_interp[ni] ? plan_interp(g, g->nodes[crop_interp[ni] - 1], &out, &n) : plan_crop_u8(g, n, &out);
+            break;
         case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;
         case TAMD_OP_PRIORBOX: rc = plan_priorbox_u8(g, n, x, y); break;
         case TAMD_OP_CONCAT: rc = plan_concat_u8(g, n, perm_src, &out); break;
-        case TAMD_OP_ELTWISE: rc = plan_eltwise_u8(g, n, gate_lut[ni] - 1, &out); break;
+        case TAMD_OP_ELTWISE:
+            if (topdown[ni]) {                                  // Interp -> Crop -> this node: one topdown_u8 launch
+                HNode& cn = g->nodes[topdown[ni] - 1];
+                rc = plan_topdown_u8(g, g->nodes[crop_interp[topdown[ni] - 1] - 1], cn, n, &out);
+            } else {
+                rc = plan_eltwise_u8(g, n, gate_lut[ni] - 1, &out);
+            }
+            break;
         default:
             set_error("op %d (%s) is not supported on the device for uint8", n.op, n.name.c_str());
             rc = -1;

@@ -381,6 +381,22 @@ struct TransposeArgs {
 };
 enum { kTransposeGather = 0, kTransposeRows = 1, kTransposeTile = 2 };
 
+// The top-down merge of a feature pyramid in a uint8 graph, nearest Interp -> Crop -> same-shape Eltwise, as one launch (topdown.hip).
+// All three tensors dense NCHW; lat and y have the output's dims (N, C, OH, OW) and are 16-byte aligned.  Per output byte
+//   u = table[small[n][c][iy[h]][ix[w]]]          (the Interp's byte map; iy / ix: its index vectors, shifted and cut by the Crop's box)
+//   y = requant(deq(u; su, zu) op deq(lat; sl, zl))  with the operands in the node's order (u_first), the chain of eltwise_u8_k
+struct TopdownU8Args {
+    const uint8_t* small; const uint8_t* lat; uint8_t* y;
+    long planes;                   // N * C
+    int H, W, OH, OW;              // the small map, the output map; every iy[h] < H, ix[w] < W (the planner checks the tables it uploads)
+    const int* iy; const int* ix;  // [OH], [OW]
+    const unsigned* table;         // [64]: the Interp's 256-byte map as it lies
+    int identity;                  // the map is the identity: no lookups
+    int type, u_first;             // ELT_PROD 0, SUM 2, SUB 4, MAX 6; 1: the cropped operand is the Eltwise's input 0
+    float su, sl, out_scale;       // u is dequantised with the CROP OUTPUT's parameters (the Eltwise reads that tensor), lat with its own
+    int zu, zl, out_zp;
+};
+
 // PReLU of a quantised graph (prelu.hip; the host truth: prelu_tables.cc)
 struct PreluI8Args {       // NHWC int8, x and y of one pixel stride: y = requant(x < 0 ? x * slope[c] : x), the chain of relu_i8 per channel
     const int8_t* x; int8_t* y;
@@ -543,6 +559,7 @@ hipError_t launch_chan_map_i8(const ChanMapI8Args& a, hipStream_t s);
 hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
 hipError_t launch_slice_u8(const SliceU8Args& a, hipStream_t s);
+hipError_t launch_topdown_u8(const TopdownU8Args& a, hipStream_t s);
 // which forms a geometry is legal in, and the default among them (transpose.hip: the one place it is decided)
 bool transpose_form_legal(const TransposeArgs& a, int form);
 int transpose_default_form(const TransposeArgs& a);

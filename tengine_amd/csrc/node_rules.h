@@ -299,6 +299,55 @@ inline const char* transpose_refusal(const tamd_transpose_param* p, int dtype, i
     return nullptr;
 }
 
+// Crop: the uint8 kernel of the reference (crop_ref.c:147-253).  There is no int8 kernel (run() writes nothing), and fp32 graphs keep the
+// node on the CPU device
+inline bool crop_on_device(int dtype) { return dtype == TAMD_DT_UINT8; }
+// what crop_refusal resolves for its callers: the box of the data tensor that the output is, on N, C, H, W
+struct CropGeom {
+    int start[4], out_dims[4];
+};
+// One Crop node: nullptr when the device runs it (*geom resolved; may be null), else the reason.  x: input 0, the data; like: input 1, of
+// which only the shape is read (crop.c:37).  out_dims: the output's dims where the caller has them (null: not checked).  The bytes are
+// the data's own: no quantisation VALUE of either tensor is read, only that both carry one pair.
+//  - num_args 1 (the centre crop): crop.c:37 takes input 1 unconditionally, and such a node has none
+//  - any other flag, axis or num_args: ref_crop_uint8 has no branch for it and writes nothing
+//  - a negative offset, or a box that leaves the data on any axis: the reference reads out of bounds (the caffe form has no guard at all;
+//    the MXNet guard offset + out <= in, crop_ref.c:190, fails silently and leaves the output unwritten; neither form looks at C or N)
+inline const char* crop_refusal(const tamd_crop_param* p, int dtype, int input_num, int x_dim_num, const int* x_dims, bool x_const, size_t x_quant, int like_dim_num,
+                                const int* like_dims, size_t out_quant, int out_dim_num, const int* out_dims, CropGeom* geom)
+{
+    if (!p) return "Crop needs its parameter";
+    if (!crop_on_device(dtype)) return "Crop runs on the device in uint8 graphs only";
+    if (p->flag == 1 && p->num_args == 1) return "the centre crop (MXNet form, num_args 1) does not run on the device";
+    if (p->flag != 0 && p->flag != 1) return "Crop: a flag other than 0 (caffe) and 1 (MXNet) has no kernel in the reference";
+    if (p->flag == 1 && p->num_args != 2) return "Crop: the MXNet form runs with num_args 2 only";
+    if (p->flag == 0 && p->axis != 1 && p->axis != 2) return "Crop: the caffe form runs with axis 1 or 2 only";
+    if (input_num != 2) return "Crop takes two inputs: the data and the tensor whose shape it takes";
+    if (x_dim_num != 4 || like_dim_num != 4) return "Crop runs on the device on 4-D tensors only";
+    if (x_const) return "Crop: the data input must not be a constant";
+    if (x_quant != 1 || out_quant != 1) return "Crop needs per-tensor quant params on the data and the output";
+    CropGeom cg;
+    cg.start[0] = 0;
+    cg.start[1] = p->flag == 0 && p->axis == 1 ? p->offset_c : 0;
+    cg.start[2] = p->offset_h;
+    cg.start[3] = p->offset_w;
+    for (int i = 0; i < 4; i++) {
+        cg.out_dims[i] = like_dims[i];                            // crop.c:70-73: N and C of input 1 too
+        if (x_dims[i] < 1 || like_dims[i] < 1) return "Crop: every dimension must be at least 1";
+        if (cg.start[i] < 0) return "Crop: a negative offset does not run on the device";
+    }
+    if (like_dims[0] != x_dims[0]) return "Crop: the two inputs must have the same batch";
+    for (int i = 1; i < 4; i++)
+        if ((long)cg.start[i] + (long)cg.out_dims[i] > (long)x_dims[i]) return "Crop: the box leaves the data tensor";
+    if (out_dims) {
+        if (out_dim_num != 4) return "Crop: the output does not have the dims the reference infers";
+        for (int i = 0; i < 4; i++)
+            if (out_dims[i] != cg.out_dims[i]) return "Crop: the output does not have the dims the reference infers";
+    }
+    if (geom) *geom = cg;
+    return nullptr;
+}
+
 // PReLU: the two quantised kernels of the reference (prelu_ref.c; prelu.hip).  fp32 graphs keep the node on the CPU device
 inline bool prelu_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
 // One PReLU node: nullptr when the device runs it, else the reason.  input_num: the node's inputs ([data, slope]); slope_data: the

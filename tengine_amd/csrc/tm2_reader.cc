@@ -81,6 +81,7 @@ int map_op(uint32_t t)
     case 37: return TAMD_OP_SIGMOID;
     case 51: return TAMD_OP_UPSAMPLE;
     case 55: return TAMD_OP_SHUFFLECHANNEL;
+    case 56: return TAMD_OP_CROP;
     case 70: return TAMD_OP_HARDSWISH;
     case 71: return TAMD_OP_INTERP;
     case 77: return TAMD_OP_TRANSPOSE;
@@ -226,6 +227,14 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 if (!r.ok) break;
                 p.transpose.dim_num = (int)order.size();       // any length travels: transpose_refusal names the ones that do not run
                 for (size_t i = 0; i < order.size() && i < 8; i++) p.transpose.order[i] = (int)order[i];
+                break;
+            }
+            case TAMD_OP_CROP: {                               // TM2_CropParam :812-823 {num_args, offset_c, offset_h, offset_w, crop_h, crop_w,
+                tamd_crop_param& q = p.crop;                   // bool center_crop + 3 bytes of padding, axis, flag} (tm2_crop.c:42-61)
+                q.num_args = r.i32(po); q.offset_c = r.i32(po + 4); q.offset_h = r.i32(po + 8); q.offset_w = r.i32(po + 12);
+                q.crop_h = r.i32(po + 16); q.crop_w = r.i32(po + 20);
+                q.center_crop = (r.u32(po + 24) & 0xffu) != 0;  // one byte; the three behind it are whatever the writer's compiler left there
+                q.axis = r.i32(po + 28); q.flag = r.i32(po + 32);
                 break;
             }
             case TAMD_OP_PRIORBOX: {                           // TM2_PriorBoxParam :526-542 (tm2_priorbox.c:43-84)

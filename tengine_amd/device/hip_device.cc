@@ -45,6 +45,7 @@ extern "C" {
 #include "clip_param.h"
 #include "concat_param.h"
 #include "convolution_param.h"
+#include "crop_param.h"
 #include "eltwise_param.h"
 #include "fc_param.h"
 #include "flatten_param.h"
@@ -104,6 +105,9 @@ const OpRow kOps[] = {
     // head permute -- the two quantised kernels of the reference, rank 2 .. 6.  An fp32 graph keeps the node on the CPU device (which
     // orders: tamd_node_supported)
     {OP_TRANSPOSE, TAMD_OP_TRANSPOSE, true},
+    // the cut of RetinaFace's top-down pyramid (csrc/topdown.hip, csrc/slice.hip): a box of raw bytes in uint8 graphs.  The reference has no
+    // int8 kernel, and an fp32 graph keeps the node on the CPU device (which forms and boxes: tamd_node_supported)
+    {OP_CROP, TAMD_OP_CROP, true},
 };
 
 const OpRow* find_op(int op)
@@ -166,7 +170,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_transpose_param transpose;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_transpose_param transpose;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -230,6 +234,11 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
         s->slice.slice_point_num = p->slice_point_ ? get_vector_num(p->slice_point_) : 0;
         s->slice.begin_num = p->begin_ ? get_vector_num(p->begin_) : 0;
         s->slice.size_num = p->size_ ? get_vector_num(p->size_) : 0;
+        break;
+    }
+    case TAMD_OP_CROP: {             // crop_param.h, field for field
+        const struct crop_param* p = (const struct crop_param*)n->op.param_mem;
+        s->crop = tamd_crop_param{p->num_args, p->offset_c, p->offset_h, p->offset_w, p->crop_h, p->crop_w, p->center_crop, p->axis, p->flag};
         break;
     }
     case TAMD_OP_TRANSPOSE: {        // the tr_shape vector inline; its length as it is (the first 8 entries: transpose_refusal names the lengths that do not run)

@@ -25,10 +25,12 @@ TT_VAR, TT_CONST, TT_INPUT = 1, 2, 3
 LAYOUT_NCHW = 0
 
 # tm2 operator type codes (tm2_format.h:157-264)
+CROP_FIELDS = ("num_args", "offset_c", "offset_h", "offset_w", "crop_h", "crop_w", "center_crop", "axis", "flag")      # crop_param.h
+
 OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
-    "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55,
+    "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55, "Crop": 56,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "Clip": 87, "Mish": 97,
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
@@ -186,6 +188,9 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
 
         return {"axis": axis, "slice_points": vi(vsp), "begins": vi(vbg), "sizes": vi(vsz), "iscaffe": iscaffe, "ismxnet": ismxnet,
                 "isonnx": isonnx, "begin": begin, "end": end, "step": step}
+    if op == "Crop":            # TM2_CropParam (tm2_format.h:812-823): six int32, a one-byte bool and three bytes of padding, two int32
+        v = struct.unpack_from("<6iB3x2i", b, off)
+        return dict(zip(CROP_FIELDS, v))
     if op == "Transpose":       # TM2_TransposeParam (tm2_format.h:929-932): {offset_tr_shape -> TM2_Vector_dims}
         voff = struct.unpack_from("<I", b, off)[0]
         n = struct.unpack_from("<I", b, voff)[0] if voff else 0
@@ -283,6 +288,9 @@ def write_tm2(g: Graph) -> bytes:
             vecs = [bl.vec_i32(q[k]) if q.get(k) else 0 for k in ("slice_points", "begins", "sizes")]
             pb = struct.pack("<i3I6i", q.get("axis", 1), vecs[0], vecs[1], vecs[2], q.get("iscaffe", 0), q.get("ismxnet", 0), q.get("isonnx", 1),
                              q.get("begin", 0), q.get("end", 0), q.get("step", 1))
+        elif n.op == "Crop":     # TM2_CropParam; the defaults are crop.c's init_op (axis 2, everything else 0)
+            q = n.params
+            pb = struct.pack("<6iB3x2i", *[int(q.get(k, 2 if k == "axis" else 0)) for k in CROP_FIELDS])
         elif n.op == "Transpose":  # TM2_TransposeParam {offset_tr_shape -> TM2_Vector_dims}; tr_shape None: TM2_NOT_SET, a node no loader accepts
             order = n.params.get("tr_shape")
             pb = struct.pack("<I", bl.vec_i32(order) if order is not None else 0)
