@@ -55,8 +55,15 @@ enum {
     TAMD_OP_ELTWISE = 6, /* param: tamd_eltwise_param; PROD 0 / SUM 2 / SUB 4 / MAX 6 of two tensors of one shape in every graph type; in
                           * int8 / uint8 graphs also the channel gate of a Squeeze-and-Excitation block, x (N,C,H,W) op gate (N,C,1,1) for
                           * PROD / SUM / SUB -- always x op gate, the gate may be listed first at batch 1 (eltwise_ref.c); the output has
-                          * x's dims.  MAX with a gate, a gate of another shape, one-element operands and the scalar / unary types are
-                          * refused by name (tamd_node_supported answers 0) */
+                          * x's dims.  In int8 / uint8 graphs also, by a 256-entry table and one lut_u8 launch (tamd_eltwise_table):
+                          *  - the scalar form, inputs [x, c]: x a 4-D activation, c a CONSTANT of one element listed second (uint8 graphs:
+                          *    a uint8 or an fp32 constant; int8 graphs: an int8 one); PROD 0, PROD_SCALAR 1, SUM 2, SUB 4, SUB_SCALAR 5,
+                          *    MIN_SCALAR 8, DIV 10
+                          *  - the unary form, one input, 4-D: RSQRT 7, LOG 11, EXP 12, SQRT 13, FLOOR 14, SQUARE 15, POWER 17 (shift, scale,
+                          *    power)
+                          * MAX with a gate or a scalar, a gate of another shape, a one-element operand that is no constant or is listed
+                          * first, SUM_SCALAR 3, LAST 9, POW 16, and a node whose table holds a value the reference cannot convert to int
+                          * are refused by name (tamd_node_supported answers 0) */
     TAMD_OP_CONCAT = 7,  /* param: tamd_concat_param */
     TAMD_OP_DROPOUT = 8, /* identity */
     TAMD_OP_UPSAMPLE = 9,/* param: tamd_upsample_param; nearest, an integer factor >= 1; fp32 / uint8 graphs, and int8 graphs for a 4-D
@@ -115,6 +122,15 @@ enum {
      * offset and a box that leaves the data tensor are refused by name; int8 graphs (no kernel in the reference) and fp32 graphs keep
      * the node on the CPU device */
     TAMD_OP_CROP = 30,
+    /* 31: reserved, never supported (like 21, 24, 27 and 29: tests/test_crop_cpu.py holds the code to that answer) */
+    /* the not-folded BatchNorm of an MXNet / insightface export -- fc1, the last node of mobilefacenets_benchmark.tmfile --, uint8 graphs:
+     * param tamd_batchnorm_param; inputs [x, gamma, beta, mean, var], the four statistics fp32 constants of C elements (caffe_flavor:
+     * only mean and var are read); x 2-D [N,C], 3-D [N,C,W] or 4-D [N,C,H,W] (batchnorm_ref.c:117-141).  The reference
+     * (batchnorm_kernel_ref_uint8.c:40-107) dequantises, computes x * s2[c] + s1[c] and requantises: a byte map per channel
+     * (tamd_batchnorm_table), applied by chan_lut_u8 or, on large planes, by prelu_u8's per-plane form.  int8 graphs (no kernel in the
+     * reference), fp32 graphs, another rank, a statistic that is no fp32 constant of C elements and a channel whose table is not
+     * finite are refused by name */
+    TAMD_OP_BATCHNORM = 32,
     TAMD_OP_NUM
 };
 
@@ -138,6 +154,8 @@ typedef struct tamd_pool_param {
 } tamd_pool_param;
 
 typedef struct tamd_relu_param { float negative_slope; } tamd_relu_param;   /* relu_param.h */
+/* field meaning == struct batchnorm_param (batchnorm_param.h) */
+typedef struct tamd_batchnorm_param { float rescale_factor, eps; int caffe_flavor; } tamd_batchnorm_param;
 typedef struct tamd_eltwise_param { int type; int caffe_flavor; float shift, power, scale; } tamd_eltwise_param;
 typedef struct tamd_concat_param { int axis; } tamd_concat_param;
 typedef struct tamd_upsample_param { float scale; } tamd_upsample_param;
@@ -284,6 +302,31 @@ TAMD_API int tamd_node_supported(const tamd_node_desc* node, const tamd_tensor_d
  * the device does not run */
 TAMD_API int tamd_lut_table(int op, int dtype, const void* param, float in_scale, int in_zp, float out_scale, int out_zp,
                             unsigned char table[256]);
+/* the byte maps of an Eltwise node with a constant one-element second operand, or with no second operand (csrc/lut_tables.cc; no GPU
+ * needed), dtype TAMD_DT_INT8 | TAMD_DT_UINT8 (eltwise_ref.c:589-847 | :311-587).
+ * tamd_eltwise_table: table[raw input byte] = the raw output byte: the byte dequantised (uint8 (u - zero) * scale, int8 (float)q * scale),
+ * the operator's line against `scalar` (the types that read one: PROD 0, PROD_SCALAR 1, SUM 2, SUB 4, SUB_SCALAR 5, MIN_SCALAR 8,
+ * DIV 10) or alone (RSQRT 7, LOG 11, EXP 12, SQRT 13, FLOOR 14, SQUARE 15, POWER 17: pow(shift + scale * x, power) of `param`, which the
+ * other types do not read), round(f / out_scale) (+ out_zp) clamped to -127 .. 127 | 0 .. 255.  0; -1 for another type or dtype (or
+ * POWER without param); -2 when one of the 256 values before the clamp is NaN, infinite or outside int -- RSQRT or LOG of a tensor whose
+ * zero-point byte is 0.0, a division by 0: the reference's conversion is undefined there and the node is refused.
+ * tamd_eltwise_scalar: the float the kernels make of the constant's first element: an fp32 constant as it is (uint8 graphs only), a
+ * uint8 one (u - zp) * scale, an int8 one (float)q * scale.  0, or -1 for another type.
+ * tamd_eltwise_pair: the output byte (0 .. 255, int8 as its bit pattern) of the same-shape PROD 0 / SUM 2 / SUB 4 / MAX 6 on ONE pair of
+ * bytes; -1 for another type or dtype, -2 where the conversion is undefined */
+TAMD_API int tamd_eltwise_table(int type, int dtype, const tamd_eltwise_param* param, float scalar, float in_scale, int in_zp,
+                                float out_scale, int out_zp, unsigned char table[256]);
+TAMD_API int tamd_eltwise_scalar(int const_dtype, const void* value, float scale, int zp, float* scalar);
+TAMD_API int tamd_eltwise_pair(int type, int dtype, unsigned char a, float a_scale, int a_zp, unsigned char b, float b_scale, int b_zp,
+                               float out_scale, int out_zp);
+/* the byte map of ONE channel of a uint8 BatchNorm (csrc/lut_tables.cc; no GPU needed), batchnorm_ref.c:76-86 and
+ * batchnorm_kernel_ref_uint8.c:57-101 as the built reference's compiler contracts them: rescale = rescale_factor ? 1 / rescale_factor : 0;
+ * scale_var_inv = 1 / sqrtf(fmaf(var, rescale, eps)); scale_mean = -mean * (rescale * scale_var_inv); s1 = scale_mean, s2 =
+ * scale_var_inv, unless caffe_flavor: s1 = fmaf(gamma, scale_mean, beta), s2 = gamma * scale_var_inv; table[b] = (int)roundf(fmaf(((float)b
+ * - (float)in_zp) * in_scale, s2, s1) / out_scale + (float)out_zp) clamped to 0 .. 255.  0; -1 without param or table; -2 when s1, s2 or
+ * one of the 256 values before the clamp is not finite or lies outside int (the node is refused) */
+TAMD_API int tamd_batchnorm_table(const tamd_batchnorm_param* param, float gamma, float beta, float mean, float var, float in_scale, int in_zp,
+                                  float out_scale, int out_zp, unsigned char table[256]);
 /* the two host-built operands of a nearest Interp node (csrc/interp_tables.cc; no GPU needed).
  * tamd_interp_table: table[b] = the output byte for input byte b between tensors of these quantisation parameters (interp_ref.c:269-272,
  * 346-354: int8 saturates at +-127, so -128 comes out as -127 even between equal scales; :378-381, 455-463: uint8 at 0 .. 255).  0, or
@@ -430,6 +473,14 @@ TAMD_API int tamd_graph_profile(tamd_graph* g, int iters, tamd_kernel_info* out,
 TAMD_API int tamd_graph_read_tensor(tamd_graph* g, int tensor_idx, void* host_nchw, size_t bytes);
 TAMD_API int tamd_graph_tensor_num(const tamd_graph* g);
 TAMD_API int tamd_graph_tensor_desc(const tamd_graph* g, int tensor_idx, int* dims8, int* dtype);
+/* the byte-pure chain that starts at table node `node` (index in the order the nodes were added) of a loaded int8 / uint8 graph, as the
+ * planners look for it before their own layout conditions: table nodes (Sigmoid / Clip / HardSwish / Mish, scalar and unary Eltwise)
+ * and same-shape Eltwise nodes whose output byte is a function of ONE byte of the first node's input, none of whose intermediate
+ * tensors has a reader outside the chain or is a graph output.  Such a chain runs as one lut_u8 launch.  nodes[0 .. min(count, cap)): the
+ * members in node order; table[b]: the byte of the last member's output where the source holds byte b -- every node evaluated with
+ * the reference's arithmetic (tamd_lut_table, tamd_eltwise_table, tamd_eltwise_pair).  The member count (>= 2); 0: no chain starts
+ * there (or TAMD_PIN=bytemap_chain=0); -1: bad arguments.  Needs no GPU and no prerun */
+TAMD_API int tamd_graph_bytemap_chain(const tamd_graph* g, int node, int* nodes, int cap, unsigned char table[256]);
 
 TAMD_API void tamd_graph_destroy(tamd_graph* g);
 

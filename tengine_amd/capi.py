@@ -26,14 +26,14 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_eltwise_table", "tamd_eltwise_scalar", "tamd_eltwise_pair", "tamd_batchnorm_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
     "tamd_graph_set_input", "tamd_graph_set_output", "tamd_graph_run", "tamd_graph_run_async", "tamd_graph_wait", "tamd_graph_inflight", "tamd_graph_upload_inputs",
     "tamd_graph_launch", "tamd_graph_sync", "tamd_graph_direct_packets", "tamd_graph_direct_meta_packets", "tamd_graph_download_outputs", "tamd_graph_output_device",
     "tamd_graph_direct_timestamps", "tamd_graph_slot_timestamps", "tamd_graph_direct_packet_name", "tamd_graph_stream", "tamd_graph_time_launches", "tamd_graph_prerun_ms", "tamd_graph_kernel_num", "tamd_graph_profile",
-    "tamd_graph_read_tensor", "tamd_graph_tensor_num", "tamd_graph_tensor_desc", "tamd_graph_destroy",
+    "tamd_graph_read_tensor", "tamd_graph_tensor_num", "tamd_graph_tensor_desc", "tamd_graph_bytemap_chain", "tamd_graph_destroy",
 ]
 
 _lib = None
@@ -89,6 +89,12 @@ def lib():
             getattr(L, name).argtypes = args
         L.tamd_graph_destroy.restype = None
         L.tamd_lut_table.argtypes = [ci, ci, vp, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+        if hasattr(L, "tamd_eltwise_table"):      # (guarded like the slots: an older build has no Eltwise tables)
+            L.tamd_eltwise_table.argtypes = [ci, ci, vp, C.c_float, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+            L.tamd_eltwise_scalar.argtypes = [ci, vp, C.c_float, ci, C.POINTER(C.c_float)]
+            L.tamd_eltwise_pair.argtypes = [ci, ci, C.c_ubyte, C.c_float, ci, C.c_ubyte, C.c_float, ci, C.c_float, ci]
+            L.tamd_graph_bytemap_chain.argtypes = [vp, ci, C.POINTER(ci), ci, C.POINTER(C.c_ubyte)]
+            L.tamd_batchnorm_table.argtypes = [vp] + [C.c_float] * 5 + [ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
@@ -205,6 +211,65 @@ def lut_table(op, dtype, in_scale, in_zp, out_scale, out_zp, params=None):
     p = (C.c_float * 2)(*params) if params is not None else None
     rc = lib().tamd_lut_table(op, dtype, C.cast(p, C.c_void_p) if p is not None else None, in_scale, in_zp, out_scale, out_zp, tab)
     return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
+
+
+class EltwiseParam(C.Structure):        # tamd_eltwise_param
+    _fields_ = [("type", C.c_int), ("caffe_flavor", C.c_int), ("shift", C.c_float), ("power", C.c_float), ("scale", C.c_float)]
+
+
+def eltwise_scalar(const_dtype, value, scale=0.0, zp=0):
+    """tamd_eltwise_scalar(): the float the reference's quantised Eltwise kernels make of a one-element constant (a numpy scalar or array
+    of the constant's own type: float32 as it is, uint8 (u - zp) * scale, int8 q * scale); None for another type"""
+    v = np.ascontiguousarray(value).reshape(-1)[:1]
+    out = C.c_float()
+    rc = lib().tamd_eltwise_scalar(const_dtype, v.ctypes.data_as(C.c_void_p), scale, zp, C.byref(out))
+    return None if rc != 0 else out.value
+
+
+def eltwise_table(typ, dtype, scalar, in_scale, in_zp, out_scale, out_zp, shift=0.0, power=1.0, scale=1.0):
+    """tamd_eltwise_table(): (rc, the 256 output bytes) of an Eltwise node with a constant one-element second operand (`scalar`, already a
+    float: eltwise_scalar) or of a unary type (shift / power / scale: POWER 17 reads them).  rc 0; -1: no such (type, dtype) on the
+    device; -2: the table holds a value the reference does not define.  The bytes are None unless rc is 0.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    p = EltwiseParam(typ, 0, shift, power, scale)
+    rc = lib().tamd_eltwise_table(typ, dtype, C.cast(C.pointer(p), C.c_void_p), scalar, in_scale, in_zp, out_scale, out_zp, tab)
+    return rc, (np.frombuffer(tab, dtype=np.uint8).copy() if rc == 0 else None)
+
+
+class BatchNormParam(C.Structure):      # tamd_batchnorm_param
+    _fields_ = [("rescale_factor", C.c_float), ("eps", C.c_float), ("caffe_flavor", C.c_int)]
+
+
+def batchnorm_table(gamma, beta, mean, var, in_scale, in_zp, out_scale, out_zp, rescale_factor=1.0, eps=1e-5, caffe_flavor=0):
+    """tamd_batchnorm_table(): (rc, the 256 output bytes of ONE channel of a uint8 BatchNorm); rc -2: s1 / s2 or the table is not
+    finite.  The bytes are None unless rc is 0.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    p = BatchNormParam(rescale_factor, eps, caffe_flavor)
+    rc = lib().tamd_batchnorm_table(C.cast(C.pointer(p), C.c_void_p), gamma, beta, mean, var, in_scale, in_zp, out_scale, out_zp, tab)
+    return rc, (np.frombuffer(tab, dtype=np.uint8).copy() if rc == 0 else None)
+
+
+def eltwise_pair(typ, dtype, a, qa, b, qb, qo):
+    """tamd_eltwise_pair(): the output byte of the same-shape PROD / SUM / SUB / MAX on one pair of bytes (q*: (scale, zero point)); < 0
+    as the C function answers"""
+    return lib().tamd_eltwise_pair(typ, dtype, int(a) & 255, qa[0], int(qa[1]), int(b) & 255, qb[0], int(qb[1]), qo[0], int(qo[1]))
+
+
+def bytemap_chain(tm_bytes, node):
+    """tamd_graph_bytemap_chain() of the model's node `node` (its index in the file): (member node indices, the 256-byte table from the
+    chain's source tensor to its last tensor), or ([], None) where no chain starts.  Needs no GPU."""
+    L = lib()
+    h = L.tamd_graph_load_tm2(tm_bytes, len(tm_bytes))
+    if not h:
+        raise TamdError("load_tm2 failed: %s" % L.tamd_last_error().decode())
+    try:
+        nodes, tab = (C.c_int * 64)(), (C.c_ubyte * 256)()
+        n = L.tamd_graph_bytemap_chain(h, node, nodes, 64, tab)
+        if n < 0:
+            raise TamdError("bytemap_chain: bad arguments")
+        return (list(nodes[:n]), np.frombuffer(tab, dtype=np.uint8).copy()) if n else ([], None)
+    finally:
+        L.tamd_graph_destroy(h)
 
 
 def _check(rc, what):

@@ -56,6 +56,7 @@ union NodeParam {
     tamd_slice_param slice;
     tamd_transpose_param transpose;
     tamd_crop_param crop;
+    tamd_batchnorm_param bn;
 };
 
 struct HNode {
@@ -354,8 +355,32 @@ int plan_crop_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // Interp `in` -> Crop `cn` -> Eltwise `n` as ONE topdown_u8 launch (topdown.hip), planned at the Eltwise's position
 int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
-// same-shape form, else which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1)
-const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated);
+// same-shape form, 0 | 1 which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1), kEltScalar / kEltUnary the two
+// forms that run by table; table[256]: the byte map of those two (may be null)
+const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated, unsigned char* table = nullptr);
+// batchnorm_refusal (node_rules.h) asked of a node of this graph, payloads included: validate_graph and plan_batchnorm_u8.  tables (may be
+// null): the [C][64] dwords of the C byte maps
+const char* batchnorm_refusal_of(const tamd_graph* g, const HNode& n, std::vector<unsigned>* tables);
+// a BatchNorm node of a uint8 graph as ONE launch through its C byte maps: chan_lut_u8 (chan_lut.hip), or prelu_u8's per-plane form
+// (prelu.hip) on planes of at least kBnPlaneForm bytes; TAMD_PIN=bn_form=0 | 1 forces the first | the second
+int plan_batchnorm_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// the scalar and the unary Eltwise, int8 and uint8 graphs alike: one lut_u8 launch through tamd_eltwise_table's bytes
+int plan_eltwise_table(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// A byte-pure chain (graph_plan_maps.hip): nodes[] in node order, each a table node (Sigmoid / Clip / HardSwish / Mish, scalar or unary
+// Eltwise) behind `src` or a member, or a same-shape Eltwise whose operands are `src` or members, and each one that `last`, the last
+// member's output, depends on; table: the byte of `last` for every byte of `src`.  The outputs of all members but the last have no reader outside the chain and are no graph
+// outputs.
+struct ByteChain {
+    int src = -1, last = -1;
+    std::vector<int> nodes;
+    unsigned char table[256];
+};
+// the maximal chain of at least two nodes that starts at table node `ni`, false: none (or TAMD_PIN=bytemap_chain=0).  node_free(node):
+// the planner has not given the node to another launch; tensor_plain(tensor): it owns a whole buffer in the layout of its neighbours
+// (no view, no alias, not dense among NHWC tensors) -- what only a planner knows stays with that planner
+bool bytemap_chain_from(const tamd_graph* g, size_t ni, const std::function<bool(int)>& node_free, const std::function<bool(int)>& tensor_plain, ByteChain* c);
+// the chain as ONE lut_u8 launch from src to last, planned at the LAST member's position; the tensors between are fused away
+int plan_bytemap_chain(tamd_graph* g, const ByteChain& c, std::vector<Step>* out);
 // the byte-map node (Sigmoid / Clip / HardSwish / Mish) that produces the gate of the channel-gate Eltwise `e` and can run inside
 // its launch -- the gate has no other reader, is no graph output and no view, TAMD_PIN=gate_lut=0 is not set --, -1: none.  What
 // only a planner knows of its layout (int8: dense / view bookkeeping before the buffers exist) stays with that planner

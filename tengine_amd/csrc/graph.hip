@@ -84,6 +84,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_SLICE) return slice_on_device(dtype);        // the onnx form, uint8 (which forms and extents: tamd_node_supported)
     if (op == TAMD_OP_TRANSPOSE) return transpose_on_device(dtype);      // int8 / uint8 (which ranks and orders: tamd_node_supported)
     if (op == TAMD_OP_CROP) return crop_on_device(dtype);          // a box of raw bytes, uint8 (which forms and boxes: tamd_node_supported)
+    if (op == TAMD_OP_BATCHNORM) return batchnorm_on_device(dtype);  // a byte map per channel, uint8 (which ranks and statistics: tamd_node_supported)
     if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
@@ -133,14 +134,24 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         return 1;
     }
     case TAMD_OP_ELTWISE: {
-        if (n_in != 2 || !in) return 0;
+        if ((n_in != 1 && n_in != 2) || !in) return 0;
         int gated = -1;
-        if (eltwise_refusal((const tamd_eltwise_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, in[1].dim_num,
-                            in[1].dims, in[1].ttype == TAMD_TT_CONST, (size_t)in[1].quant_num, (size_t)out[0].quant_num, &gated))
+        const tamd_tensor_desc& b = in[n_in - 1];                 // (one input: unread)
+        // the values a scalar or unary form's table is built from, where the caller gave them: the scales and zero points of x and of
+        // the output, and the constant's first element
+        EltwiseValues v{};
+        const bool have_q = in[0].quant_num == 1 && in[0].scales && out[0].quant_num == 1 && out[0].scales && (b.dtype == TAMD_DT_FP32 || n_in == 1 || b.scales);
+        if (have_q) {
+            v.x_scale = in[0].scales[0]; v.x_zp = in[0].zero_points ? in[0].zero_points[0] : 0;
+            v.out_scale = out[0].scales[0]; v.out_zp = out[0].zero_points ? out[0].zero_points[0] : 0;
+            if (n_in == 2) { v.c_data = b.data; v.c_scale = b.scales ? b.scales[0] : 0.f; v.c_zp = b.zero_points ? b.zero_points[0] : 0; }
+        }
+        if (eltwise_refusal((const tamd_eltwise_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, b.dim_num,
+                            b.dims, b.ttype == TAMD_TT_CONST, (size_t)b.quant_num, (size_t)out[0].quant_num, &gated, b.dtype, have_q ? &v : nullptr))
             return 0;
         const tamd_tensor_desc& big = in[gated == 1 ? 1 : 0];     // eltwise.c infer_shape: the output has the dims of the operand with more elements
-        if (gated >= 0 && out[0].dim_num != big.dim_num) return 0;
-        for (int i = 0; gated >= 0 && i < big.dim_num; i++) if (out[0].dims[i] != big.dims[i]) return 0;
+        if (gated != kEltSame && out[0].dim_num != big.dim_num) return 0;
+        for (int i = 0; gated != kEltSame && i < big.dim_num; i++) if (out[0].dims[i] != big.dims[i]) return 0;
         return 1;
     }
     case TAMD_OP_CONCAT: {
@@ -244,6 +255,23 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
                             in[1].dims, (size_t)out[0].quant_num, out[0].dim_num, out[0].dims, nullptr)
                == nullptr;
     }
+    case TAMD_OP_BATCHNORM: {
+        if (n_in != 5 || !in) return 0;
+        BnStat st[4];
+        for (int k = 0; k < 4; k++) st[k] = BnStat{in[k + 1].dtype, in[k + 1].ttype == TAMD_TT_CONST, elems(in[k + 1]), (const float*)in[k + 1].data};
+        EltwiseValues v{};
+        const bool have_q = in[0].quant_num == 1 && in[0].scales && out[0].quant_num == 1 && out[0].scales;
+        if (have_q) {
+            v.x_scale = in[0].scales[0]; v.x_zp = in[0].zero_points ? in[0].zero_points[0] : 0;
+            v.out_scale = out[0].scales[0]; v.out_zp = out[0].zero_points ? out[0].zero_points[0] : 0;
+        }
+        if (batchnorm_refusal((const tamd_batchnorm_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                              (size_t)out[0].quant_num, st, have_q ? &v : nullptr, nullptr))
+            return 0;
+        if (out[0].dim_num != in[0].dim_num) return 0;
+        for (int i = 0; i < in[0].dim_num; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
+        return 1;
+    }
     case TAMD_OP_PRELU: {
         if (n_in < 2 || !in) return 0;
         if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
@@ -317,6 +345,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_SLICE: n.p.slice = *(const tamd_slice_param*)d->param; break;
         case TAMD_OP_TRANSPOSE: n.p.transpose = *(const tamd_transpose_param*)d->param; break;
         case TAMD_OP_CROP: n.p.crop = *(const tamd_crop_param*)d->param; break;
+        case TAMD_OP_BATCHNORM: n.p.bn = *(const tamd_batchnorm_param*)d->param; break;
         default: break;
         }
     }

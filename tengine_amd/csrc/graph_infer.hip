@@ -268,6 +268,7 @@ int infer_shapes(tamd_graph* g)
             y.dims.assign(cg.out_dims, cg.out_dims + 4);
             break;
         }
+        case TAMD_OP_BATCHNORM: y.dims = x.dims; y.dtype = x.dtype; break;      // batchnorm.c: the input's shape; the statistics are fp32, the data is not
         case TAMD_OP_PRELU: y.dims = x.dims; y.dtype = x.dtype; break;      // prelu.c: the input's shape; the type is the data's, not the fp16 slope's
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
@@ -362,6 +363,10 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_TRANSPOSE) {
             const char* why = transpose_refusal_of(g, n, true, nullptr, nullptr);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_BATCHNORM) {
+            const char* why = batchnorm_refusal_of(g, n, nullptr);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_PRELU) {

@@ -56,9 +56,13 @@ struct I8Layout {
     // tview[node]: a Transpose that reads a convolution-stack tensor THROUGH the Reshape in front of it (plan_dense: match_transpose_view),
     // node index of that Reshape tview[node] - 1; the Reshape has no launch and its output no buffer
     std::vector<int> tview;
+    // chain_at[node]: the last member of a byte-pure chain (match_bytemap_chains), which runs as one lut_u8 launch at this node's
+    // position: chains[chain_at[node] - 1]; the other members are fused[]
+    std::vector<int> chain_at;
+    std::vector<ByteChain> chains;
     I8Layout(size_t nt, size_t nn)
         : view_of(nt, -1), view_off(nt, 0), alias_of(nt, -1), perm_src(nt, -1), dense(nt, 0), flat_concat(nn, 0), fused(nn, 0), has_fuse(nn, 0), fuse_at(nn),
-          cat_shuffle(nn, 0), in_multi_cat(nt, 0), gate_lut(nn, 0), tview(nn, 0) {}
+          cat_shuffle(nn, 0), in_multi_cat(nt, 0), gate_lut(nn, 0), tview(nn, 0), chain_at(nn, 0) {}
 };
 
 // One planned launch, as plan_conv / plan_pool hand it out: the step, which form it took, and that form's kernel arguments for a

@@ -263,6 +263,22 @@ static int plan_input_staging(tamd_graph* g)
     return 0;
 }
 
+// byte-pure chains (bytemap_chain_from, graph_plan_maps.hip) as one lut_u8 launch each, at the LAST member's position: no member is
+// planned inside another launch already, and the source, the tensors between and the result are convolution-stack tensors with
+// buffers of their own.  In front of plan_buffers: the source is read at the last member's position
+static void match_bytemap_chains(tamd_graph* g, I8Layout& L)
+{
+    auto node_free = [&](int k) { return !L.fused[k] && !L.gate_lut[k] && !L.tview[k] && !L.cat_shuffle[k] && !L.chain_at[k]; };
+    auto tensor_plain = [&](int t) { return g->tensors[t].ttype != TAMD_TT_CONST && L.view_of[t] < 0 && L.alias_of[t] < 0 && !L.dense[t] && !L.in_multi_cat[t]; };
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        ByteChain c;
+        if (!bytemap_chain_from(g, ni, node_free, tensor_plain, &c)) continue;      // (a byte map inside its gate's launch is fused[]: no member)
+        for (size_t k = 0; k + 1 < c.nodes.size(); k++) L.fused[c.nodes[k]] = 1;
+        L.chains.push_back(c);
+        L.chain_at[c.nodes.back()] = (int)L.chains.size();
+    }
+}
+
 // ---- activation buffers.  Tensors whose lifetimes cannot overlap share device memory (tamd_options.keep_tensors = 0, the
 // default): a pass then touches a fraction of the bytes -- ResNet-50 at batch 32 owns 345 MB of activations one by one, more
 // than the 256 MB last-level cache, but never has more than ~65 MB of them alive.  Lifetime of a buffer, in node positions
@@ -326,6 +342,9 @@ static int plan_buffers(tamd_graph* g, I8Layout& L)
     // the input of a byte map that runs inside its channel-gate Eltwise's launch (match_gate_lut) is read at the ELTWISE's position
     for (int ni = 0; ni < NN; ni++)
         if (L.gate_lut[ni]) { const int r = root_of(g->nodes[L.gate_lut[ni] - 1].in[0]); death[r] = std::max(death[r], ni); }
+    // the source of a byte-pure chain (match_bytemap_chains) is read at the LAST member's position
+    for (int ni = 0; ni < NN; ni++)
+        if (L.chain_at[ni]) { const int r = root_of(L.chains[L.chain_at[ni] - 1].src); death[r] = std::max(death[r], ni); }
     // the source of a Reshape that its Transpose reads through (plan_dense: tview) is read at the TRANSPOSE's position
     for (int ni = 0; ni < NN; ni++)
         if (L.tview[ni]) { const int r = root_of(g->nodes[L.tview[ni] - 1].in[0]); death[r] = std::max(death[r], ni); }
@@ -402,7 +421,7 @@ static void scan_eltwise_fusion(tamd_graph* g, I8Layout& L)
     auto producer = [&](int t) { for (size_t i = 0; i < g->nodes.size(); i++) for (int o : g->nodes[i].out) if (o == t) return (int)i; return -1; };
     for (size_t ei = 0; ei < g->nodes.size() && !(fuse_env && atoi(fuse_env) == 0); ei++) {
         HNode& e = g->nodes[ei];
-        if (e.op != TAMD_OP_ELTWISE || e.in.size() != 2) continue;
+        if (e.op != TAMD_OP_ELTWISE || e.in.size() != 2 || L.fused[ei] || L.chain_at[ei]) continue;      // (a member of a byte-pure chain is taken)
         const int ty = e.p.elt.type;
         if (!eltwise_type_on_device(ty)) continue;
         HTensor& ta = g->tensors[e.in[0]];
@@ -823,7 +842,7 @@ static int plan_upsample(tamd_graph* g, I8Layout& L, HNode& n, std::vector<Step>
     return 0;
 }
 
-// the same-shape form: eltwise_i8 (+ the ReLU behind it); the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate, with the
+// the scalar and unary forms: one lut_u8 launch by table (plan_eltwise_table); the same-shape form: eltwise_i8 (+ the ReLU behind it); the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate, with the
 // byte map in front of the gate where match_gate_lut took it.  The ReLU-behind-Eltwise fusion is not extended to the gate form
 static int plan_eltwise(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>* out)
 {
@@ -831,6 +850,7 @@ static int plan_eltwise(tamd_graph* g, I8Layout& L, size_t ni, std::vector<Step>
     int gated = -1;
     const char* why = eltwise_refusal_of(g, n, &gated);
     if (why) { set_error("eltwise %s: %s", n.name.c_str(), why); return -1; }
+    if (gated == kEltScalar || gated == kEltUnary) return plan_eltwise_table(g, n, out);
     if (gated >= 0) return plan_chan_gate(g, n, gated, L.gate_lut[ni] - 1, out);
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
@@ -882,12 +902,17 @@ int plan_i8(tamd_graph* g)
     plan_split_views(g, L);
     if (plan_concat_views(g, L)) return -1;
     match_gate_lut(g, L);                    // (behind every pass that makes a tensor a view, in front of the one that shares buffers)
+    match_bytemap_chains(g, L);              // (the same place, and behind match_gate_lut: a byte map inside its gate's launch is no member)
     if (plan_input_staging(g) || plan_buffers(g, L) || resolve_views(g, L)) return -1;
     scan_eltwise_fusion(g, L);
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (L.fused[ni]) continue;
         std::vector<Step> out;
+        if (L.chain_at[ni]) {                // a byte-pure chain that ends here: one lut_u8 launch
+            if (plan_bytemap_chain(g, L.chains[L.chain_at[ni] - 1], &out) || append_steps(g, out)) return -1;
+            continue;
+        }
         Planned one;                 // FC / pooling: a single launch as plan_conv / plan_pool hand it to the fusers
         int r = 0;
         switch (n.op) {

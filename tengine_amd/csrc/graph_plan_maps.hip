@@ -1,5 +1,5 @@
 // The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
-// table (plan_lut), PReLU, nearest Interp, the uint8 Slice, the uint8 Crop (alone, inside the Interp's launch, or with both inside the Eltwise's), Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
+// table (plan_lut), the scalar and the unary Eltwise by table (plan_eltwise_table), byte-pure chains of such nodes as ONE table (bytemap_chain_from, plan_bytemap_chain), PReLU, nearest Interp, the uint8 Slice, the uint8 Crop (alone, inside the Interp's launch, or with both inside the Eltwise's), Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
 // plan_interp and plan_transpose serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
 // graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
 #include "graph.h"
@@ -39,6 +39,24 @@ static int lut_table_upload(tamd_graph* g, const HNode& n, unsigned** dtable)
     return upload(g, table, dtable);
 }
 
+// one lut_u8 launch from x to y through an uploaded table: an NHWC int8 tensor with padding lanes channel by channel, else a run of bytes
+static int lut_step(const std::string& node, const char* what, HTensor& x, HTensor& y, const unsigned* dtable, std::vector<Step>* out)
+{
+    if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, node.c_str()); return -1; }
+    LutArgs a{};
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
+    const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
+    if (x_nhwc != y_nhwc || (x_nhwc && (x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off))) { set_error("%s %s: input and output layouts differ", what, node.c_str()); return -1; }
+    if (x_nhwc) {
+        a.count = (size_t)x.n * x.h * x.w * x.cs;
+        if (x.cs != x.c) { a.C = x.c; a.cs = x.cs; }
+    } else {
+        a.count = x.elems();
+    }
+    out->push_back(make_step(node, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
 int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
 {
     HTensor& x = g->tensors[n.in[0]];
@@ -47,28 +65,214 @@ int plan_lut(tamd_graph* g, HNode& n, std::vector<Step>* out)
     if (x.is_view || y.is_view) { set_error("%s %s on a concat view is not supported", what, n.name.c_str()); return -1; }
     unsigned* dtable = nullptr;
     if (lut_table_upload(g, n, &dtable)) return -1;
-    LutArgs a{};
-    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = dtable;
-    const bool x_nhwc = !x.nchw_raw && x.cs > 0, y_nhwc = !y.nchw_raw && y.cs > 0;
-    if (x_nhwc != y_nhwc || (x_nhwc && (x.cs != y.cs || x.cs % 16 || x.c_off || y.c_off))) { set_error("%s %s: input and output layouts differ", what, n.name.c_str()); return -1; }
-    if (x_nhwc) {
-        a.count = (size_t)x.n * x.h * x.w * x.cs;
-        if (x.cs != x.c) { a.C = x.c; a.cs = x.cs; }
-    } else {
-        a.count = x.elems();
+    return lut_step(n.name, what, x, y, dtable, out);
+}
+
+const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated, unsigned char* table)
+{
+    *gated = -1;
+    if ((n.in.size() != 1 && n.in.size() != 2) || n.out.empty()) return "Eltwise runs on the device on two tensors";
+    const HTensor& a = g->tensors[n.in[0]];
+    const HTensor& b = g->tensors[n.in.back()];                    // (one input: unread)
+    const HTensor& y = g->tensors[n.out[0]];
+    EltwiseValues v{};
+    const bool have_q = a.scales.size() == 1 && y.scales.size() == 1;
+    if (have_q) {
+        v.x_scale = a.scales[0]; v.x_zp = a.zps.empty() ? 0 : a.zps[0];
+        v.out_scale = y.scales[0]; v.out_zp = y.zps.empty() ? 0 : y.zps[0];
+        if (n.in.size() == 2 && b.ttype == TAMD_TT_CONST && b.data.size() >= (size_t)esize(b.dtype)) {
+            v.c_data = b.data.data(); v.c_scale = b.scales.empty() ? 0.f : b.scales[0]; v.c_zp = b.zps.empty() ? 0 : b.zps[0];
+        }
     }
-    out->push_back(make_step(n.name, "lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_lut(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return eltwise_refusal(&n.p.elt, a.dtype, (int)n.in.size(), (int)a.dims.size(), a.dims.data(), a.ttype == TAMD_TT_CONST, a.scales.size(), (int)b.dims.size(), b.dims.data(),
+                           b.ttype == TAMD_TT_CONST, b.scales.size(), y.scales.size(), gated, b.dtype, have_q ? &v : nullptr, table);
+}
+
+// The scalar and the unary Eltwise (eltwise_refusal: kEltScalar, kEltUnary), int8 and uint8 graphs alike: the node's byte map through
+// one lut_u8 launch, exactly as plan_lut applies a Sigmoid's -- an NHWC int8 tensor with padding lanes channel by channel, its padding
+// written as zero, everything else a run of bytes.  The constant is read here, at prerun, and never again
+int plan_eltwise_table(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    int form = -1;
+    std::vector<unsigned> table(64);
+    const char* why = eltwise_refusal_of(g, n, &form, (unsigned char*)table.data());
+    if (why) { set_error("eltwise %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (form != kEltScalar && form != kEltUnary) { set_error("eltwise %s: not a scalar or unary form", n.name.c_str()); return -1; }
+    if (form == kEltScalar && g->tensors[n.in[1]].data.size() < (size_t)esize(g->tensors[n.in[1]].dtype)) { set_error("eltwise %s: the constant has no value", n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("eltwise %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    return lut_step(n.name, "eltwise", x, y, dtable, out);
+}
+
+// ---- uint8 BatchNorm: a byte map per channel ----
+const char* batchnorm_refusal_of(const tamd_graph* g, const HNode& n, std::vector<unsigned>* tables)
+{
+    if (n.in.size() != 5 || n.out.empty()) return "BatchNorm takes five inputs: the data, gamma, beta, mean and var";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    BnStat st[4];
+    for (int k = 0; k < 4; k++) {
+        const HTensor& t = g->tensors[n.in[k + 1]];
+        const bool whole = t.dtype == TAMD_DT_FP32 && t.data.size() >= t.elems() * 4;
+        st[k] = BnStat{t.dtype, t.ttype == TAMD_TT_CONST, t.elems(), whole ? (const float*)t.data.data() : nullptr};
+    }
+    EltwiseValues v{};
+    const bool have_q = x.scales.size() == 1 && y.scales.size() == 1;
+    if (have_q) { v.x_scale = x.scales[0]; v.x_zp = x.zps.empty() ? 0 : x.zps[0]; v.out_scale = y.scales[0]; v.out_zp = y.zps.empty() ? 0 : y.zps[0]; }
+    return batchnorm_refusal(&n.p.bn, x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), st,
+                             have_q ? &v : nullptr, tables);
+}
+
+// batchnorm_kernel_ref_uint8.c:40-107 is a function of one byte and its channel: the C tables are built at prerun and uploaded once.
+// Planes of at least kBnPlaneForm bytes go through prelu_u8's per-plane form (its arguments already are [C][64] tables), smaller ones --
+// the [N,C] output of a FullyConnected, H * W = 1, included -- through chan_lut_u8 (chan_lut.hip); TAMD_PIN=bn_form=0 | 1 forces
+// chan_lut_u8 | the per-plane form.  Measured (profiles/bytemap_chains.txt): chan_lut_u8 takes 3.0 us at every size up to 200 KB; the
+// per-plane form is behind it with the ranges apart on [32,128] (3.79 us) and on planes of 49 and 196 bytes (3.61, 3.67 us), and level
+// with it -- the ranges touch -- on planes of 784 and 3136 bytes and on [1,128]: it is ahead nowhere.  The threshold stands at the
+// first power of two above the sizes where chan_lut_u8 wins; from there on the choice is free as far as it was measured
+static const int kBnPlaneForm = 1024;
+int plan_batchnorm_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    std::vector<unsigned> tables;
+    const char* why = batchnorm_refusal_of(g, n, &tables);
+    if (why) { set_error("batchnorm %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("batchnorm %s on a concat view is not supported in a uint8 graph", n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("batchnorm %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const int C = x.dims[1];
+    if (tables.size() != (size_t)C * 64) { set_error("batchnorm %s: the statistics have no values", n.name.c_str()); return -1; }
+    size_t hw = 1;
+    for (size_t i = 2; i < x.dims.size(); i++) hw *= (size_t)x.dims[i];
+    if (hw > 0x7fffffffu) { set_error("batchnorm %s: a plane of more than 2^31 bytes", n.name.c_str()); return -1; }
+    unsigned* dtables = nullptr;
+    if (upload(g, tables, &dtables)) return -1;
+    const int form = tamd_pin_int("bn_form", hw >= (size_t)kBnPlaneForm ? 1 : 0);
+    if (form == 1) {
+        PreluU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.planes = (long)x.dims[0] * C; a.C = C; a.HW = (int)hw; a.tables = dtables; a.shared = 0;
+        out->push_back(make_step(n.name, "prelu_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_prelu_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    } else {
+        ChanLutU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.total = x.elems(); a.C = C; a.HW = (int)hw; a.tables = dtables;
+        out->push_back(make_step(n.name, "chan_lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_chan_lut_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    }
     return 0;
 }
 
-const char* eltwise_refusal_of(const tamd_graph* g, const HNode& n, int* gated)
+// ---- byte-pure chains as ONE table ----
+// A node whose output byte depends on ONE byte of a tensor S alone is byte-pure over S: a table node (Sigmoid / Clip / HardSwish / Mish,
+// the scalar and the unary Eltwise) that reads S or a byte-pure tensor, and a same-shape PROD / SUM / SUB / MAX whose operands are both
+// S or byte-pure over the same S -- x * sigmoid(x), x * clip(x + 3, 0, 6) / 6.  The value of every such tensor is known for each of the
+// 256 bytes S can hold, so the chain is evaluated node by node on the host -- table2[table1[b]], tamd_eltwise_pair(val_a[b], val_b[b]):
+// the reference's own arithmetic at every node -- and runs as one lut_u8 launch from S to the chain's last tensor; what lies between is
+// never written.  The bytes are the node-by-node bytes by construction.
+
+// the table of a table node between its two tensors; false: no table node, or one the device does not run alone either
+static bool byte_node_table(const tamd_graph* g, const HNode& n, unsigned char table[256])
 {
-    *gated = -1;
-    if (n.in.size() != 2 || n.out.empty()) return "Eltwise runs on the device on two tensors";
-    const HTensor& a = g->tensors[n.in[0]];
-    const HTensor& b = g->tensors[n.in[1]];
-    return eltwise_refusal(&n.p.elt, a.dtype, (int)n.in.size(), (int)a.dims.size(), a.dims.data(), a.ttype == TAMD_TT_CONST, a.scales.size(), (int)b.dims.size(), b.dims.data(),
-                           b.ttype == TAMD_TT_CONST, b.scales.size(), g->tensors[n.out[0]].scales.size(), gated);
+    if (n.in.empty() || n.out.size() != 1) return false;
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    if (x.ttype == TAMD_TT_CONST || x.scales.size() != 1 || y.scales.size() != 1 || x.dims != y.dims || x.dtype != y.dtype) return false;
+    if (is_lut_op(n.op)) {
+        if (n.in.size() != 1 || !lut_op_on_device(n.op, x.dtype) || !lut_rank_on_device(n.op, (int)x.dims.size())) return false;
+        const void* param = n.op == TAMD_OP_CLIP ? (const void*)&n.p.clip : n.op == TAMD_OP_HARDSWISH ? (const void*)&n.p.hardswish : nullptr;
+        return tamd_lut_table(n.op, x.dtype, param, x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0], table) == 0;
+    }
+    if (n.op != TAMD_OP_ELTWISE) return false;
+    int form = kEltSame;
+    return eltwise_refusal_of(g, n, &form, table) == nullptr && (form == kEltScalar || form == kEltUnary);
+}
+
+bool bytemap_chain_from(const tamd_graph* g, size_t ni, const std::function<bool(int)>& node_free, const std::function<bool(int)>& tensor_plain, ByteChain* c)
+{
+    if (!tamd_pin_int("bytemap_chain", 1)) return false;
+    const HNode& first = g->nodes[ni];
+    unsigned char tab[256];
+    if (!node_free((int)ni) || !byte_node_table(g, first, tab)) return false;
+    const int src = first.in[0];
+    if (!tensor_plain(src)) return false;
+    const int dtype = g->tensors[src].dtype;
+    if (dtype != TAMD_DT_INT8 && dtype != TAMD_DT_UINT8) return false;
+    // val[t][b]: the byte tensor t holds where S holds b
+    std::vector<std::vector<unsigned char>> val(g->tensors.size());
+    val[src].resize(256);
+    for (int b = 0; b < 256; b++) val[src][b] = (unsigned char)b;
+    std::vector<int> members;
+    auto q = [&](int t, float* s, int* z) { *s = g->tensors[t].scales[0]; *z = g->tensors[t].zps.empty() ? 0 : g->tensors[t].zps[0]; };
+    for (size_t nj = ni; nj < g->nodes.size(); nj++) {
+        const HNode& n = g->nodes[nj];
+        if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.in.empty() || n.out.size() != 1 || !node_free((int)nj) || !tensor_plain(n.out[0])) continue;
+        const int x = n.in[0], y = n.out[0];
+        std::vector<unsigned char> v(256);
+        if (!val[x].empty() && byte_node_table(g, n, tab)) {                                                   // a table node behind S or a member
+            for (int b = 0; b < 256; b++) v[b] = tab[val[x][b]];
+        } else if (n.op == TAMD_OP_ELTWISE && n.in.size() == 2 && !val[x].empty() && !val[n.in[1]].empty()) {
+            int form = 0;                                                                                     // same shape: both operands S or members
+            if (eltwise_refusal_of(g, n, &form) || form != kEltSame || g->tensors[x].dims != g->tensors[y].dims || g->tensors[y].scales.size() != 1) continue;
+            float sa, sb, so; int za, zb, zo;
+            q(x, &sa, &za); q(n.in[1], &sb, &zb); q(y, &so, &zo);
+            bool defined = true;
+            for (int b = 0; b < 256 && defined; b++) {
+                const int r = tamd_eltwise_pair(n.p.elt.type, dtype, val[x][b], sa, za, val[n.in[1]][b], sb, zb, so, zo);
+                defined = r >= 0;
+                v[b] = (unsigned char)r;
+            }
+            if (!defined) continue;
+        } else {
+            continue;
+        }
+        val[y] = v;
+        members.push_back((int)nj);
+    }
+    // The chain ends at ONE tensor, the last candidate's output if that works, else the one before, and so on: of the candidates it keeps
+    // those that this tensor depends on (a table node on another branch of S stays a node of its own), and what lies between must be
+    // the chain's alone -- an intermediate with a reader outside the set, or one that is a graph output, ends the set there
+    for (size_t t = members.size(); t-- > 1;) {
+        std::vector<char> in_set(g->nodes.size(), 0), needed(g->tensors.size(), 0);
+        std::vector<int> set;
+        needed[g->nodes[members[t]].out[0]] = 1;
+        for (size_t k = t + 1; k-- > 0;) {
+            const HNode& n = g->nodes[members[k]];
+            if (!needed[n.out[0]]) continue;
+            set.insert(set.begin(), members[k]);
+            in_set[members[k]] = 1;
+            for (int i : n.in) needed[i] = 1;
+        }
+        bool closed = set.size() >= 2 && set.front() == (int)ni;
+        for (size_t k = 0; closed && k + 1 < set.size(); k++) {
+            const int mid = g->nodes[set[k]].out[0];
+            for (auto& o : g->outputs) closed = closed && o.tensor != mid;
+            for (size_t nj = 0; closed && nj < g->nodes.size(); nj++)
+                if (!in_set[nj]) for (int i : g->nodes[nj].in) closed = closed && i != mid;
+        }
+        if (!closed) continue;
+        c->src = src; c->last = g->nodes[set.back()].out[0]; c->nodes = set;
+        memcpy(c->table, val[c->last].data(), 256);
+        return true;
+    }
+    return false;
+}
+
+int plan_bytemap_chain(tamd_graph* g, const ByteChain& c, std::vector<Step>* out)
+{
+    HTensor& x = g->tensors[c.src];
+    HTensor& y = g->tensors[c.last];
+    std::string node;
+    for (int m : c.nodes) node += (node.empty() ? "" : "+") + g->nodes[m].name;
+    if (x.dims != y.dims || x.dtype != y.dtype) { set_error("bytemap chain %s: output shape / type mismatch", node.c_str()); return -1; }
+    std::vector<unsigned> table(64);
+    memcpy(table.data(), c.table, 256);
+    unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    if (lut_step(node, "bytemap chain", x, y, dtable, out)) return -1;
+    if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+    for (size_t k = 0; k + 1 < c.nodes.size(); k++) g->fused_away[g->nodes[c.nodes[k]].out[0]] = 1;      // never written
+    return 0;
 }
 
 int gate_lut_producer(const tamd_graph* g, const HNode& e, int gated)
@@ -610,7 +814,7 @@ int crop_topdown_next(const tamd_graph* g, size_t ci)
         for (int i : e.in) reads = reads || i == cut;
         if (!reads) continue;
         int gated = -1;
-        if (e.op != TAMD_OP_ELTWISE || e.out.size() != 1 || eltwise_refusal_of(g, e, &gated) || gated >= 0) return -1;
+        if (e.op != TAMD_OP_ELTWISE || e.out.size() != 1 || eltwise_refusal_of(g, e, &gated) || gated != kEltSame) return -1;
         const HTensor& lat = g->tensors[e.in[e.in[0] == cut ? 1 : 0]];
         const HTensor& y = g->tensors[e.out[0]];
         if (lat.is_view || y.is_view || lat.dims != g->tensors[cut].dims || y.dims != lat.dims || lat.scales.size() != 1 || y.scales.size() != 1) return -1;
@@ -655,7 +859,7 @@ int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<S
     if (!why) why = crop_refusal_of(g, cn, true, &cg);
     if (!why) why = eltwise_refusal_of(g, n, &gated);
     if (why) { set_error("topdown %s: %s", node.c_str(), why); return -1; }
-    if (x.dtype != TAMD_DT_UINT8 || gated >= 0 || cn.in[0] != in.out[0] || mid.dims.size() != 4 || mid.dims[2] != geom.out_h || mid.dims[3] != geom.out_w || cg.start[1] != 0
+    if (x.dtype != TAMD_DT_UINT8 || gated != kEltSame || cn.in[0] != in.out[0] || mid.dims.size() != 4 || mid.dims[2] != geom.out_h || mid.dims[3] != geom.out_w || cg.start[1] != 0
         || cg.out_dims[1] != x.dims[1] || cg.out_dims[0] != x.dims[0] || lat.dims != cut.dims || y.dims != cut.dims || x.is_view || lat.is_view || y.is_view || !x.nchw_raw
         || !lat.nchw_raw || !y.nchw_raw || lat.dtype != x.dtype || y.dtype != x.dtype) {
         set_error("topdown %s: the three nodes do not run as one launch", node.c_str());
@@ -753,3 +957,14 @@ int plan_shuffle_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
 }
 
 }  // namespace tamd
+
+extern "C" int tamd_graph_bytemap_chain(const tamd_graph* g, int node, int* nodes, int cap, unsigned char table[256])
+{
+    using namespace tamd;
+    if (!g || node < 0 || node >= (int)g->nodes.size() || !nodes || cap < 0 || !table) return -1;
+    ByteChain c;
+    if (!bytemap_chain_from(g, (size_t)node, [](int) { return true; }, [&](int t) { return g->tensors[t].ttype != TAMD_TT_CONST; }, &c)) return 0;
+    for (size_t k = 0; k < c.nodes.size() && (int)k < cap; k++) nodes[k] = c.nodes[k];
+    memcpy(table, c.table, 256);
+    return (int)c.nodes.size();
+}

@@ -753,13 +753,14 @@ static int plan_concat_u8(tamd_graph* g, HNode& n, const std::vector<int>& perm_
     return 0;
 }
 
-// the same-shape form: eltwise_u8; the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate (graph_plan_maps.hip), with the
+// the scalar and unary forms: one lut_u8 launch by table (plan_eltwise_table); the same-shape form: eltwise_u8; the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1): plan_chan_gate (graph_plan_maps.hip), with the
 // byte map in front of the gate (node lut_node, -1: none) inside the launch
 static int plan_eltwise_u8(tamd_graph* g, HNode& n, int lut_node, std::vector<Step>* out)
 {
     int gated = -1;
     const char* why = eltwise_refusal_of(g, n, &gated);
     if (why) { set_error("eltwise %s: %s", n.name.c_str(), why); return -1; }
+    if (gated == kEltScalar || gated == kEltUnary) return plan_eltwise_table(g, n, out);
     if (gated >= 0) return plan_chan_gate(g, n, gated, lut_node, out);
     HTensor& xa = g->tensors[n.in[0]];
     HTensor& xb = g->tensors[n.in[1]];
@@ -904,9 +905,27 @@ int plan_u8(tamd_graph* g)
         const int ej = crop_topdown_next(g, ci);
         if (ej > (int)ci && !fused[ej] && !gate_lut[ej] && !topdown[ej]) { topdown[ej] = (int)ci + 1; fused[ci] = 1; }
     }
+    // byte-pure chains (bytemap_chain_from, graph_plan_maps.hip) as one lut_u8 launch each at the LAST member's position:
+    // chain_at[last member] = the chain's index + 1, the other members are skipped.  Every tensor owns its buffer here: only views are out
+    std::vector<ByteChain> chains;
+    std::vector<int> chain_at(g->nodes.size(), 0);
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        ByteChain c;
+        if (!bytemap_chain_from(g, ni, [&](int k) { return !fused[k] && !gate_lut[k] && !slice_next[k] && !crop_interp[k] && !topdown[k] && !chain_at[k]; },
+                                [&](int t) { return g->tensors[t].ttype != TAMD_TT_CONST && !g->tensors[t].is_view; }, &c))
+            continue;
+        for (size_t k = 0; k + 1 < c.nodes.size(); k++) fused[c.nodes[k]] = 1;
+        chains.push_back(c);
+        chain_at[c.nodes.back()] = (int)chains.size();
+    }
     for (size_t ni = 0; ni < g->nodes.size(); ni++) {
         HNode& n = g->nodes[ni];
         if (fused[ni]) continue;
+        if (chain_at[ni]) {
+            std::vector<Step> one;
+            if (plan_bytemap_chain(g, chains[chain_at[ni] - 1], &one) || append_steps(g, one)) return -1;
+            continue;
+        }
         if (n.op == TAMD_OP_INPUT || n.op == TAMD_OP_CONST || n.op == TAMD_OP_DROPOUT || n.op == TAMD_OP_FLATTEN || n.op == TAMD_OP_RESHAPE) continue;
         HTensor& x = g->tensors[n.in[0]];
         HTensor& y = g->tensors[n.out[0]];
@@ -929,6 +948,7 @@ int plan_u8(tamd_graph* g)
             rc = crop_interp[ni] ? plan_interp(g, g->nodes[crop_interp[ni] - 1], &out, &n) : plan_crop_u8(g, n, &out);
             break;
         case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
+        case TAMD_OP_BATCHNORM: rc = plan_batchnorm_u8(g, n, &out); break;      // chan_lut_u8, or prelu_u8's per-plane form on large planes
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it
             break;

@@ -567,6 +567,14 @@ const char* transpose_kernel_name(int form);
 hipError_t launch_transpose(const TransposeArgs& a, hipStream_t s);
 hipError_t launch_prelu_i8(const PreluI8Args& a, hipStream_t s);
 hipError_t launch_prelu_u8(const PreluU8Args& a, hipStream_t s);
+// A byte map per channel over a dense uint8 tensor [N][C][HW] (chan_lut.hip): y[i] = tables[c(i)][x[i]], c(i) = (i / HW) % C
+struct ChanLutU8Args {
+    const uint8_t* x; uint8_t* y;      // both 16-byte aligned: chunk k is bytes [16k, 16k + 16) of either
+    size_t total;          // N * C * HW bytes
+    int C, HW;
+    const unsigned* tables;// [C][64]: the 256 bytes of every channel's map as they lie
+};
+hipError_t launch_chan_lut_u8(const ChanLutU8Args& a, hipStream_t s);
 hipError_t launch_chan_gate_i8(const ChanGateI8Args& a, hipStream_t s);
 hipError_t launch_chan_gate_u8(const ChanGateU8Args& a, hipStream_t s);
 hipError_t launch_softmax_i8(const SoftmaxI8Args& a, hipStream_t s);

@@ -15,13 +15,14 @@
 namespace tamd {
 
 // Eltwise: the binary forms over two tensors of one shape -- ELT_PROD 0, ELT_SUM 2, ELT_SUB 4, ELT_MAX 6 (eltwise_param.h); the odd
-// values next to them are the tensor-with-scalar forms, 7 and up the unary ones: no device kernel for those
+// values next to them are the tensor-with-scalar forms, 7 and up the unary ones: byte maps by table, below (eltwise_refusal)
 inline bool eltwise_type_on_device(int type) { return type == 0 || type == 2 || type == 4 || type == 6; }
 // .. and the channel gate of a Squeeze-and-Excitation block: x (N, C, H, W) op gate (N, C, 1, 1), int8 and uint8 graphs (chan_gate.hip).
 // fp32 graphs keep it on the CPU device (their Sigmoid is there anyway)
 inline bool chan_gate_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
-// One Eltwise node: nullptr when the device runs it, else the reason.  *gated: -1 for the same-shape form, else which input (0 | 1) is
-// x, the operand with more elements; the other one is the gate.  a / b: inputs 0 / 1.
+// One Eltwise node: nullptr when the device runs it, else the reason.  *gated: -1 (kEltSame) for the same-shape form, 0 | 1: which input
+// is x, the operand with more elements, of the gate form -- the other one is the gate --, kEltScalar / kEltUnary for the two table forms
+// below.  a / b: inputs 0 / 1 (b_*: unread with one input); b_dtype: the data type of input 1.
 // eltwise_ref.c: run() makes the operand with more elements in0, whichever input it is, and hands over input_chan = dims[-4] * dims[-3]
 // (N * C), input_hw = H * W and input1_count4 = the smaller operand's element count; the branch input_chan == input1_count4 of
 // ref_eltwise_int8 / _uint8 computes out[i] = in0[i] op in1[i / input_hw] for PROD, SUM and SUB: always x op gate, for SUB too.
@@ -30,19 +31,85 @@ inline bool chan_gate_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dty
 //    unwritten
 //  - a smaller operand of another shape (2-D, (1, N * C, 1, 1), one element, a row of H * W) takes other branches of the reference, or
 //    the same one with a meaning the device tensors' layout does not carry: each is refused by its own name
-inline const char* eltwise_refusal(const tamd_eltwise_param* p, int dtype, int input_num, int a_dim_num, const int* a_dims, bool a_const, size_t a_quant, int b_dim_num,
-                                   const int* b_dims, bool b_const, size_t b_quant, size_t out_quant, int* gated)
+//
+// The scalar form (*gated = kEltScalar) and the unary form (*gated = kEltUnary), int8 and uint8 graphs: both kernels dequantise, run the
+// operator's line against in1[0] or against nothing, and requantise -- one byte in, one byte out, so the device maps bytes through
+// tamd_eltwise_table with one lut_u8 launch.  The two kernels have the same cases (eltwise_ref.c:359-568, :619-828):
+//  - scalar: inputs [x, c], x a 4-D activation, c a CONSTANT of one element.  PROD_SCALAR 1, SUB_SCALAR 5 and MIN_SCALAR 8 read in1[0]
+//    whatever the count; PROD 0, SUM 2, SUB 4 and DIV 10 have the branch input1_count4 == 1.  (Where N * C == 1 SUB takes the channel
+//    branch in1[i / input_hw] first, and on a one-element x every type the same-shape one: in1[0] in both.)  The uint8 kernel takes a
+//    uint8 or an fp32 constant (:336-351); the int8 kernel reads the buffer as int8 whatever its type, so an fp32 constant is refused
+//  - unary: one input.  RSQRT 7, LOG 11, EXP 12, SQRT 13, FLOOR 14, SQUARE 15, POWER 17 (shift, scale, power)
+//  - SUM_SCALAR 3 has no case in either kernel (the output is requantised from a buffer nobody wrote); MAX 6 reads in1[i] over the
+//    larger count, past a one-element operand's end; the one-element loops of POW 16 run over the wrong count; LAST 9 is no operator
+//  - a one-element operand that is not a constant, or is listed first, stays refused: the table is built at prerun from the value
+//  - a table entry the reference does not define -- the float result NaN or infinite, or the rounded value outside int, where its
+//    float-to-int conversion is undefined behaviour: RSQRT or LOG of a tensor whose zero-point byte is 0.0, a division by 0 --
+//    refuses the node: there are no bytes to equal
+// v: the values the table is built from, where the caller has them (a support query may not: then the table is not checked, and prerun
+// refuses by name what the query let through); table[256]: the byte map (may be null)
+enum { kEltSame = -1, kEltScalar = -2, kEltUnary = -3 };
+struct EltwiseValues {
+    float x_scale; int x_zp; float out_scale; int out_zp;
+    const void* c_data; float c_scale; int c_zp;                  // the constant's first element and its one pair (scalar form)
+};
+inline const char* eltwise_table_refusal(const tamd_eltwise_param* p, int dtype, int c_dtype, const EltwiseValues& v, unsigned char* table)
 {
-    *gated = -1;
+    float s = 0.f;
+    if (c_dtype >= 0 && tamd_eltwise_scalar(c_dtype, v.c_data, v.c_scale, v.c_zp, &s)) return "Eltwise: the constant's value cannot be read";
+    unsigned char map[256];
+    const int rc = tamd_eltwise_table(p->type, dtype, p, s, v.x_scale, v.x_zp, v.out_scale, v.out_zp, map);
+    if (rc == -2) return "Eltwise: the table holds a value the reference does not define (NaN, infinite or outside int before its conversion)";
+    if (rc) return "Eltwise: the reference's quantised kernels have no case for this type";
+    if (table) for (int b = 0; b < 256; b++) table[b] = map[b];
+    return nullptr;
+}
+inline const char* eltwise_refusal(const tamd_eltwise_param* p, int dtype, int input_num, int a_dim_num, const int* a_dims, bool a_const, size_t a_quant, int b_dim_num,
+                                   const int* b_dims, bool b_const, size_t b_quant, size_t out_quant, int* gated, int b_dtype = -1, const EltwiseValues* v = nullptr,
+                                   unsigned char* table = nullptr)
+{
+    *gated = kEltSame;
     if (!p) return "Eltwise needs its parameter";
+    const bool quantised = chan_gate_on_device(dtype);
+    if (p->type == 3) return "Eltwise SUM_SCALAR: alone of the scalar and unary types it has no case in either quantised kernel of the reference";
+    if (p->type == 9) return "Eltwise LAST is no operator: of the scalar and unary types only those with a case in the reference run on the device";
+    if (p->type == 16) return "Eltwise POW does not run on the device: its one-element loops in the reference run over the wrong count";
+    if (eltwise_unary_type(p->type)) {
+        if (input_num != 1) return "the scalar and unary Eltwise types run in their own form only: a unary type takes one input";
+        if (!quantised) return "the scalar and unary forms of Eltwise run on the device in int8 and uint8 graphs only";
+        if (a_const) return "Eltwise: the input of a unary type must not be a constant";
+        if (a_dim_num != 4) return "the scalar and unary forms of Eltwise take a 4-D activation";
+        if (a_quant != 1 || out_quant != 1) return "the scalar and unary forms of Eltwise need per-tensor quant params on both sides";
+        if (v) { const char* why = eltwise_table_refusal(p, dtype, -1, *v, table); if (why) return why; }
+        *gated = kEltUnary;
+        return nullptr;
+    }
     if (input_num != 2) return "Eltwise runs on the device on two tensors";
-    bool same = a_dim_num == b_dim_num;
-    for (int i = 0; same && i < a_dim_num; i++) same = a_dims[i] == b_dims[i];
-    if (!eltwise_type_on_device(p->type)) return "the scalar and unary Eltwise types do not run on the device";
-    if (a_const || b_const) return "Eltwise: neither operand may be a constant";
-    if (same) return nullptr;                                     // PROD, SUM, SUB, MAX of two tensors of one shape, every graph type
     auto elems = [](int n, const int* d) { size_t e = 1; for (int i = 0; i < n; i++) e *= (size_t)d[i]; return e; };
     const size_t ea = elems(a_dim_num, a_dims), eb = elems(b_dim_num, b_dims);
+    if (a_const && ea == 1 && !b_const) return "an Eltwise whose one-element constant is listed first does not run on the device";
+    if (b_const && eb == 1 && !a_const) {
+        if (!quantised) return "the scalar and unary forms of Eltwise run on the device in int8 and uint8 graphs only";
+        if (p->type == 6) return "Eltwise MAX with a one-element operand does not run on the device: the reference reads in1[i] past its end";
+        if (!eltwise_scalar_type(p->type)) return "Eltwise: the reference's quantised kernels have no case for this type with a one-element operand";
+        if (a_dim_num != 4) return "the scalar and unary forms of Eltwise take a 4-D activation";
+        if (a_quant != 1 || out_quant != 1) return "the scalar and unary forms of Eltwise need per-tensor quant params on both sides";
+        if (dtype == TAMD_DT_INT8 && b_dtype == TAMD_DT_FP32) return "an int8 Eltwise reads its constant as int8: an fp32 constant does not run on the device";
+        if (dtype == TAMD_DT_INT8 ? b_dtype != TAMD_DT_INT8 : (b_dtype != TAMD_DT_UINT8 && b_dtype != TAMD_DT_FP32))
+            return "Eltwise: the one-element constant must be uint8 or fp32 in a uint8 graph, int8 in an int8 graph";
+        if (b_dtype != TAMD_DT_FP32 && b_quant != 1) return "Eltwise: a quantised one-element constant needs one (scale, zero point) pair";
+        if (v && v->c_data) { const char* why = eltwise_table_refusal(p, dtype, b_dtype, *v, table); if (why) return why; }
+        *gated = kEltScalar;
+        return nullptr;
+    }
+    bool same = a_dim_num == b_dim_num;
+    for (int i = 0; same && i < a_dim_num; i++) same = a_dims[i] == b_dims[i];
+    if (!eltwise_type_on_device(p->type)) {
+        if ((ea == 1 || eb == 1) && !a_const && !b_const) return "an Eltwise with a one-element operand that is not a constant does not run on the device";
+        return "the scalar and unary Eltwise types run in their own form only: a 4-D activation, then a constant of one element";
+    }
+    if (a_const || b_const) return "Eltwise: neither operand may be a constant";
+    if (same) return nullptr;                                     // PROD, SUM, SUB, MAX of two tensors of one shape, every graph type
     const int big = ea >= eb ? 0 : 1;
     const int xn = big ? b_dim_num : a_dim_num, gn = big ? a_dim_num : b_dim_num;
     const int* xd = big ? b_dims : a_dims;
@@ -62,6 +129,44 @@ inline const char* eltwise_refusal(const tamd_eltwise_param* p, int dtype, int i
     if (a_quant != 1 || b_quant != 1 || out_quant != 1) return "a gated Eltwise needs per-tensor quant params on all three tensors";
     if (big == 1 && xd[0] != 1) return "an Eltwise gate listed first is defined for batch 1 only";
     *gated = big;
+    return nullptr;
+}
+
+// BatchNorm: the uint8 kernel of the reference (batchnorm_kernel_ref_uint8.c:40-107; chan_lut.hip, prelu.hip).  There is no int8 kernel
+// (run() writes nothing), and fp32 graphs keep the node on the CPU device
+inline bool batchnorm_on_device(int dtype) { return dtype == TAMD_DT_UINT8; }
+// one of the four statistics of a BatchNorm node (inputs 1 .. 4: gamma, beta, mean, var); data: its payload where the caller has it
+struct BnStat { int dtype; bool is_const; size_t elems; const float* data; };
+// One BatchNorm node: nullptr when the device runs it, else the reason.  st[4]: gamma, beta, mean, var.  v (may be null): the scales and
+// zero points of x and of the output; with them and every payload the C tables are built (tables: [C][64] dwords, may be null) and a
+// channel whose s1 / s2 or table is not finite refuses the node: the reference's (int) conversion is undefined there.
+//  - 2-D [N,C], 3-D [N,C,W], 4-D [N,C,H,W]: the three cases of batchnorm_ref.c:117-141; any other rank fails there
+//  - caffe_flavor: gamma and beta are never read (prerun :88-95), so only mean and var must be fp32 constants of C elements
+inline const char* batchnorm_refusal(const tamd_batchnorm_param* p, int dtype, int input_num, int x_dim_num, const int* x_dims, bool x_const, size_t x_quant,
+                                     size_t out_quant, const BnStat* st, const EltwiseValues* v, std::vector<unsigned>* tables)
+{
+    if (!p) return "BatchNorm needs its parameter";
+    if (dtype == TAMD_DT_INT8) return "BatchNorm does not run on the device in int8 graphs: the reference has no int8 kernel";
+    if (!batchnorm_on_device(dtype)) return "BatchNorm runs on the device in uint8 graphs only";
+    if (input_num != 5) return "BatchNorm takes five inputs: the data, gamma, beta, mean and var";
+    if (x_dim_num < 2 || x_dim_num > 4) return "BatchNorm runs on a 2-D [N,C], 3-D [N,C,W] or 4-D [N,C,H,W] tensor only";
+    if (x_const) return "BatchNorm: the data tensor must not be a constant";
+    if (x_quant != 1 || out_quant != 1) return "BatchNorm needs per-tensor quant params on both sides";
+    for (int i = 0; i < x_dim_num; i++) if (x_dims[i] < 1) return "BatchNorm: every dimension must be at least 1";
+    const size_t C = (size_t)x_dims[1];
+    for (int k = p->caffe_flavor ? 2 : 0; k < 4; k++)
+        if (st[k].dtype != TAMD_DT_FP32 || !st[k].is_const || st[k].elems != C) return "BatchNorm: gamma, beta, mean and var must be fp32 constants of C elements";
+    bool values = v != nullptr;
+    for (int k = p->caffe_flavor ? 2 : 0; k < 4; k++) values = values && st[k].data;
+    if (!values) return nullptr;
+    if (tables) tables->assign(C * 64, 0u);
+    unsigned char map[256];
+    for (size_t c = 0; c < C; c++) {
+        const float gamma = p->caffe_flavor ? 1.f : st[0].data[c], beta = p->caffe_flavor ? 0.f : st[1].data[c];
+        if (tamd_batchnorm_table(p, gamma, beta, st[2].data[c], st[3].data[c], v->x_scale, v->x_zp, v->out_scale, v->out_zp, map))
+            return "BatchNorm: a channel's s1 / s2 or table is not finite (the reference's conversion to int is undefined there)";
+        if (tables) for (int b = 0; b < 256; b++) ((unsigned char*)tables->data())[c * 256 + b] = map[b];
+    }
     return nullptr;
 }
 

@@ -60,6 +60,7 @@ struct Reader {
 int map_op(uint32_t t)
 {
     switch (t) {
+    case 1: return TAMD_OP_BATCHNORM;                 // TM2_OPTYPE_BATCHNORMALIZATION: TM2_BatchNormParam; inputs [x, gamma, beta, mean, var]
     case 3: return TAMD_OP_CONCAT;
     case 4: return TAMD_OP_CONST;
     case 5: return TAMD_OP_CONV;
@@ -181,6 +182,7 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 break;
             }
             case TAMD_OP_FC: p.fc.num_output = r.i32(po); break;
+            case TAMD_OP_BATCHNORM: p.bn.rescale_factor = r.f32(po); p.bn.eps = r.f32(po + 4); p.bn.caffe_flavor = r.i32(po + 8); break;      // TM2_BatchNormParam :407-412
             case TAMD_OP_RELU: p.relu.negative_slope = r.f32(po); break;
             case TAMD_OP_ELTWISE:
                 p.elt.type = (int)r.u32(po); p.elt.caffe_flavor = r.i32(po + 4); p.elt.shift = r.f32(po + 8);

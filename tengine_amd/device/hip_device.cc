@@ -42,6 +42,7 @@ extern "C" {
 #include "utility/sys_port.h"
 #include "utility/vector.h"
 // operator parameter structs (source/operator/prototype/)
+#include "batchnorm_param.h"
 #include "clip_param.h"
 #include "concat_param.h"
 #include "convolution_param.h"
@@ -98,6 +99,9 @@ const OpRow kOps[] = {
     // the activation of the face models (csrc/prelu.hip): the two quantised kernels of the reference; its fp16 slope constant travels
     // like any constant.  An fp32 graph keeps the node on the CPU device (which ranks and slopes: tamd_node_supported)
     {OP_PRELU, TAMD_OP_PRELU, true},
+    // the not-folded BatchNorm of an MXNet export (csrc/chan_lut.hip): the uint8 kernel of the reference, a byte map per channel; int8 (no
+    // kernel in the reference) and fp32 graphs keep the node on the CPU device (which ranks and statistics: tamd_node_supported)
+    {OP_BATCHNORM, TAMD_OP_BATCHNORM, true},
     // YOLOv4-tiny's routes and Focus's strided picks (csrc/slice.hip): the onnx form in uint8 graphs.  The reference has no int8 kernel, and
     // an fp32 graph keeps the node on the CPU device -- the caffe Slice of the ShuffleNet benchmark file too (which: tamd_node_supported)
     {OP_SLICE, TAMD_OP_SLICE, true},
@@ -170,7 +174,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_transpose_param transpose;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_transpose_param transpose; tamd_batchnorm_param bn;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -234,6 +238,11 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
         s->slice.slice_point_num = p->slice_point_ ? get_vector_num(p->slice_point_) : 0;
         s->slice.begin_num = p->begin_ ? get_vector_num(p->begin_) : 0;
         s->slice.size_num = p->size_ ? get_vector_num(p->size_) : 0;
+        break;
+    }
+    case TAMD_OP_BATCHNORM: {        // batchnorm_param.h, field for field
+        const struct batchnorm_param* p = (const struct batchnorm_param*)n->op.param_mem;
+        s->bn = {p->rescale_factor, p->eps, p->caffe_flavor};
         break;
     }
     case TAMD_OP_CROP: {             // crop_param.h, field for field
@@ -543,8 +552,9 @@ static bool node_supported(struct graph* ir, struct node* n)
     if (op == TAMD_OP_INPUT || op == TAMD_OP_CONST) return true;
     std::vector<tamd_tensor_desc> in, out;
     // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device --
-    // and for the quantisation values on both sides of a Slice or a Transpose: a pair whose byte map the reference cannot compute does the same)
-    const bool values = op == TAMD_OP_SLICE || op == TAMD_OP_TRANSPOSE;
+    // and for the quantisation values on both sides of a Slice or a Transpose: a pair whose byte map the reference cannot compute does the same;
+    // an Eltwise with a constant scalar or of a unary type is such a byte map too, of those values and the constant's)
+    const bool values = op == TAMD_OP_SLICE || op == TAMD_OP_TRANSPOSE || op == TAMD_OP_ELTWISE || op == TAMD_OP_BATCHNORM;      // (BatchNorm: the four statistics too)
     for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), values || (op == TAMD_OP_PRELU && k == 1)));
     for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), values));
     NodeParams params;

@@ -400,9 +400,16 @@ def fp32_forward(g: Graph, x: np.ndarray):
         elif op == "ReLU6":
             y = torch.clamp(a, 0, 6)
         elif op == "Eltwise":
-            bb = vals[n.inputs[1]]
-            y = {tm2.ELT_SUM: a + bb, tm2.ELT_PROD: a * bb, tm2.ELT_MAX: torch.maximum(a, bb),
-                 tm2.ELT_SUB: a - bb}[p["type"]]
+            t = p["type"]
+            if len(n.inputs) == 1:      # the unary types (eltwise_ref.c): value ranges for calibration
+                y = {tm2.ELT_RSQRT: lambda: torch.rsqrt(a), tm2.ELT_LOG: lambda: torch.log(a), tm2.ELT_EXP: lambda: torch.exp(a),
+                     tm2.ELT_SQRT: lambda: torch.sqrt(a), tm2.ELT_FLOOR: lambda: torch.floor(a), tm2.ELT_SQUARE: lambda: a * a,
+                     tm2.ELT_POWER: lambda: torch.pow(p.get("shift", 0.0) + p.get("scale", 1.0) * a, p.get("power", 1.0))}[t]()
+            else:                       # a one-element second operand broadcasts: the scalar form
+                bb = vals[n.inputs[1]]
+                y = {tm2.ELT_SUM: lambda: a + bb, tm2.ELT_PROD: lambda: a * bb, tm2.ELT_MAX: lambda: torch.maximum(a, bb), tm2.ELT_SUB: lambda: a - bb,
+                     tm2.ELT_PROD_SCALAR: lambda: a * bb.reshape(-1)[0], tm2.ELT_SUB_SCALAR: lambda: a - bb.reshape(-1)[0],
+                     tm2.ELT_MIN_SCALAR: lambda: torch.clamp(a, max=float(bb.reshape(-1)[0])), tm2.ELT_DIV: lambda: a / bb}[t]()
         elif op == "Concat":
             y = torch.cat([vals[i] for i in n.inputs], dim=p.get("axis", 1))
         elif op == "Dropout":

@@ -28,6 +28,7 @@ LAYOUT_NCHW = 0
 CROP_FIELDS = ("num_args", "offset_c", "offset_h", "offset_w", "crop_h", "crop_w", "center_crop", "axis", "flag")      # crop_param.h
 
 OPTYPE = {
+    "BatchNormalization": 1,      # TM2_BatchNormParam; inputs [x, gamma, beta, mean, var], the four statistics fp32 constants of C elements
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55, "Crop": 56,
@@ -38,6 +39,7 @@ OPNAME = {v: k for k, v in OPTYPE.items()}
 
 # eltwise types (source/operator/prototype/eltwise_param.h)
 ELT_PROD, ELT_PROD_SCALAR, ELT_SUM, ELT_SUM_SCALAR, ELT_SUB, ELT_SUB_SCALAR, ELT_MAX = 0, 1, 2, 3, 4, 5, 6
+ELT_RSQRT, ELT_MIN_SCALAR, ELT_LAST, ELT_DIV, ELT_LOG, ELT_EXP, ELT_SQRT, ELT_FLOOR, ELT_SQUARE, ELT_POW, ELT_POWER = 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17
 POOL_MAX, POOL_AVG = 0, 1
 
 
@@ -111,6 +113,8 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<I10i", p["alg"], p["kernel_h"], p["kernel_w"], p["stride_h"], p["stride_w"],
                            p.get("global", 0), p.get("caffe_flavor", 0), p.get("pad_h0", 0),
                            p.get("pad_w0", 0), p.get("pad_h1", 0), p.get("pad_w1", 0))
+    if op == "BatchNormalization":      # TM2_BatchNormParam :407-412
+        return struct.pack("<2fi", p.get("rescale_factor", 1.0), p.get("eps", 1e-5), p.get("caffe_flavor", 0))
     if op == "FullyConnected":   # TM2_FCParam :474-477
         return struct.pack("<i", p["num_output"])
     if op == "Eltwise":          # TM2_EltwiseParam :465-472
@@ -153,6 +157,8 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         k = ["alg", "kernel_h", "kernel_w", "stride_h", "stride_w", "global", "caffe_flavor", "pad_h0",
              "pad_w0", "pad_h1", "pad_w1"]
         return dict(zip(k, struct.unpack_from("<I10i", b, off)))
+    if op == "BatchNormalization":
+        return dict(zip(["rescale_factor", "eps", "caffe_flavor"], struct.unpack_from("<2fi", b, off)))
     if op == "FullyConnected":
         return {"num_output": struct.unpack_from("<i", b, off)[0]}
     if op == "Eltwise":
