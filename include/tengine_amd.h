@@ -131,6 +131,14 @@ enum {
      * reference), fp32 graphs, another rank, a statistic that is no fp32 constant of C elements and a channel whose table is not
      * finite are refused by name */
     TAMD_OP_BATCHNORM = 32,
+    /* 33: reserved, never supported (like 21, 24, 27, 29 and 31: tests/test_bytemap_cpu.py holds the code to that answer) */
+    /* sub-pixel convolution's shuffle -- ESPCN, EDSR, torch.nn.PixelShuffle; tm2 operator 80 --, int8 / uint8 graphs: param
+     * tamd_depthtospace_param.  Input (N, C, H, W), block size r >= 1 with C % (r * r) == 0; the output is (N, C / r^2, H * r, W * r)
+     * (depthtospace.c infer_shape) and out[b, s, h, w] = in[b, s * r^2 + (h % r) * r + (w % r), h / r, w / r], the CRD order
+     * (depthtospace_ref.c).  The reference moves RAW bytes: no quantisation parameter of either tensor is read, and the int8 byte -128
+     * stays -128.  Other ranks, a block size below 1, a channel count that r^2 does not divide (the reference then silently drops
+     * channels), a constant input and per-channel parameters are refused by name; fp32 graphs keep the node on the CPU device */
+    TAMD_OP_DEPTHTOSPACE = 34,
     TAMD_OP_NUM
 };
 
@@ -156,6 +164,7 @@ typedef struct tamd_pool_param {
 typedef struct tamd_relu_param { float negative_slope; } tamd_relu_param;   /* relu_param.h */
 /* field meaning == struct batchnorm_param (batchnorm_param.h) */
 typedef struct tamd_batchnorm_param { float rescale_factor, eps; int caffe_flavor; } tamd_batchnorm_param;
+typedef struct tamd_depthtospace_param { int block_size; } tamd_depthtospace_param;   /* depthtospace_param.h */
 typedef struct tamd_eltwise_param { int type; int caffe_flavor; float shift, power, scale; } tamd_eltwise_param;
 typedef struct tamd_concat_param { int axis; } tamd_concat_param;
 typedef struct tamd_upsample_param { float scale; } tamd_upsample_param;

@@ -127,6 +127,11 @@ def slice_table(in_scale, in_zp, out_scale, out_zp):
     return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
 OP_TRANSPOSE = 28        # (27: reserved, like 21 and 24)
 OP_CROP = 30             # (29: reserved too)
+OP_DEPTHTOSPACE = 34     # (33: reserved too)
+
+
+class DepthToSpaceParam(C.Structure):  # tamd_depthtospace_param
+    _fields_ = [("block_size", C.c_int)]
 
 
 class CropParam(C.Structure):         # tamd_crop_param

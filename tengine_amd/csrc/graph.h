@@ -56,6 +56,7 @@ union NodeParam {
     tamd_slice_param slice;
     tamd_transpose_param transpose;
     tamd_crop_param crop;
+    tamd_depthtospace_param d2s;
     tamd_batchnorm_param bn;
 };
 
@@ -354,6 +355,13 @@ int crop_topdown_next(const tamd_graph* g, size_t ci);
 int plan_crop_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // Interp `in` -> Crop `cn` -> Eltwise `n` as ONE topdown_u8 launch (topdown.hip), planned at the Eltwise's position
 int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out);
+// depthtospace_refusal (node_rules.h) asked of a node of this graph: infer_shapes (check_out false: the output's dims are not made yet),
+// validate_graph and the planners.  *geom (may be null): the block size, the output's dims, the six-axis view
+const char* depthtospace_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, DepthToSpaceGeom* geom);
+// a DepthToSpace node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch: d2s_i8 / d2s_u8 (d2s.hip), or with TAMD_PIN=d2s_form=0, where
+// the output is one dense run, the canonical gather of transpose.hip with the identity map.  fix128 (int8): the output lies in the
+// buffer of a Concat of several inputs, whose copy stores 127 for the byte -128
+int plan_depthtospace(tamd_graph* g, HNode& n, bool fix128, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
 // same-shape form, 0 | 1 which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1), kEltScalar / kEltUnary the two
 // forms that run by table; table[256]: the byte map of those two (may be null)

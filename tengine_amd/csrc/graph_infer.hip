@@ -269,6 +269,13 @@ int infer_shapes(tamd_graph* g)
             break;
         }
         case TAMD_OP_BATCHNORM: y.dims = x.dims; y.dtype = x.dtype; break;      // batchnorm.c: the input's shape; the statistics are fp32, the data is not
+        case TAMD_OP_DEPTHTOSPACE: {      // depthtospace.c infer_shape: (N, C / r^2, H * r, W * r).  What the device does not run is refused HERE, by name
+            DepthToSpaceGeom dg;
+            const char* why = depthtospace_refusal_of(g, n, false, &dg);
+            if (why) { set_error("depthtospace %s: %s", n.name.c_str(), why); return -1; }
+            y.dims.assign(dg.out_dims, dg.out_dims + 4);
+            break;
+        }
         case TAMD_OP_PRELU: y.dims = x.dims; y.dtype = x.dtype; break;      // prelu.c: the input's shape; the type is the data's, not the fp16 slope's
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
@@ -359,6 +366,10 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_CROP) {
             const char* why = crop_refusal_of(g, n, true, nullptr);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_DEPTHTOSPACE) {
+            const char* why = depthtospace_refusal_of(g, n, true, nullptr);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_TRANSPOSE) {

@@ -45,7 +45,7 @@ static bool ops_allow_split(const tamd_graph* g)
             break;
         case TAMD_OP_TRANSPOSE: return false;              // order[0] != 0 moves the batch axis: the images are not independent (and the Reshapes
                                                            // around every Transpose of the supported graphs are not on this list either)
-        // (a Crop is not on the list: a graph with one is not split by batch)
+        // (a Crop is not on the list: a graph with one is not split by batch; neither is a DepthToSpace)
         case TAMD_OP_CONCAT: if (n.p.concat.axis < 1) return false; break;
         case TAMD_OP_SOFTMAX: if (n.p.softmax.axis < 1) return false; break;
         default: return false;

@@ -129,11 +129,12 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 // channel count / offset not a multiple of 16; produced or also consumed by a kernel that does not address channel
 // slices; a graph input) keeps its own buffer and is copied by concat_copy_i8 at the concat's position.
 // the operators whose launches address a channel slice of a wider buffer, on the side they read and on the side they write
-static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP; }
+static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP || op == TAMD_OP_DEPTHTOSPACE; }
 // .. and on the side they read alone.  Split and ShuffleChannel are NOT written in place into a Concat's buffer: they hand on the byte
 // -128 where their input holds it, and the reference's Concat of several inputs turns that byte into 127 even between equal scales
 // (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not.  Upsample holds that byte too and IS written in
-// place: its launch stores 127 for it, where the Concat is its only reader (plan_concat_views, plan_upsample)
+// place: its launch stores 127 for it, where the Concat is its only reader (plan_concat_views, plan_upsample).  DepthToSpace moves raw
+// bytes, -128 among them, and follows the Upsample's rule (plan_depthtospace: D2sI8Args::fix128)
 // A Transpose reads its source through strides (plan_transpose): a channel slice is the same read from another base
 static bool reads_slices(int op) { return slice_capable(op) || op == TAMD_OP_SPLIT || op == TAMD_OP_SHUFFLECHANNEL || op == TAMD_OP_TRANSPOSE; }
 
@@ -164,7 +165,7 @@ static int plan_concat_views(tamd_graph* g, I8Layout& L)
             // (UpsampleI8Args::fix128) -- which is what the Concat's readers must see and NOT what another reader of the Upsample's own
             // tensor must see: with a second reader it keeps its buffer and concat_copy_i8 copies.  (Conv, FC, Pool and Interp
             // saturate at +-127 and never hold the byte.)
-            if (producer_op(i) == TAMD_OP_UPSAMPLE && n.in.size() > 1 && count_consumers(g, i) > 1) ok = false;
+            if ((producer_op(i) == TAMD_OP_UPSAMPLE || producer_op(i) == TAMD_OP_DEPTHTOSPACE) && n.in.size() > 1 && count_consumers(g, i) > 1) ok = false;      // (DepthToSpace: raw bytes, the same rule)
             if (ok) { L.view_of[i] = n.out[0]; L.view_off[i] = off; L.in_multi_cat[i] = n.in.size() > 1; }
             off += x.c;
         }
@@ -930,6 +931,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_SOFTMAX: r = plan_softmax(g, L, n, &out); break;
         case TAMD_OP_RELU: r = plan_relu(g, L, ni, &out); break;
         case TAMD_OP_UPSAMPLE: r = plan_upsample(g, L, n, &out); break;
+        case TAMD_OP_DEPTHTOSPACE: r = plan_depthtospace(g, n, L.in_multi_cat[n.out[0]] != 0, &out); break;      // one d2s_i8 launch (d2s.hip)
         case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, ni, &out); break;
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: r = plan_lut(g, n, &out); break;
         case TAMD_OP_INTERP: r = plan_interp(g, n, &out); break;

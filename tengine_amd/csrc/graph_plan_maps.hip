@@ -842,6 +842,94 @@ int plan_crop_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
     return 0;
 }
 
+// ---- DepthToSpace of a quantised graph (d2s.hip), both types.  Everything the reference decides for the node is decided by
+// depthtospace_refusal (node_rules.h): the block size, the channel count, the output's dims.  The output is a shuffle of the input's RAW
+// bytes (depthtospace_ref.c reads no quantisation parameter, -128 stays -128), so no table is made
+const char* depthtospace_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, DepthToSpaceGeom* geom)
+{
+    if (n.in.size() != 1 || n.out.empty()) return "DepthToSpace takes one input";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    return depthtospace_refusal(&n.p.d2s, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), (int)y.dims.size(),
+                                check_out ? y.dims.data() : nullptr, geom);
+}
+
+// One launch.  uint8 (NCHW): d2s_u8; the output may be a channel range of a Concat's buffer (out_img / out_c0).  int8 (NHWC): d2s_i8;
+// the input is read where it lies (a concat or Split view: another base and pixel stride), the output may be a concat view.
+// Block size 1 is a copy in the reference: the uint8 graph runs it as slice_u8 over the whole tensor in its identity form; d2s_i8 with
+// r == 1 IS a 16-byte copy per lane.  Form 0 (TAMD_PIN=d2s_form=0, and the default below kD2sNewFormFromBytes output bytes: profiles/d2s.txt)
+// is the baseline the new kernels are measured against -- the canonical gather of transpose.hip over the six-axis view with the identity
+// map (raw bytes: no table, no clamp) -- where the output is ONE dense run, which is all that kernel writes: a uint8 output that is no
+// slice of a Concat's buffer (or one of a single image), an int8 output without padding channels that is no concat view.  Elsewhere
+// form 0 is not legal and the new kernel runs whatever the size or the pin
+int plan_depthtospace(tamd_graph* g, HNode& n, bool fix128, std::vector<Step>* out)
+{
+    DepthToSpaceGeom dg;
+    const char* why = depthtospace_refusal_of(g, n, true, &dg);
+    if (why) { set_error("depthtospace %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (y.dtype != x.dtype) { set_error("depthtospace %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const int N = x.dims[0], C = dg.out_dims[1], H = x.dims[2], W = x.dims[3], r = dg.r;
+    const double bytes = 2.0 * (double)y.elems();
+    const bool want_gather = tamd_pin_int("d2s_form", (size_t)y.elems() >= kD2sNewFormFromBytes ? 1 : 0) == 0;
+    TransposeArgs t{};
+    t.identity = 1; t.form = kTransposeGather; t.total = (unsigned)y.elems();
+    auto gather_step = [&](const long* strides, const int* order) {
+        TransposeGeom tg;
+        transpose_canon(6, dg.view_dims, strides, order, &tg);
+        t.nd = tg.nd; t.unit = tg.unit;
+        for (int d = 0; d < 6; d++) { t.extent[d] = tg.extent[d]; t.stride[d] = (int)tg.stride[d]; }
+        const TransposeArgs a = t;
+        out->push_back(make_step(n.name, transpose_kernel_name(a.form), 0, bytes, [a](hipStream_t st) { return launch_transpose(a, st); }, {access_of(x)}, {access_of(y)}, false));
+    };
+    if (x.dtype == TAMD_DT_UINT8) {
+        if (x.is_view || fix128) { set_error("depthtospace %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
+        const long OHW = (long)H * r * W * r;
+        if (want_gather && (!y.is_view || N == 1)) {
+            const long strides[6] = {(long)C * r * r * H * W, (long)r * r * H * W, (long)r * H * W, (long)H * W, W, 1};
+            t.x = (const uint8_t*)x.dptr; t.y = (uint8_t*)y.dptr + (size_t)y.c_off * OHW; t.src_bytes = (unsigned)x.elems();
+            gather_step(strides, dg.order);
+            return 0;
+        }
+        if (r == 1) {                                            // a copy: slice_u8 over the whole tensor, raw bytes, step 1
+            SliceU8Args a{};
+            for (int i = 0; i < 4; i++) { a.in_dims[i] = x.dims[i]; a.out_dims[i] = dg.out_dims[i]; a.start[i] = 0; a.step[i] = 1; }
+            a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.table = nullptr; a.identity = 1;
+            a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.w2 = 0;
+            out->push_back(make_step(n.name, "slice_u8", 0, bytes, [a](hipStream_t s) { return launch_slice_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+            return 0;
+        }
+        D2sU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.N = N; a.C = C; a.H = H; a.W = W; a.r = r;
+        a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+        out->push_back(make_step(n.name, "d2s_u8", 0, bytes, [a](hipStream_t s) { return launch_d2s_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+        return 0;
+    }
+    // int8: convolution-stack NHWC buffers on both sides
+    if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || y.cs <= 0) { set_error("depthtospace %s: a dense (permuted / flattened) tensor is not supported in an int8 graph", n.name.c_str()); return -1; }
+    const int cv = rup(C, 16);
+    if (x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + x.dims[1] > x.cs || y.c_off + cv > y.cs) {
+        set_error("depthtospace %s: channel slice not 16-byte aligned", n.name.c_str());
+        return -1;
+    }
+    const size_t src_bytes = (size_t)N * H * W * x.cs - (size_t)x.c_off;
+    if (want_gather && !y.is_view && y.cs == C && y.c_off == 0 && !fix128 && src_bytes < 0x7fffffffu) {
+        // the NHWC output (n, h, w, s) = (n, hq, i, wq, j, s) reads the view's axes (0, 4, 2, 5, 3, 1) of a buffer with these strides
+        const long strides[6] = {(long)H * W * x.cs, (long)r * r, r, 1, (long)W * x.cs, x.cs};
+        const int order[6] = {0, 4, 2, 5, 3, 1};
+        t.x = (const uint8_t*)x.dptr + x.c_off; t.y = (uint8_t*)y.dptr; t.src_bytes = (unsigned)src_bytes;
+        gather_step(strides, order);
+        return 0;
+    }
+    D2sI8Args a{};
+    a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+    a.N = N; a.C = C; a.H = H; a.W = W; a.r = r; a.cs_in = x.cs; a.ldc = y.cs; a.c_off = y.c_off; a.src_bytes = src_bytes;
+    a.fix128 = fix128 ? 1 : 0;
+    out->push_back(make_step(n.name, "d2s_i8", 0, bytes, [a](hipStream_t s) { return launch_d2s_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
 int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out)
 {
     const std::string node = in.name + "+" + cn.name + "+" + n.name;

@@ -868,10 +868,10 @@ static int plan_conv_node_u8(tamd_graph* g, size_t ni, std::vector<char>* fused,
 int plan_u8(tamd_graph* g)
 {
     // concat-by-offset: when an input carries the concat output's (scale, zero point) the reference's per-element rescale
-    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample / interp whose only
+    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample / interp / depthtospace whose only
     // consumer is that concat writes in place
     if (plan_nchw_buffers(g, 1, [](const HNode& pn, const HTensor& xi, const HTensor& y) {
-            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE || pn.op == TAMD_OP_INTERP) && !xi.scales.empty() && !y.scales.empty()
+            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE || pn.op == TAMD_OP_INTERP || pn.op == TAMD_OP_DEPTHTOSPACE) && !xi.scales.empty() && !y.scales.empty()
                    && xi.scales[0] == y.scales[0] && (xi.zps.empty() ? 0 : xi.zps[0]) == (y.zps.empty() ? 0 : y.zps[0]);
         }))
         return -1;
@@ -944,6 +944,7 @@ int plan_u8(tamd_graph* g)
         case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
         case TAMD_OP_SLICE: rc = plan_slice_u8(g, n, slice_next[ni] - 1, &out); break;      // one slice_u8 launch, the Slice behind it inside
         case TAMD_OP_TRANSPOSE: rc = plan_transpose(g, n, -1, &out); break;      // one launch; the Reshapes around it are views
+        case TAMD_OP_DEPTHTOSPACE: rc = plan_depthtospace(g, n, false, &out); break;      // one d2s_u8 launch (d2s.hip)
         case TAMD_OP_CROP:                                      // alone: slice_u8 over the box; behind a nearest Interp: that launch, shifted
             rc = crop_interp[ni] ? plan_interp(g, g->nodes[crop_interp[ni] - 1], &out, &n) : plan_crop_u8(g, n, &out);
             break;

@@ -381,6 +381,34 @@ struct TransposeArgs {
 };
 enum { kTransposeGather = 0, kTransposeRows = 1, kTransposeTile = 2 };
 
+// DepthToSpace of a quantised graph (d2s.hip), the CRD order of depthtospace_ref.c: raw bytes, no map --
+//   out[n, s, h, w] = in[n, s * r * r + (h % r) * r + (w % r), h / r, w / r]
+// uint8: x dense NCHW (N, C * r * r, H, W); y dense NCHW (N, C, H * r, W * r), or a channel range of a Concat's NCHW buffer (out_img /
+// out_c0: planes at any byte offset)
+// which of the two forms a DepthToSpace node takes when TAMD_PIN=d2s_form does not say: 1, the kernels of d2s.hip, from this many output
+// bytes on; below, 0: the canonical gather of transpose.hip (where the output is one dense run, which is all that kernel writes).  What
+// was measured decides it (profiles/d2s.txt): from 1 MiB to 14 MB d2s_u8 and d2s_i8 are ahead of the gather with the ranges apart
+// (2.67 against 4.72 us at 1 MiB, 4.58 against 30.3 us at 11 MB); at 256 KB and 389 KB the gather is ahead in uint8 (3.05 against 3.39 us,
+// 3.03 against 4.57 us) and level in int8 (2.63 against 2.64 us).  Between 389 KB and 1 MiB nothing was measured: the threshold stands at
+// the smallest size measured as a win
+constexpr size_t kD2sNewFormFromBytes = (size_t)1 << 20;
+struct D2sU8Args {
+    const uint8_t* x; uint8_t* y;
+    int N, C, H, W;                // C: OUTPUT channels; H, W: the INPUT map
+    int r;
+    long out_img; int out_c0;      // bytes per image of the buffer y lies in, first channel of y in it
+};
+// int8: NHWC with padded pixel strides.  x: first channel of the input (a view's channel offset applied), pixel stride cs_in, read where
+// it lies; y: base of the output buffer, pixel stride ldc, channel offset c_off (a concat view).  Whole 16-byte channel vectors are
+// stored, the lanes from C on as ZERO: c_off, ldc multiples of 16, c_off + rup(C, 16) <= ldc (launch_d2s_i8 checks)
+struct D2sI8Args {
+    const int8_t* x; int8_t* y;
+    int N, C, H, W;                // C: OUTPUT channels; H, W: the INPUT map
+    int r, cs_in, ldc, c_off;
+    size_t src_bytes;              // bytes of the buffer x points into, from x on: every read stays below (launch_d2s_i8 checks)
+    int fix128;                    // 1: the output is a view of a Concat of several inputs, whose copy stores 127 for the byte -128 (epilogue.h: fix128_4)
+};
+
 // The top-down merge of a feature pyramid in a uint8 graph, nearest Interp -> Crop -> same-shape Eltwise, as one launch (topdown.hip).
 // All three tensors dense NCHW; lat and y have the output's dims (N, C, OH, OW) and are 16-byte aligned.  Per output byte
 //   u = table[small[n][c][iy[h]][ix[w]]]          (the Interp's byte map; iy / ix: its index vectors, shifted and cut by the Crop's box)
@@ -560,6 +588,8 @@ hipError_t launch_chan_map_g2(const ChanMapG2Args& a, hipStream_t s);
 hipError_t launch_chan_map_u8(const ChanMapU8Args& a, hipStream_t s);
 hipError_t launch_slice_u8(const SliceU8Args& a, hipStream_t s);
 hipError_t launch_topdown_u8(const TopdownU8Args& a, hipStream_t s);
+hipError_t launch_d2s_u8(const D2sU8Args& a, hipStream_t s);
+hipError_t launch_d2s_i8(const D2sI8Args& a, hipStream_t s);
 // which forms a geometry is legal in, and the default among them (transpose.hip: the one place it is decided)
 bool transpose_form_legal(const TransposeArgs& a, int form);
 int transpose_default_form(const TransposeArgs& a);

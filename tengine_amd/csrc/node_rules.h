@@ -453,6 +453,52 @@ inline const char* crop_refusal(const tamd_crop_param* p, int dtype, int input_n
     return nullptr;
 }
 
+// DepthToSpace: the two quantised kernels of the reference (depthtospace_ref.c; d2s.hip).  fp32 graphs keep the node on the CPU device
+inline bool depthtospace_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// what depthtospace_refusal resolves for its callers: the block size, the output's dims as the reference infers them
+// (N, C / r^2, H * r, W * r: depthtospace.c infer_shape) and the move as the SIX axes of x.reshape(N, outc, r, r, H, W) in the output's
+// order (0, 1, 4, 2, 5, 3): view_dims[] and order[] are what transpose_canon takes (the form-0 baseline of the planners)
+struct DepthToSpaceGeom {
+    int r;
+    int out_dims[4];
+    int view_dims[6], order[6];
+};
+// One DepthToSpace node: nullptr when the device runs it (*geom resolved; may be null), else the reason.  out_dims: the output's dims
+// where the caller has them (null: not checked).  The bytes are the input's own (depthtospace_ref.c reads no quantisation VALUE of either
+// tensor, and the int8 byte -128 stays -128), so the two tensors' parameters may differ; only that both carry one pair is asked.
+//  - another rank: run() indexes dims[0 .. 3] whatever the tensor has
+//  - block_size < 1: the reference divides by it
+//  - C % r^2 != 0: the reference computes outc = C / r^2 rounded down and silently drops the channels behind outc * r^2
+inline const char* depthtospace_refusal(const tamd_depthtospace_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, size_t out_quant,
+                                        int out_dim_num, const int* out_dims, DepthToSpaceGeom* geom)
+{
+    if (!p) return "DepthToSpace needs its parameter";
+    if (!depthtospace_on_device(dtype)) return "DepthToSpace runs on the device in int8 and uint8 graphs only";
+    if (in_dim_num != 4) return "DepthToSpace runs on the device on 4-D tensors only";
+    if (p->block_size < 1) return "DepthToSpace: the block size must be at least 1";
+    for (int i = 0; i < 4; i++) if (in_dims[i] < 1) return "DepthToSpace: every dimension must be at least 1";
+    const long r = p->block_size;
+    if (r > 0x7fff || (long)in_dims[1] % (r * r) != 0) return "DepthToSpace: the channel count is not a multiple of the block size squared (the reference would drop channels)";
+    if (in_const) return "DepthToSpace: the input must not be a constant";
+    if (in_quant != 1 || out_quant != 1) return "DepthToSpace needs per-tensor quant params on both sides";
+    const long oh = (long)in_dims[2] * r, ow = (long)in_dims[3] * r;
+    if ((long)in_dims[0] * in_dims[1] > 0x7fffffffL - 64 || (long)in_dims[0] * in_dims[1] * in_dims[2] > 0x7fffffffL - 64
+        || (long)in_dims[0] * in_dims[1] * in_dims[2] * in_dims[3] > 0x7fffffffL - 64 || oh > 0x7fffffffL - 64 || ow > 0x7fffffffL - 64)
+        return "DepthToSpace: the tensor has more than 2^31 elements";                             // 32-bit positions in the kernels
+    DepthToSpaceGeom dg;
+    dg.r = (int)r;
+    dg.out_dims[0] = in_dims[0]; dg.out_dims[1] = (int)(in_dims[1] / (r * r)); dg.out_dims[2] = (int)oh; dg.out_dims[3] = (int)ow;
+    const int view[6] = {in_dims[0], dg.out_dims[1], (int)r, (int)r, in_dims[2], in_dims[3]}, order[6] = {0, 1, 4, 2, 5, 3};
+    for (int i = 0; i < 6; i++) { dg.view_dims[i] = view[i]; dg.order[i] = order[i]; }
+    if (out_dims) {
+        if (out_dim_num != 4) return "DepthToSpace: the output does not have the dims the reference infers";
+        for (int i = 0; i < 4; i++)
+            if (out_dims[i] != dg.out_dims[i]) return "DepthToSpace: the output does not have the dims the reference infers";
+    }
+    if (geom) *geom = dg;
+    return nullptr;
+}
+
 // PReLU: the two quantised kernels of the reference (prelu_ref.c; prelu.hip).  fp32 graphs keep the node on the CPU device
 inline bool prelu_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
 // One PReLU node: nullptr when the device runs it, else the reason.  input_num: the node's inputs ([data, slope]); slope_data: the

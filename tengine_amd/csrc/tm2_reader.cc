@@ -86,6 +86,7 @@ int map_op(uint32_t t)
     case 70: return TAMD_OP_HARDSWISH;
     case 71: return TAMD_OP_INTERP;
     case 77: return TAMD_OP_TRANSPOSE;
+    case 80: return TAMD_OP_DEPTHTOSPACE;
     case 87: return TAMD_OP_CLIP;
     case 97: return TAMD_OP_MISH;
     default: return -1;
@@ -231,6 +232,7 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 for (size_t i = 0; i < order.size() && i < 8; i++) p.transpose.order[i] = (int)order[i];
                 break;
             }
+            case TAMD_OP_DEPTHTOSPACE: p.d2s.block_size = r.i32(po); break;      // TM2_DepthToSpaceParam :942-945 {block_size} (tm2_depthtospace.c)
             case TAMD_OP_CROP: {                               // TM2_CropParam :812-823 {num_args, offset_c, offset_h, offset_w, crop_h, crop_w,
                 tamd_crop_param& q = p.crop;                   // bool center_crop + 3 bytes of padding, axis, flag} (tm2_crop.c:42-61)
                 q.num_args = r.i32(po); q.offset_c = r.i32(po + 4); q.offset_h = r.i32(po + 8); q.offset_w = r.i32(po + 12);

@@ -47,6 +47,7 @@ extern "C" {
 #include "concat_param.h"
 #include "convolution_param.h"
 #include "crop_param.h"
+#include "depthtospace_param.h"
 #include "eltwise_param.h"
 #include "fc_param.h"
 #include "flatten_param.h"
@@ -112,6 +113,9 @@ const OpRow kOps[] = {
     // the cut of RetinaFace's top-down pyramid (csrc/topdown.hip, csrc/slice.hip): a box of raw bytes in uint8 graphs.  The reference has no
     // int8 kernel, and an fp32 graph keeps the node on the CPU device (which forms and boxes: tamd_node_supported)
     {OP_CROP, TAMD_OP_CROP, true},
+    // sub-pixel convolution's shuffle (csrc/d2s.hip): ESPCN / EDSR tails, torch's PixelShuffle -- the two quantised kernels of the
+    // reference, raw bytes.  An fp32 graph keeps the node on the CPU device (which shapes: tamd_node_supported)
+    {OP_DEPTHTOSPACE, TAMD_OP_DEPTHTOSPACE, true},
 };
 
 const OpRow* find_op(int op)
@@ -174,7 +178,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_transpose_param transpose; tamd_batchnorm_param bn;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_depthtospace_param d2s; tamd_transpose_param transpose; tamd_batchnorm_param bn;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -245,6 +249,9 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
         s->bn = {p->rescale_factor, p->eps, p->caffe_flavor};
         break;
     }
+    case TAMD_OP_DEPTHTOSPACE:       // depthtospace_param.h: the one field
+        s->d2s = tamd_depthtospace_param{((const struct depthtospace_param*)n->op.param_mem)->block_size};
+        break;
     case TAMD_OP_CROP: {             // crop_param.h, field for field
         const struct crop_param* p = (const struct crop_param*)n->op.param_mem;
         s->crop = tamd_crop_param{p->num_args, p->offset_c, p->offset_h, p->offset_w, p->crop_h, p->crop_w, p->center_crop, p->axis, p->flag};

@@ -115,6 +115,15 @@ class _B:
         self.g.add_node(name, "Upsample", [x], [y], scale=float(scale))
         return y
 
+    def depth_to_space(self, name, x, block_size=2):
+        """sub-pixel convolution's shuffle (torch.nn.PixelShuffle, the CRD order): (N, C, H, W) -> (N, C / r^2, H * r, W * r)"""
+        n, c, h, w = self.dims(x)
+        r = int(block_size)
+        assert r >= 1 and c % (r * r) == 0, "DepthToSpace: C must be a multiple of block_size squared"
+        y = self.g.add_tensor(name + "/0", [n, c // (r * r), h * r, w * r], DT_FP32)
+        self.g.add_node(name, "DepthToSpace", [x], [y], block_size=r)
+        return y
+
     def permute(self, name, x, order=(0, 2, 3, 1)):
         d = self.dims(x)
         y = self.g.add_tensor(name + "/0", [d[i] for i in order], DT_FP32)

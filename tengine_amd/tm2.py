@@ -32,7 +32,7 @@ OPTYPE = {
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55, "Crop": 56,
-    "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "Clip": 87, "Mish": 97,
+    "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "DepthToSpace": 80, "Clip": 87, "Mish": 97,
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
@@ -197,6 +197,8 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
     if op == "Crop":            # TM2_CropParam (tm2_format.h:812-823): six int32, a one-byte bool and three bytes of padding, two int32
         v = struct.unpack_from("<6iB3x2i", b, off)
         return dict(zip(CROP_FIELDS, v))
+    if op == "DepthToSpace":    # TM2_DepthToSpaceParam (tm2_format.h:942-945): {block_size}
+        return {"block_size": struct.unpack_from("<i", b, off)[0]}
     if op == "Transpose":       # TM2_TransposeParam (tm2_format.h:929-932): {offset_tr_shape -> TM2_Vector_dims}
         voff = struct.unpack_from("<I", b, off)[0]
         n = struct.unpack_from("<I", b, voff)[0] if voff else 0
@@ -297,6 +299,8 @@ def write_tm2(g: Graph) -> bytes:
         elif n.op == "Crop":     # TM2_CropParam; the defaults are crop.c's init_op (axis 2, everything else 0)
             q = n.params
             pb = struct.pack("<6iB3x2i", *[int(q.get(k, 2 if k == "axis" else 0)) for k in CROP_FIELDS])
+        elif n.op == "DepthToSpace":  # TM2_DepthToSpaceParam {block_size}; the default is depthtospace.c's init_op (1)
+            pb = struct.pack("<i", int(n.params.get("block_size", 1)))
         elif n.op == "Transpose":  # TM2_TransposeParam {offset_tr_shape -> TM2_Vector_dims}; tr_shape None: TM2_NOT_SET, a node no loader accepts
             order = n.params.get("tr_shape")
             pb = struct.pack("<I", bl.vec_i32(order) if order is not None else 0)
