@@ -139,6 +139,16 @@ enum {
      * stays -128.  Other ranks, a block size below 1, a channel count that r^2 does not divide (the reference then silently drops
      * channels), a constant input and per-channel parameters are refused by name; fp32 graphs keep the node on the CPU device */
     TAMD_OP_DEPTHTOSPACE = 34,
+    /* 35: reserved, never supported (like 21, 24, 27, 29, 31 and 33: tests/test_d2s_cpu.py holds the code to that answer) */
+    /* the nearest up-sampling of an ONNX Upsample (darknet YOLOv3 / YOLOv4 exports, opset <= 9 torch exports) and caffe's Resize layer;
+     * tm2 operator 54 --, int8 / uint8 graphs: param tamd_resize_param.  Input (1, C, H, W); the output is
+     * (1, C, (int)(H * scale_h), (int)(W * scale_w)) (resize.c infer_shape) and output pixel (i, j) takes input pixel
+     * (min((int)(i * (1.f / scale_h)), H - 1), min((int)(j * (1.f / scale_w)), W - 1)) through the byte map between the two tensors'
+     * quantisation parameters (resize_ref.c:261-381; tamd_resize_indices, tamd_resize_table).  The reference defines the operator for
+     * batch 1 only (its loop over the batch moves image 0 every time), and a tm2 file never carries `type`: batch > 1, bilinear (type 1),
+     * other ranks, a constant input, a scale that is not finite and positive, an empty output and per-channel parameters are refused by
+     * name; fp32 graphs keep the node on the CPU device */
+    TAMD_OP_RESIZE = 36,
     TAMD_OP_NUM
 };
 
@@ -165,6 +175,9 @@ typedef struct tamd_relu_param { float negative_slope; } tamd_relu_param;   /* r
 /* field meaning == struct batchnorm_param (batchnorm_param.h) */
 typedef struct tamd_batchnorm_param { float rescale_factor, eps; int caffe_flavor; } tamd_batchnorm_param;
 typedef struct tamd_depthtospace_param { int block_size; } tamd_depthtospace_param;   /* depthtospace_param.h */
+/* == struct resize_param (resize_param.h): type 0 nearest, 1 bilinear.  The tm2 loader fills scale_h from TM2_ResizeParam.scale_x and
+ * scale_w from .scale_y and does not read .type (tm2_resize.c:42-54) */
+typedef struct tamd_resize_param { float scale_w, scale_h; int type; } tamd_resize_param;
 typedef struct tamd_eltwise_param { int type; int caffe_flavor; float shift, power, scale; } tamd_eltwise_param;
 typedef struct tamd_concat_param { int axis; } tamd_concat_param;
 typedef struct tamd_upsample_param { float scale; } tamd_upsample_param;
@@ -345,6 +358,16 @@ TAMD_API int tamd_batchnorm_table(const tamd_batchnorm_param* param, float gamma
  * extent is not positive */
 TAMD_API int tamd_interp_table(int dtype, float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
 TAMD_API int tamd_interp_indices(int in_extent, int out_extent, float scale, int* idx);
+/* the two host-built operands of a nearest Resize node (csrc/resize_tables.cc; no GPU needed).
+ * tamd_resize_table: table[b] = the output byte for input byte b between tensors of these quantisation parameters (resize_ref.c:288,
+ * :310-315: int8 saturates at +-127, so -128 comes out as -127 even between equal parameters; :349, :371-376: uint8 at 0 .. 255) -- the
+ * lines of tamd_interp_table, and its implementation.  0; -1 for a dtype other than int8 / uint8; -2 when one of the 256 values before
+ * its conversion to int is not finite or lies outside int: the reference's conversion is undefined there and the node is refused.
+ * tamd_resize_indices: idx[o] = min((int)((float)o * (1.f / scale)), in_extent - 1) for o in [0, out_extent), the source row / column
+ * of output row / column o (resize_ref.c:298, :301, :409-410); `scale` is the node's own scale_h / scale_w, the reciprocal is formed
+ * here.  0, or -1 when the scale is not finite and positive, an extent is not positive or a product leaves int */
+TAMD_API int tamd_resize_table(int dtype, float in_scale, int in_zp, float out_scale, int out_zp, unsigned char table[256]);
+TAMD_API int tamd_resize_indices(int in_extent, int out_extent, float scale, int* idx);
 /* the two host-built operands of the channel-moving operators (csrc/chanmap_tables.cc; no GPU needed).
  * tamd_shuffle_sources: src[o] = the input channel that output channel o of a ShuffleChannel node takes: src[group * j + i] =
  * (channels / group) * i + j (shuffle_channel_ref.c).  0, or -1 for group < 1 or channels % group != 0 -- the reference never writes the

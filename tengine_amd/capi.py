@@ -26,7 +26,7 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_eltwise_table", "tamd_eltwise_scalar", "tamd_eltwise_pair", "tamd_batchnorm_table", "tamd_interp_table", "tamd_interp_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_eltwise_table", "tamd_eltwise_scalar", "tamd_eltwise_pair", "tamd_batchnorm_table", "tamd_interp_table", "tamd_interp_indices", "tamd_resize_table", "tamd_resize_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
@@ -97,6 +97,9 @@ def lib():
             L.tamd_batchnorm_table.argtypes = [vp] + [C.c_float] * 5 + [ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_interp_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
+        if hasattr(L, "tamd_resize_table"):       # (guarded like the slots: an older build has no Resize)
+            L.tamd_resize_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
+            L.tamd_resize_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
         L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_slice_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
@@ -132,6 +135,28 @@ OP_DEPTHTOSPACE = 34     # (33: reserved too)
 
 class DepthToSpaceParam(C.Structure):  # tamd_depthtospace_param
     _fields_ = [("block_size", C.c_int)]
+OP_RESIZE = 36           # (35: reserved too)
+
+
+class ResizeParam(C.Structure):       # tamd_resize_param
+    _fields_ = [("scale_w", C.c_float), ("scale_h", C.c_float), ("type", C.c_int)]
+
+
+def resize_table(dtype, in_scale, in_zp, out_scale, out_zp):
+    """tamd_resize_table(): the 256 output bytes (uint8 array, indexed by the input byte's bit pattern) of a nearest Resize node between
+    tensors of these quantisation parameters; None for a type the device does not run and where the reference's conversion to int is
+    undefined.  Needs no GPU."""
+    tab = (C.c_ubyte * 256)()
+    rc = lib().tamd_resize_table(dtype, in_scale, in_zp, out_scale, out_zp, tab)
+    return None if rc != 0 else np.frombuffer(tab, dtype=np.uint8).copy()
+
+
+def resize_indices(in_extent, out_extent, scale):
+    """tamd_resize_indices(): the source row (column) of every output row (column) of a nearest Resize node whose scale_h (scale_w) is
+    `scale`: min((int)(o * (1.f / scale)), in_extent - 1); None for a scale that is not finite and positive.  Needs no GPU."""
+    idx = (C.c_int * max(out_extent, 1))()
+    rc = lib().tamd_resize_indices(in_extent, out_extent, scale, idx)
+    return None if rc != 0 else np.array(idx[:out_extent], dtype=np.int32)
 
 
 class CropParam(C.Structure):         # tamd_crop_param

@@ -57,6 +57,7 @@ union NodeParam {
     tamd_transpose_param transpose;
     tamd_crop_param crop;
     tamd_depthtospace_param d2s;
+    tamd_resize_param resize;
     tamd_batchnorm_param bn;
 };
 
@@ -362,6 +363,13 @@ const char* depthtospace_refusal_of(const tamd_graph* g, const HNode& n, bool ch
 // the output is one dense run, the canonical gather of transpose.hip with the identity map.  fix128 (int8): the output lies in the
 // buffer of a Concat of several inputs, whose copy stores 127 for the byte -128
 int plan_depthtospace(tamd_graph* g, HNode& n, bool fix128, std::vector<Step>* out);
+// resize_refusal (node_rules.h) asked of a node of this graph: infer_shapes (check_out false: the output's dims are not made yet),
+// validate_graph and the planners.  *geom (may be null): the output's dims, the two index vectors, the byte map, the whole-number factors
+const char* resize_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, ResizeGeom* geom);
+// a nearest Resize node of an int8 (NHWC) or uint8 (NCHW) graph as ONE launch.  Form 0: interp_nearest_i8 / interp_nearest_u8 (interp.hip)
+// fed with Resize's index vectors and table, legal for every accepted node.  Form 1: resize_rep_i8 / resize_rep_u8 (resize.hip), legal
+// at whole-number factors (ResizeGeom::sh / sw).  TAMD_PIN=resize_form=0|1 chooses; the output's size otherwise (kernels.h: kResizeRepFromBytesU8 / I8)
+int plan_resize(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // eltwise_refusal (node_rules.h) asked of a node of this graph: validate_graph and the int8 / uint8 Eltwise planners.  *gated: -1 the
 // same-shape form, 0 | 1 which input is x of the channel-gate form x (N, C, H, W) op gate (N, C, 1, 1), kEltScalar / kEltUnary the two
 // forms that run by table; table[256]: the byte map of those two (may be null)

@@ -86,6 +86,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_CROP) return crop_on_device(dtype);          // a box of raw bytes, uint8 (which forms and boxes: tamd_node_supported)
     if (op == TAMD_OP_BATCHNORM) return batchnorm_on_device(dtype);  // a byte map per channel, uint8 (which ranks and statistics: tamd_node_supported)
     if (op == TAMD_OP_DEPTHTOSPACE) return depthtospace_on_device(dtype);      // raw bytes shuffled, int8 / uint8 (which shapes: tamd_node_supported)
+    if (op == TAMD_OP_RESIZE) return resize_on_device(dtype);      // nearest by byte map, int8 / uint8 (which scales and shapes: tamd_node_supported)
     if (op == TAMD_OP_PRELU) return prelu_on_device(dtype);        // int8 / uint8 (which ranks and slopes: tamd_node_supported)
     switch (op) {
     case TAMD_OP_INPUT: case TAMD_OP_CONST: case TAMD_OP_CONV: case TAMD_OP_FC: case TAMD_OP_POOL: case TAMD_OP_RELU:
@@ -256,6 +257,15 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
                                     (size_t)out[0].quant_num, out[0].dim_num, out[0].dims, nullptr)
                == nullptr;
     }
+    case TAMD_OP_RESIZE: {
+        if (n_in != 1 || !in) return 0;
+        const bool have_q = in[0].quant_num == 1 && in[0].scales && out[0].quant_num == 1 && out[0].scales;
+        ResizeQuant q{};
+        if (have_q) q = ResizeQuant{in[0].scales[0], in[0].zero_points ? in[0].zero_points[0] : 0, out[0].scales[0], out[0].zero_points ? out[0].zero_points[0] : 0};
+        return resize_refusal((const tamd_resize_param*)n->param, dt, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                              (size_t)out[0].quant_num, have_q ? &q : nullptr, out[0].dim_num, out[0].dims, nullptr)
+               == nullptr;
+    }
     case TAMD_OP_CROP: {
         if (n_in != 2 || !in) return 0;
         return crop_refusal((const tamd_crop_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, in[1].dim_num,
@@ -353,6 +363,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_TRANSPOSE: n.p.transpose = *(const tamd_transpose_param*)d->param; break;
         case TAMD_OP_CROP: n.p.crop = *(const tamd_crop_param*)d->param; break;
         case TAMD_OP_DEPTHTOSPACE: n.p.d2s = *(const tamd_depthtospace_param*)d->param; break;
+        case TAMD_OP_RESIZE: n.p.resize = *(const tamd_resize_param*)d->param; break;
         case TAMD_OP_BATCHNORM: n.p.bn = *(const tamd_batchnorm_param*)d->param; break;
         default: break;
         }

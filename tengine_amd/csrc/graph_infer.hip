@@ -276,6 +276,13 @@ int infer_shapes(tamd_graph* g)
             y.dims.assign(dg.out_dims, dg.out_dims + 4);
             break;
         }
+        case TAMD_OP_RESIZE: {            // resize.c infer_shape: (N, C, (int)(H * scale_h), (int)(W * scale_w)).  What the device does not run is refused HERE, by name
+            ResizeGeom rg;
+            const char* why = resize_refusal_of(g, n, false, &rg);
+            if (why) { set_error("resize %s: %s", n.name.c_str(), why); return -1; }
+            y.dims.assign(rg.out_dims, rg.out_dims + 4);
+            break;
+        }
         case TAMD_OP_PRELU: y.dims = x.dims; y.dtype = x.dtype; break;      // prelu.c: the input's shape; the type is the data's, not the fp16 slope's
         case TAMD_OP_PERMUTE: {           // permute.c infer_shape: out.dims[i] = in.dims[order[i]]
             if (x.dims.size() != 4) { set_error("permute %s: only 4-D tensors", n.name.c_str()); return -1; }
@@ -370,6 +377,10 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_DEPTHTOSPACE) {
             const char* why = depthtospace_refusal_of(g, n, true, nullptr);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_RESIZE) {
+            const char* why = resize_refusal_of(g, n, true, nullptr);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_TRANSPOSE) {

@@ -129,7 +129,7 @@ static int plan_dense(tamd_graph* g, I8Layout& L)
 // channel count / offset not a multiple of 16; produced or also consumed by a kernel that does not address channel
 // slices; a graph input) keeps its own buffer and is copied by concat_copy_i8 at the concat's position.
 // the operators whose launches address a channel slice of a wider buffer, on the side they read and on the side they write
-static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP || op == TAMD_OP_DEPTHTOSPACE; }
+static bool slice_capable(int op) { return op == TAMD_OP_CONV || op == TAMD_OP_FC || op == TAMD_OP_POOL || op == TAMD_OP_UPSAMPLE || op == TAMD_OP_INTERP || op == TAMD_OP_DEPTHTOSPACE || op == TAMD_OP_RESIZE; }
 // .. and on the side they read alone.  Split and ShuffleChannel are NOT written in place into a Concat's buffer: they hand on the byte
 // -128 where their input holds it, and the reference's Concat of several inputs turns that byte into 127 even between equal scales
 // (concat_kernel_ref_int8.c:83-84) -- concat_copy_i8 does that, a view would not.  Upsample holds that byte too and IS written in
@@ -935,6 +935,7 @@ int plan_i8(tamd_graph* g)
         case TAMD_OP_ELTWISE: r = plan_eltwise(g, L, ni, &out); break;
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: r = plan_lut(g, n, &out); break;
         case TAMD_OP_INTERP: r = plan_interp(g, n, &out); break;
+        case TAMD_OP_RESIZE: r = plan_resize(g, n, &out); break;      // one launch: interp_nearest_i8 with Resize's operands, or resize_rep_i8 (resize.hip)
         case TAMD_OP_SPLIT: r = plan_split(g, L, n, &out); break;
         case TAMD_OP_SHUFFLECHANNEL: r = plan_shuffle(g, n, &out); break;
         case TAMD_OP_PRELU: r = plan_prelu(g, n, &out); break;

@@ -930,6 +930,82 @@ int plan_depthtospace(tamd_graph* g, HNode& n, bool fix128, std::vector<Step>* o
     return 0;
 }
 
+// ---- nearest Resize of a quantised graph, both types.  Everything the reference decides for the node is decided by resize_refusal
+// (node_rules.h): the output's dims, the two index vectors, the byte map, and whether the vectors are those of whole-number factors
+const char* resize_refusal_of(const tamd_graph* g, const HNode& n, bool check_out, ResizeGeom* geom)
+{
+    if (n.in.size() != 1 || n.out.empty()) return "Resize takes one input";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    const bool have_q = x.scales.size() == 1 && y.scales.size() == 1;
+    ResizeQuant q{};
+    if (have_q) q = ResizeQuant{x.scales[0], x.zps.empty() ? 0 : x.zps[0], y.scales[0], y.zps.empty() ? 0 : y.zps[0]};
+    return resize_refusal(&n.p.resize, x.dtype, (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), have_q ? &q : nullptr,
+                          (int)y.dims.size(), check_out ? y.dims.data() : nullptr, geom);
+}
+
+// One launch, two forms (graph.h).  Both read and write what plan_interp's launches do: int8 (NHWC) reads a concat or Split view in place
+// (another base and pixel stride) and writes a Concat's buffer in place through ldc / c_off -- the table saturates at +-127, so the byte
+// -128 never comes out and the Concat's rule for it (plan_concat_views) does not arise --; uint8 (NCHW) writes a channel range of a
+// Concat's buffer through out_img / out_c0.  Form 0 uploads the two index vectors; form 1 needs none
+int plan_resize(tamd_graph* g, HNode& n, std::vector<Step>* out)
+{
+    ResizeGeom rg;
+    const char* why = resize_refusal_of(g, n, true, &rg);
+    if (why) { set_error("resize %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& y = g->tensors[n.out[0]];
+    if (y.dtype != x.dtype || !rg.have_table) { set_error("resize %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const int by_size = (size_t)y.elems() >= (x.dtype == TAMD_DT_INT8 ? kResizeRepFromBytesI8 : kResizeRepFromBytesU8) ? 1 : 0;      // (kernels.h: what was measured)
+    const bool rep = rg.sh >= 1 && rg.sw >= 1 && tamd_pin_int("resize_form", by_size) == 1;
+    std::vector<unsigned> table(64);
+    memcpy(table.data(), rg.table, 256);
+    int* diy = nullptr; int* dix = nullptr; unsigned* dtable = nullptr;
+    if (upload(g, table, &dtable)) return -1;
+    if (!rep && (upload(g, rg.iy, &diy) || upload(g, rg.ix, &dix))) return -1;
+    const double bytes = (double)x.elems() + (double)y.elems();
+    if (x.dtype == TAMD_DT_INT8) {
+        // whole 16-byte vectors: up to the padding channels of its own buffers, never into a neighbour's slice (a view has c % 16 == 0)
+        const int cv = rup(x.c, 16);
+        if (x.nchw_raw || y.nchw_raw || x.cs <= 0 || y.cs <= 0 || x.cs % 16 || y.cs % 16 || x.c_off % 16 || y.c_off % 16 || x.c_off + cv > x.cs || y.c_off + cv > y.cs) {
+            set_error("resize %s: channel slice not 16-byte aligned", n.name.c_str());
+            return -1;
+        }
+        if (rep) {
+            ResizeRepI8Args a{};
+            a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+            a.C = x.c; a.H = x.h; a.W = x.w; a.sh = rg.sh; a.sw = rg.sw; a.cs_in = x.cs; a.ldc = y.cs; a.c_off = y.c_off; a.table = dtable;
+            out->push_back(make_step(n.name, "resize_rep_i8", 0, bytes, [a](hipStream_t s) { return launch_resize_rep_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+            return 0;
+        }
+        InterpI8Args a{};
+        a.x = (const int8_t*)x.dptr + x.c_off; a.y = (int8_t*)y.dptr;
+        a.N = 1; a.H = x.h; a.W = x.w; a.C = x.c; a.cs_in = x.cs;
+        a.OH = y.h; a.OW = y.w; a.ldc = y.cs; a.c_off = y.c_off;
+        a.iy = diy; a.ix = dix; a.table = dtable;
+        out->push_back(make_step(n.name, "interp_nearest_i8", 0, bytes, [a](hipStream_t s) { return launch_interp_i8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+        return 0;
+    }
+    if (x.is_view) { set_error("resize %s reads a concat view: not supported in a uint8 graph", n.name.c_str()); return -1; }
+    int identity = 1;
+    for (int b = 0; b < 256; b++) identity &= rg.table[b] == b;
+    if (rep) {
+        ResizeRepU8Args a{};
+        a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+        a.C = x.c; a.H = x.h; a.W = x.w; a.sh = rg.sh; a.sw = rg.sw;
+        a.out_img = nchw_out_img(y); a.out_c0 = y.c_off; a.table = dtable; a.identity = identity;
+        out->push_back(make_step(n.name, "resize_rep_u8", 0, bytes, [a](hipStream_t s) { return launch_resize_rep_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+        return 0;
+    }
+    InterpU8Args a{};
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+    a.N = 1; a.C = x.c; a.H = x.h; a.W = x.w; a.OH = y.h; a.OW = y.w;
+    a.out_img = nchw_out_img(y); a.out_c0 = y.c_off;
+    a.iy = diy; a.ix = dix; a.table = dtable; a.identity = identity;
+    out->push_back(make_step(n.name, "interp_nearest_u8", 0, bytes, [a](hipStream_t s) { return launch_interp_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    return 0;
+}
+
 int plan_topdown_u8(tamd_graph* g, HNode& in, HNode& cn, HNode& n, std::vector<Step>* out)
 {
     const std::string node = in.name + "+" + cn.name + "+" + n.name;

@@ -868,10 +868,10 @@ static int plan_conv_node_u8(tamd_graph* g, size_t ni, std::vector<char>* fused,
 int plan_u8(tamd_graph* g)
 {
     // concat-by-offset: when an input carries the concat output's (scale, zero point) the reference's per-element rescale
-    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample / interp / depthtospace whose only
+    // roundf((u - zp) * 1 + zp) is the identity (concat_kernel_ref_uint8.c:309-352), so a conv / relu / upsample / interp / depthtospace / resize whose only
     // consumer is that concat writes in place
     if (plan_nchw_buffers(g, 1, [](const HNode& pn, const HTensor& xi, const HTensor& y) {
-            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE || pn.op == TAMD_OP_INTERP || pn.op == TAMD_OP_DEPTHTOSPACE) && !xi.scales.empty() && !y.scales.empty()
+            return (pn.op == TAMD_OP_CONV || pn.op == TAMD_OP_RELU || pn.op == TAMD_OP_UPSAMPLE || pn.op == TAMD_OP_INTERP || pn.op == TAMD_OP_DEPTHTOSPACE || pn.op == TAMD_OP_RESIZE) && !xi.scales.empty() && !y.scales.empty()
                    && xi.scales[0] == y.scales[0] && (xi.zps.empty() ? 0 : xi.zps[0]) == (y.zps.empty() ? 0 : y.zps[0]);
         }))
         return -1;
@@ -940,6 +940,7 @@ int plan_u8(tamd_graph* g)
         // the byte-map planners both quantised graphs share (graph_plan_maps.hip): tables, index vectors and plane maps at prerun
         case TAMD_OP_SIGMOID: case TAMD_OP_CLIP: case TAMD_OP_HARDSWISH: case TAMD_OP_MISH: rc = plan_lut(g, n, &out); break;
         case TAMD_OP_INTERP: rc = plan_interp(g, n, &out); break;
+        case TAMD_OP_RESIZE: rc = plan_resize(g, n, &out); break;      // one launch: interp_nearest_u8 with Resize's operands, or resize_rep_u8 (resize.hip)
         case TAMD_OP_SPLIT: rc = plan_split_u8(g, n, &out); break;      // one chan_map_u8 launch per output
         case TAMD_OP_SHUFFLECHANNEL: rc = plan_shuffle_u8(g, n, &out); break;
         case TAMD_OP_SLICE: rc = plan_slice_u8(g, n, slice_next[ni] - 1, &out); break;      // one slice_u8 launch, the Slice behind it inside

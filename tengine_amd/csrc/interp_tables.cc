@@ -18,18 +18,20 @@ namespace {
 // scale of 0 gets there; in range it is the plain truncation
 int to_int(double d) { return d >= -2147483648.0 && d < 2147483648.0 ? (int)d : INT32_MIN; }
 
-// interp_ref.c:271 / :380 then :348 / :457 for one element: ((float)q - (float)zero) * scale; round(f / scale + zero) -- the division
-// and the addition in float (the zero point converted to float), then the DOUBLE round of libm
-int requant(int q, float in_scale, int in_zp, float out_scale, int out_zp)
-{
-    const float f = ((float)q - (float)in_zp) * in_scale;
-    const float scaled = f / out_scale + (float)out_zp;
-    return to_int(round((double)scaled));
-}
+int requant(int q, float in_scale, int in_zp, float out_scale, int out_zp) { return to_int(tamd::interp_rounded(q, in_scale, in_zp, out_scale, out_zp)); }
 
 }  // namespace
 
 namespace tamd {
+
+// interp_ref.c:271 / :380 then :348 / :457 for one element: ((float)q - (float)zero) * scale; round(f / scale + zero) -- the division
+// and the addition in float (the zero point converted to float), then the DOUBLE round of libm
+double interp_rounded(int q, float in_scale, int in_zp, float out_scale, int out_zp)
+{
+    const float f = ((float)q - (float)in_zp) * in_scale;
+    const float scaled = f / out_scale + (float)out_zp;
+    return round((double)scaled);
+}
 
 bool interp_resolve(const tamd_interp_param& p, int in_h, int in_w, InterpGeom* g)
 {

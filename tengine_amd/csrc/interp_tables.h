@@ -13,4 +13,9 @@ struct InterpGeom { float height_scale, width_scale; int out_h, out_w; };
 // some pairs (11 -> 13 gives 12, 7 -> 31 gives 30) it then shrinks the tensor under a kernel that was planned for the other size
 bool interp_resolve(const tamd_interp_param& p, int in_h, int in_w, InterpGeom* g);
 
+// the value of one element before its conversion to int: round(((float)q - (float)in_zp) * in_scale / out_scale + (float)out_zp), the
+// division and the addition in float, the rounding the double round().  tamd_interp_table converts and clamps it; resize_ref.c has the
+// same two lines (:288 / :349, :310 / :371), so tamd_resize_table (resize_tables.cc) is built from it too
+double interp_rounded(int q, float in_scale, int in_zp, float out_scale, int out_zp);
+
 }  // namespace tamd

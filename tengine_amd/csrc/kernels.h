@@ -409,6 +409,38 @@ struct D2sI8Args {
     int fix128;                    // 1: the output is a view of a Concat of several inputs, whose copy stores 127 for the byte -128 (epilogue.h: fix128_4)
 };
 
+// Nearest Resize at whole-number factors, the replicate form (resize.hip): output pixel (h, w) = table[input pixel (h / sh, w / sw)],
+// OH = H * sh, OW = W * sw, ONE image (the reference defines the operator for batch 1 only).  A lane owns SOURCE data, maps it once and
+// stores its copies; no index vectors, no divisions by the output's extents.  Form 0 of a Resize node is interp.hip's kernel fed with
+// Resize's index vectors and table (InterpI8Args / InterpU8Args), legal for every node; this form is legal where node_rules.h:
+// ResizeGeom::sh / sw are set.
+// which form a Resize node takes when TAMD_PIN=resize_form does not say: 1 from this many OUTPUT bytes on, where it is legal; 0 below.
+// What was measured decides it (profiles/resize.txt, x2, us per launch, ranges of seven alternating rounds).  uint8: resize_rep_u8 is
+// ahead with the ranges apart at 1.6 MB (3.23 against 5.51), 4 MiB (3.69 against 11.69) and 6.5 MB (4.55 against 17.12), and behind at
+// 205 KB (4.06 against 3.65, ranges touching).  int8: resize_rep_i8 is ahead with the ranges apart at 6.5 MB alone (3.70 against 4.78);
+// at 205 KB, 1.6 MB and 4 MiB its median is lower (3.02 / 3.22 / 3.38 against 3.22 / 3.43 / 3.82) but the ranges overlap.  Each
+// threshold stands at the smallest size measured as a win; between the measured sizes nothing is known
+constexpr size_t kResizeRepFromBytesU8 = 1638400, kResizeRepFromBytesI8 = 6553600;
+// int8: NHWC with padded pixel strides.  x: first channel of the input (a view's channel offset applied), pixel stride cs_in, read where
+// it lies; y: base of the output buffer, pixel stride ldc, channel offset c_off (a concat view).  Whole 16-byte channel vectors are
+// stored, the lanes from C on as ZERO: c_off, ldc multiples of 16, c_off + rup(C, 16) <= ldc (launch_resize_rep_i8 checks)
+struct ResizeRepI8Args {
+    const int8_t* x; int8_t* y;
+    int C, H, W;                   // the INPUT map
+    int sh, sw, cs_in, ldc, c_off;
+    const unsigned* table;         // [64]: tamd_resize_table's 256 bytes as they lie
+};
+// uint8: x dense NCHW (1, C, H, W); y dense NCHW (1, C, H * sh, W * sw), or a channel range of a Concat's NCHW buffer (out_c0: planes at
+// any byte offset; out_img: the bytes of the image y lies in)
+struct ResizeRepU8Args {
+    const uint8_t* x; uint8_t* y;
+    int C, H, W;                   // the INPUT map
+    int sh, sw;
+    long out_img; int out_c0;
+    const unsigned* table;
+    int identity;                  // the table maps every byte to itself: no lookups
+};
+
 // The top-down merge of a feature pyramid in a uint8 graph, nearest Interp -> Crop -> same-shape Eltwise, as one launch (topdown.hip).
 // All three tensors dense NCHW; lat and y have the output's dims (N, C, OH, OW) and are 16-byte aligned.  Per output byte
 //   u = table[small[n][c][iy[h]][ix[w]]]          (the Interp's byte map; iy / ix: its index vectors, shifted and cut by the Crop's box)
@@ -590,6 +622,8 @@ hipError_t launch_slice_u8(const SliceU8Args& a, hipStream_t s);
 hipError_t launch_topdown_u8(const TopdownU8Args& a, hipStream_t s);
 hipError_t launch_d2s_u8(const D2sU8Args& a, hipStream_t s);
 hipError_t launch_d2s_i8(const D2sI8Args& a, hipStream_t s);
+hipError_t launch_resize_rep_i8(const ResizeRepI8Args& a, hipStream_t s);
+hipError_t launch_resize_rep_u8(const ResizeRepU8Args& a, hipStream_t s);
 // which forms a geometry is legal in, and the default among them (transpose.hip: the one place it is decided)
 bool transpose_form_legal(const TransposeArgs& a, int form);
 int transpose_default_form(const TransposeArgs& a);

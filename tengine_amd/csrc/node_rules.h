@@ -2,6 +2,8 @@
 // stated here once, with the reason for its number.  Only rules that are written at more than one site live here; what a single
 // planner alone decides stays in that planner.
 #pragma once
+#include <math.h>
+
 #include <vector>
 
 #include "kernels.h"
@@ -9,6 +11,7 @@
 #include "interp_tables.h"
 #include "lut_tables.h"
 #include "prelu_tables.h"
+#include "resize_tables.h"
 #include "slice_tables.h"
 #include "transpose_tables.h"
 
@@ -496,6 +499,76 @@ inline const char* depthtospace_refusal(const tamd_depthtospace_param* p, int dt
             if (out_dims[i] != dg.out_dims[i]) return "DepthToSpace: the output does not have the dims the reference infers";
     }
     if (geom) *geom = dg;
+    return nullptr;
+}
+
+// Resize: the nearest mode of the two quantised kernels (resize_ref.c:261-381; interp.hip fed with Resize's operands, resize.hip).  fp32
+// graphs keep the node on the CPU device
+inline bool resize_on_device(int dtype) { return dtype == TAMD_DT_INT8 || dtype == TAMD_DT_UINT8; }
+// what resize_refusal resolves for its callers: the output's dims as the reference infers them ((int)(H * scale_h), (int)(W * scale_w):
+// resize.c:47-48), the source row of every output row and the source column of every output column (tamd_resize_indices), the byte map
+// (tamd_resize_table; have_table: the caller gave the quantisation values) and, where the two index vectors ARE i / sh and j / sw for
+// whole numbers sh, sw >= 1 with OH == H * sh and OW == W * sw, those two numbers (else 0, 0): the replicate form of resize.hip is legal
+// exactly there -- decided on the vectors themselves, not on the scales
+struct ResizeGeom {
+    int out_dims[4];
+    std::vector<int> iy, ix;
+    unsigned char table[256];
+    bool have_table;
+    int sh, sw;
+};
+// the quantisation values of the two tensors, where the caller has them (a support query may not: then the table is not checked, and
+// prerun refuses by name what the query let through)
+struct ResizeQuant { float in_scale; int in_zp; float out_scale; int out_zp; };
+// One Resize node: nullptr when the device runs it (*geom resolved; may be null), else the reason.  out_dims: the output's dims where the
+// caller has them (null: not checked).
+//  - batch > 1: run() calls the whole-tensor routine once per image, and that routine moves the channels of image 0 only; the floats of
+//    the other images are an uninitialised malloc.  No bytes to equal
+//  - type 1 (bilinear): reachable only from a graph built in memory -- the tm2 loader never reads the field -- and not built
+//  - another rank: run() and infer_shape index dims[0 .. 3] whatever the tensor has
+//  - a scale that is not finite and positive: the reference divides 1.f by it
+//  - an output extent of 0: (int)(H * scale_h) with a small scale.  An extent outside int is undefined in the reference
+//  - a table entry that is not finite or lies outside int before its conversion: undefined in the reference
+// Every index lies inside the input by construction (T_MIN(.., h - 1), and a positive scale keeps it >= 0); tamd_resize_indices refuses
+// a product that leaves int
+inline const char* resize_refusal(const tamd_resize_param* p, int dtype, int in_dim_num, const int* in_dims, bool in_const, size_t in_quant, size_t out_quant,
+                                  const ResizeQuant* q, int out_dim_num, const int* out_dims, ResizeGeom* geom)
+{
+    if (!p) return "Resize needs its parameter";
+    if (!resize_on_device(dtype)) return "Resize runs on the device in int8 and uint8 graphs only";
+    if (p->type == 1) return "only nearest Resize (type 0) runs on the device: bilinear stays on the CPU device";
+    if (p->type != 0) return "Resize: the type is neither nearest (0) nor bilinear (1)";
+    if (in_dim_num != 4) return "Resize runs on the device on 4-D tensors only";
+    for (int i = 0; i < 4; i++) if (in_dims[i] < 1) return "Resize: every dimension must be at least 1";
+    if (in_dims[0] != 1) return "Resize: the reference defines the operator for batch 1 only";
+    if (in_const) return "Resize: the input must not be a constant";
+    if (!(p->scale_h > 0.f) || !(p->scale_w > 0.f) || !isfinite(p->scale_h) || !isfinite(p->scale_w)) return "Resize: both scales must be finite and positive";
+    if (in_quant != 1 || out_quant != 1) return "Resize needs per-tensor quant params on both sides";
+    int oh = 0, ow = 0;
+    if (!resize_out_extent(in_dims[2], p->scale_h, &oh) || !resize_out_extent(in_dims[3], p->scale_w, &ow)) return "Resize: an output extent lies outside int";
+    if (oh < 1 || ow < 1) return "Resize: the output is empty";
+    if ((double)in_dims[1] * in_dims[2] * in_dims[3] > (double)(0x7fffffffL - 64) || (double)in_dims[1] * oh * ow > (double)(0x7fffffffL - 64))
+        return "Resize: the tensor has more than 2^31 elements";                                      // 32-bit positions in the kernels
+    if (out_dims) {
+        if (out_dim_num != 4 || out_dims[0] != 1 || out_dims[1] != in_dims[1] || out_dims[2] != oh || out_dims[3] != ow)
+            return "Resize: the output does not have the dims the reference infers";
+    }
+    unsigned char table[256];
+    if (q) {
+        const int rc = tamd_resize_table(dtype, q->in_scale, q->in_zp, q->out_scale, q->out_zp, table);
+        if (rc) return "Resize: a table entry is not finite or lies outside int (the reference's conversion is undefined there)";
+    }
+    ResizeGeom mine;
+    if (!geom) geom = &mine;                                 // (a caller that wants nothing back: the index products are checked all the same)
+    geom->iy.assign((size_t)oh, 0); geom->ix.assign((size_t)ow, 0);
+    if (tamd_resize_indices(in_dims[2], oh, p->scale_h, geom->iy.data()) || tamd_resize_indices(in_dims[3], ow, p->scale_w, geom->ix.data())) return "Resize: a source index leaves int";
+    geom->out_dims[0] = 1; geom->out_dims[1] = in_dims[1]; geom->out_dims[2] = oh; geom->out_dims[3] = ow;
+    geom->have_table = q != nullptr;
+    for (int b = 0; b < 256; b++) geom->table[b] = q ? table[b] : 0;
+    int sh = oh % in_dims[2] == 0 ? oh / in_dims[2] : 0, sw = ow % in_dims[3] == 0 ? ow / in_dims[3] : 0;
+    for (int i = 0; i < oh && sh; i++) if (geom->iy[(size_t)i] != i / sh) sh = 0;
+    for (int j = 0; j < ow && sw; j++) if (geom->ix[(size_t)j] != j / sw) sw = 0;
+    geom->sh = sh && sw ? sh : 0; geom->sw = sh && sw ? sw : 0;
     return nullptr;
 }
 

@@ -81,6 +81,7 @@ int map_op(uint32_t t)
     case 29: return TAMD_OP_SPLIT;
     case 37: return TAMD_OP_SIGMOID;
     case 51: return TAMD_OP_UPSAMPLE;
+    case 54: return TAMD_OP_RESIZE;
     case 55: return TAMD_OP_SHUFFLECHANNEL;
     case 56: return TAMD_OP_CROP;
     case 70: return TAMD_OP_HARDSWISH;
@@ -232,6 +233,9 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 for (size_t i = 0; i < order.size() && i < 8; i++) p.transpose.order[i] = (int)order[i];
                 break;
             }
+            case TAMD_OP_RESIZE:                               // TM2_ResizeParam {scale_x, scale_y, type}: the reference's loader fills scale_h from
+                p.resize.scale_h = r.f32(po); p.resize.scale_w = r.f32(po + 4); p.resize.type = 0;      // scale_x, scale_w from scale_y, and never reads type (tm2_resize.c:50-51)
+                break;
             case TAMD_OP_DEPTHTOSPACE: p.d2s.block_size = r.i32(po); break;      // TM2_DepthToSpaceParam :942-945 {block_size} (tm2_depthtospace.c)
             case TAMD_OP_CROP: {                               // TM2_CropParam :812-823 {num_args, offset_c, offset_h, offset_w, crop_h, crop_w,
                 tamd_crop_param& q = p.crop;                   // bool center_crop + 3 bytes of padding, axis, flag} (tm2_crop.c:42-61)

@@ -56,6 +56,7 @@ extern "C" {
 #include "permute_param.h"
 #include "pooling_param.h"
 #include "priorbox_param.h"
+#include "resize_param.h"
 #include "shuffle_channel_param.h"
 #include "slice_param.h"
 #include "relu_param.h"
@@ -116,6 +117,9 @@ const OpRow kOps[] = {
     // sub-pixel convolution's shuffle (csrc/d2s.hip): ESPCN / EDSR tails, torch's PixelShuffle -- the two quantised kernels of the
     // reference, raw bytes.  An fp32 graph keeps the node on the CPU device (which shapes: tamd_node_supported)
     {OP_DEPTHTOSPACE, TAMD_OP_DEPTHTOSPACE, true},
+    // the nearest up-sampling of an ONNX Upsample and caffe's Resize layer (csrc/interp.hip, csrc/resize.hip): the nearest mode of the two
+    // quantised kernels of the reference, batch 1.  An fp32 graph keeps the node on the CPU device (which nodes: tamd_node_supported)
+    {OP_RESIZE, TAMD_OP_RESIZE, true},
 };
 
 const OpRow* find_op(int op)
@@ -178,7 +182,7 @@ union NodeParams {
     tamd_conv_param conv; tamd_pool_param pool; tamd_fc_param fc; tamd_relu_param relu; tamd_eltwise_param elt; tamd_concat_param concat;
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
-    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_depthtospace_param d2s; tamd_transpose_param transpose; tamd_batchnorm_param bn;
+    tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_depthtospace_param d2s; tamd_resize_param resize; tamd_transpose_param transpose; tamd_batchnorm_param bn;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -247,6 +251,11 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
     case TAMD_OP_BATCHNORM: {        // batchnorm_param.h, field for field
         const struct batchnorm_param* p = (const struct batchnorm_param*)n->op.param_mem;
         s->bn = {p->rescale_factor, p->eps, p->caffe_flavor};
+        break;
+    }
+    case TAMD_OP_RESIZE: {           // resize_param.h, field for field: the in-memory parameter, `type` included (a file never carries it)
+        const struct resize_param* p = (const struct resize_param*)n->op.param_mem;
+        s->resize = tamd_resize_param{p->scale_w, p->scale_h, p->type};
         break;
     }
     case TAMD_OP_DEPTHTOSPACE:       // depthtospace_param.h: the one field

@@ -124,6 +124,18 @@ class _B:
         self.g.add_node(name, "DepthToSpace", [x], [y], block_size=r)
         return y
 
+    def resize(self, name, x, scale_h=2.0, scale_w=None):
+        """nearest up-sampling as an ONNX Upsample / a caffe Resize layer becomes it (tm2 operator 54), batch 1:
+        (1, C, H, W) -> (1, C, (int)(H * scale_h), (int)(W * scale_w)).  The file's scale_x holds scale_h and scale_y holds scale_w: that is
+        how the reference's loader reads them (tm2_resize.c)"""
+        n, c, h, w = self.dims(x)
+        sh = np.float32(scale_h)
+        sw = np.float32(scale_h if scale_w is None else scale_w)
+        assert n == 1 and sh > 0 and sw > 0, "Resize: batch 1, positive scales"
+        y = self.g.add_tensor(name + "/0", [n, c, int(np.float32(h) * sh), int(np.float32(w) * sw)], DT_FP32)
+        self.g.add_node(name, "Resize", [x], [y], scale_x=float(sh), scale_y=float(sw), type=0)
+        return y
+
     def permute(self, name, x, order=(0, 2, 3, 1)):
         d = self.dims(x)
         y = self.g.add_tensor(name + "/0", [d[i] for i in order], DT_FP32)

@@ -31,7 +31,7 @@ OPTYPE = {
     "BatchNormalization": 1,      # TM2_BatchNormParam; inputs [x, gamma, beta, mean, var], the four statistics fp32 constants of C elements
     "Concat": 3, "Const": 4, "Convolution": 5, "Dropout": 8, "Eltwise": 9, "Flatten": 10,
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
-    "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "ShuffleChannel": 55, "Crop": 56,
+    "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "Resize": 54, "ShuffleChannel": 55, "Crop": 56,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "DepthToSpace": 80, "Clip": 87, "Mish": 97,
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
@@ -197,6 +197,8 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
     if op == "Crop":            # TM2_CropParam (tm2_format.h:812-823): six int32, a one-byte bool and three bytes of padding, two int32
         v = struct.unpack_from("<6iB3x2i", b, off)
         return dict(zip(CROP_FIELDS, v))
+    if op == "Resize":          # TM2_ResizeParam {scale_x, scale_y, type}, as the file has them.  The reference's loader reads scale_h from
+        return dict(zip(["scale_x", "scale_y", "type"], struct.unpack_from("<2fi", b, off)))      # scale_x, scale_w from scale_y, and no type
     if op == "DepthToSpace":    # TM2_DepthToSpaceParam (tm2_format.h:942-945): {block_size}
         return {"block_size": struct.unpack_from("<i", b, off)[0]}
     if op == "Transpose":       # TM2_TransposeParam (tm2_format.h:929-932): {offset_tr_shape -> TM2_Vector_dims}
@@ -299,6 +301,8 @@ def write_tm2(g: Graph) -> bytes:
         elif n.op == "Crop":     # TM2_CropParam; the defaults are crop.c's init_op (axis 2, everything else 0)
             q = n.params
             pb = struct.pack("<6iB3x2i", *[int(q.get(k, 2 if k == "axis" else 0)) for k in CROP_FIELDS])
+        elif n.op == "Resize":   # TM2_ResizeParam {scale_x, scale_y, type}; the defaults are resize.c's init_op (1, 1, nearest)
+            pb = struct.pack("<2fi", float(n.params.get("scale_x", 1.0)), float(n.params.get("scale_y", 1.0)), int(n.params.get("type", 0)))
         elif n.op == "DepthToSpace":  # TM2_DepthToSpaceParam {block_size}; the default is depthtospace.c's init_op (1)
             pb = struct.pack("<i", int(n.params.get("block_size", 1)))
         elif n.op == "Transpose":  # TM2_TransposeParam {offset_tr_shape -> TM2_Vector_dims}; tr_shape None: TM2_NOT_SET, a node no loader accepts
