@@ -149,6 +149,16 @@ enum {
      * other ranks, a constant input, a scale that is not finite and positive, an empty output and per-channel parameters are refused by
      * name; fp32 graphs keep the node on the CPU device */
     TAMD_OP_RESIZE = 36,
+    /* 37: reserved, never supported (like 21, 24, 27, 29, 31, 33 and 35: tests/test_resize_cpu.py holds the code to that answer) */
+    /* the per-image normalisation of image-to-image generators (fast style transfer, CycleGAN / pix2pix, AnimeGAN, U-Nets); tm2 operator
+     * 66 --, uint8 graphs: param tamd_instancenorm_param; inputs [x, gamma, beta], x (N, C, H, W), gamma and beta fp32 constants of C
+     * elements; the output has x's shape.  Per plane (n, c) the reference (instancenorm_ref.c:101-183) dequantises, sums the plane and
+     * the squared deviations in two strictly sequential fp32 chains, a = gamma / sqrt(var + eps) in double, b = fma(-mean, a, beta),
+     * y = fma(v, a, b), requantises: given a and b a byte map per plane (tamd_instancenorm_plane), computed ON THE DEVICE in the
+     * reference's summation order (csrc/instnorm.hip).  int8 graphs (no kernel in the reference), fp32 graphs, other ranks, a constant
+     * x, gamma / beta that are no finite fp32 constants of C elements, an eps that is not finite and positive, per-channel
+     * parameters, an empty plane and a node whose values could leave int before the reference's conversion are refused by name */
+    TAMD_OP_INSTANCENORM = 38,
     TAMD_OP_NUM
 };
 
@@ -175,6 +185,7 @@ typedef struct tamd_relu_param { float negative_slope; } tamd_relu_param;   /* r
 /* field meaning == struct batchnorm_param (batchnorm_param.h) */
 typedef struct tamd_batchnorm_param { float rescale_factor, eps; int caffe_flavor; } tamd_batchnorm_param;
 typedef struct tamd_depthtospace_param { int block_size; } tamd_depthtospace_param;   /* depthtospace_param.h */
+typedef struct tamd_instancenorm_param { float eps; } tamd_instancenorm_param;        /* instancenorm_param.h */
 /* == struct resize_param (resize_param.h): type 0 nearest, 1 bilinear.  The tm2 loader fills scale_h from TM2_ResizeParam.scale_x and
  * scale_w from .scale_y and does not read .type (tm2_resize.c:42-54) */
 typedef struct tamd_resize_param { float scale_w, scale_h; int type; } tamd_resize_param;
@@ -349,6 +360,15 @@ TAMD_API int tamd_eltwise_pair(int type, int dtype, unsigned char a, float a_sca
  * one of the 256 values before the clamp is not finite or lies outside int (the node is refused) */
 TAMD_API int tamd_batchnorm_table(const tamd_batchnorm_param* param, float gamma, float beta, float mean, float var, float in_scale, int in_zp,
                                   float out_scale, int out_zp, unsigned char table[256]);
+/* ONE plane of a uint8 InstanceNorm (csrc/instnorm_tables.cc; no GPU needed): the specification of the device kernels, every operation
+ * as the built reference's object code has it.  x[0 .. size): the plane's bytes.  v_j = ((float)x_j - (float)in_zp) * in_scale;
+ * sum = the sequential fp32 sum over j ascending; mean = sum / size; sqsum over j ascending of t = v_j - mean: sqsum + t * t with the
+ * product ROUNDED for j < size - size % 4 and fmaf(t, t, sqsum) for the last size % 4 elements; var = sqsum / size;
+ * a = (float)((double)gamma / sqrt((double)(var + eps))); b = fmaf(-mean, a, beta); table[u] = (int)roundf(fmaf(v(u), a, b) / out_scale +
+ * (float)out_zp) clamped to 0 .. 255.  stats (may be null): {sum, sqsum, a, b}.  0; -1: bad arguments (size < 1); -2: a table value is NaN or
+ * outside int */
+TAMD_API int tamd_instancenorm_plane(const unsigned char* x, int size, float gamma, float beta, float eps, float in_scale, int in_zp, float out_scale,
+                                     int out_zp, unsigned char table[256], float stats[4]);
 /* the two host-built operands of a nearest Interp node (csrc/interp_tables.cc; no GPU needed).
  * tamd_interp_table: table[b] = the output byte for input byte b between tensors of these quantisation parameters (interp_ref.c:269-272,
  * 346-354: int8 saturates at +-127, so -128 comes out as -127 even between equal scales; :378-381, 455-463: uint8 at 0 .. 255).  0, or
@@ -513,6 +533,13 @@ TAMD_API int tamd_graph_tensor_desc(const tamd_graph* g, int tensor_idx, int* di
  * the reference's arithmetic (tamd_lut_table, tamd_eltwise_table, tamd_eltwise_pair).  The member count (>= 2); 0: no chain starts
  * there (or TAMD_PIN=bytemap_chain=0); -1: bad arguments.  Needs no GPU and no prerun */
 TAMD_API int tamd_graph_bytemap_chain(const tamd_graph* g, int node, int* nodes, int cap, unsigned char table[256]);
+/* how the uint8 planner runs InstanceNorm node `node` (index in the order the nodes were added) of a loaded graph: *form 0: instnorm_stats_u8
+ * writes the planes' byte maps, chan_lut_u8 applies them (two launches; the default on planes above 4096 bytes); 1: instnorm_u8 does both (one
+ * launch; the default up to 4096 bytes a plane; TAMD_PIN=instnorm_form forces either).
+ * *relu_node: the index of the ReLU / leaky ReLU composed into the map -- the output's only reader, the output no graph output,
+ * TAMD_PIN=instnorm_relu=0 not set --, -1: none.  Asked before buffers are planned, this is an UPPER BOUND: prerun keeps a ReLU a launch
+ * of its own where its output turns out to be written in place into a Concat's buffer, or where another launch has taken the node.  0; -1: bad arguments or no InstanceNorm node the device runs.  Needs no GPU and no prerun */
+TAMD_API int tamd_graph_instancenorm_plan(const tamd_graph* g, int node, int* form, int* relu_node);
 
 TAMD_API void tamd_graph_destroy(tamd_graph* g);
 

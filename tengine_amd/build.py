@@ -22,7 +22,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["conv_igemm.hip", "conv_igemm2.hip", "conv_pgemm.hip", "conv_pgemm_w.hip", "gemm_direct.hip", "pw_stream.hip", "pw_rows.hip", "conv_first.hip", "conv_first_pool.hip", "dwconv.hip", "dwpw.hip", "block_i8.hip", "pwdw.hip", "pwdw_slices.hip", "chain4.hip", "conv_direct.hip", "misc_kernels.hip", "interp.hip", "chanmap.hip", "prelu.hip", "chan_lut.hip", "chan_gate.hip", "slice.hip", "d2s.hip", "resize.hip", "topdown.hip", "transpose.hip", "u8_kernels.hip", "u8_conv_gemm.hip", "u8_conv_patch.hip", "u8_conv_small.hip", "u8i_kernels.hip", "conv_f32_mfma.hip", "winograd_f32.hip", "f32_kernels.hip", "graph.hip", "graph_infer.hip", "graph_plan.hip", "graph_plan_common.hip", "graph_plan_maps.hip", "graph_plan_conv.hip", "graph_plan_pairs.hip", "plan_cache.hip", "graph_exec.hip", "graph_pair.hip", "graph_slots.hip", "graph_u8.hip", "graph_f32.hip", "tm2_reader.cc", "direct.cc", "lut_tables.cc", "interp_tables.cc", "chanmap_tables.cc", "prelu_tables.cc", "slice_tables.cc", "transpose_tables.cc", "resize_tables.cc"]
+SOURCES = ["conv_igemm.hip", "conv_igemm2.hip", "conv_pgemm.hip", "conv_pgemm_w.hip", "gemm_direct.hip", "pw_stream.hip", "pw_rows.hip", "conv_first.hip", "conv_first_pool.hip", "dwconv.hip", "dwpw.hip", "block_i8.hip", "pwdw.hip", "pwdw_slices.hip", "chain4.hip", "conv_direct.hip", "misc_kernels.hip", "interp.hip", "chanmap.hip", "prelu.hip", "chan_lut.hip", "instnorm.hip", "chan_gate.hip", "slice.hip", "d2s.hip", "resize.hip", "topdown.hip", "transpose.hip", "u8_kernels.hip", "u8_conv_gemm.hip", "u8_conv_patch.hip", "u8_conv_small.hip", "u8i_kernels.hip", "conv_f32_mfma.hip", "winograd_f32.hip", "f32_kernels.hip", "graph.hip", "graph_infer.hip", "graph_plan.hip", "graph_plan_common.hip", "graph_plan_maps.hip", "graph_plan_conv.hip", "graph_plan_pairs.hip", "plan_cache.hip", "graph_exec.hip", "graph_pair.hip", "graph_slots.hip", "graph_u8.hip", "graph_f32.hip", "tm2_reader.cc", "direct.cc", "lut_tables.cc", "interp_tables.cc", "instnorm_tables.cc", "chanmap_tables.cc", "prelu_tables.cc", "slice_tables.cc", "transpose_tables.cc", "resize_tables.cc"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value"]
 # int8 GEMM kernels: MFMA accumulators in architectural VGPRs.  hipcc's heuristic keeps them in AccVGPRs and every value

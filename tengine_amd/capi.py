@@ -26,14 +26,14 @@ class KernelInfo(C.Structure):        # tamd_kernel_info
 
 
 EXPORTS = [
-    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_eltwise_table", "tamd_eltwise_scalar", "tamd_eltwise_pair", "tamd_batchnorm_table", "tamd_interp_table", "tamd_interp_indices", "tamd_resize_table", "tamd_resize_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
+    "tamd_device_count", "tamd_init", "tamd_shutdown", "tamd_last_error", "tamd_version", "tamd_op_supported", "tamd_node_supported", "tamd_lut_table", "tamd_eltwise_table", "tamd_eltwise_scalar", "tamd_eltwise_pair", "tamd_batchnorm_table", "tamd_instancenorm_plane", "tamd_interp_table", "tamd_interp_indices", "tamd_resize_table", "tamd_resize_indices", "tamd_shuffle_sources", "tamd_split_table", "tamd_slice_table", "tamd_transpose_table", "tamd_prelu_slope", "tamd_prelu_table",
     "tamd_graph_create", "tamd_graph_add_tensor", "tamd_graph_add_node", "tamd_graph_set_inputs",
     "tamd_graph_set_outputs", "tamd_graph_load_tm2", "tamd_graph_set_batch", "tamd_graph_prerun", "tamd_graph_halves", "tamd_graph_slots",
     "tamd_graph_input_num", "tamd_graph_output_num", "tamd_graph_input_desc", "tamd_graph_output_desc",
     "tamd_graph_set_input", "tamd_graph_set_output", "tamd_graph_run", "tamd_graph_run_async", "tamd_graph_wait", "tamd_graph_inflight", "tamd_graph_upload_inputs",
     "tamd_graph_launch", "tamd_graph_sync", "tamd_graph_direct_packets", "tamd_graph_direct_meta_packets", "tamd_graph_download_outputs", "tamd_graph_output_device",
     "tamd_graph_direct_timestamps", "tamd_graph_slot_timestamps", "tamd_graph_direct_packet_name", "tamd_graph_stream", "tamd_graph_time_launches", "tamd_graph_prerun_ms", "tamd_graph_kernel_num", "tamd_graph_profile",
-    "tamd_graph_read_tensor", "tamd_graph_tensor_num", "tamd_graph_tensor_desc", "tamd_graph_bytemap_chain", "tamd_graph_destroy",
+    "tamd_graph_read_tensor", "tamd_graph_tensor_num", "tamd_graph_tensor_desc", "tamd_graph_bytemap_chain", "tamd_graph_instancenorm_plan", "tamd_graph_destroy",
 ]
 
 _lib = None
@@ -100,6 +100,9 @@ def lib():
         if hasattr(L, "tamd_resize_table"):       # (guarded like the slots: an older build has no Resize)
             L.tamd_resize_table.argtypes = [ci, C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
             L.tamd_resize_indices.argtypes = [ci, ci, C.c_float, C.POINTER(ci)]
+        if hasattr(L, "tamd_instancenorm_plane"):     # (guarded like the slots: an older build has no InstanceNorm)
+            L.tamd_instancenorm_plane.argtypes = [C.POINTER(C.c_ubyte), ci] + [C.c_float] * 4 + [ci, C.c_float, ci, C.POINTER(C.c_ubyte), C.POINTER(C.c_float)]
+            L.tamd_graph_instancenorm_plan.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci)]
         L.tamd_shuffle_sources.argtypes = [ci, ci, C.POINTER(ci)]
         L.tamd_split_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
         L.tamd_slice_table.argtypes = [C.c_float, ci, C.c_float, ci, C.POINTER(C.c_ubyte)]
@@ -157,6 +160,40 @@ def resize_indices(in_extent, out_extent, scale):
     idx = (C.c_int * max(out_extent, 1))()
     rc = lib().tamd_resize_indices(in_extent, out_extent, scale, idx)
     return None if rc != 0 else np.array(idx[:out_extent], dtype=np.int32)
+
+
+OP_INSTANCENORM = 38     # (37: reserved too)
+
+
+class InstanceNormParam(C.Structure): # tamd_instancenorm_param
+    _fields_ = [("eps", C.c_float)]
+
+
+def instancenorm_plane(x, gamma, beta, eps, in_scale, in_zp, out_scale, out_zp):
+    """tamd_instancenorm_plane(): (rc, the 256-entry byte map of ONE plane of a uint8 InstanceNorm, [sum, sqsum, a, b] as float32) for the
+    plane's bytes x (any shape, read in order).  rc -2: a value is NaN or outside int.  The map and the statistics are None unless rc is 0.  Needs no GPU."""
+    xb = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+    tab, st = (C.c_ubyte * 256)(), (C.c_float * 4)()
+    rc = lib().tamd_instancenorm_plane(xb.ctypes.data_as(C.POINTER(C.c_ubyte)), xb.size, gamma, beta, eps, in_scale, in_zp, out_scale, out_zp, tab, st)
+    if rc != 0:
+        return rc, None, None
+    return 0, np.frombuffer(tab, dtype=np.uint8).copy(), np.array(st[:], dtype=np.float32)
+
+
+def instancenorm_plan(tm_bytes, node):
+    """tamd_graph_instancenorm_plan() of the model's node `node` (its index in the file): (form -- 1 up to 4096 bytes a plane, 0 above, or what
+    TAMD_PIN=instnorm_form says --, index of the ReLU node composed into the
+    map or -1: an upper bound, asked before buffers are planned), or None where that node is no InstanceNorm the device runs.  Needs no GPU."""
+    L = lib()
+    h = L.tamd_graph_load_tm2(tm_bytes, len(tm_bytes))
+    if not h:
+        raise TamdError("load_tm2 failed: %s" % L.tamd_last_error().decode())
+    try:
+        form, relu = C.c_int(), C.c_int()
+        rc = L.tamd_graph_instancenorm_plan(h, node, C.byref(form), C.byref(relu))
+        return None if rc != 0 else (form.value, relu.value)
+    finally:
+        L.tamd_graph_destroy(h)
 
 
 class CropParam(C.Structure):         # tamd_crop_param

@@ -59,6 +59,7 @@ union NodeParam {
     tamd_depthtospace_param d2s;
     tamd_resize_param resize;
     tamd_batchnorm_param bn;
+    tamd_instancenorm_param inorm;
 };
 
 struct HNode {
@@ -380,6 +381,15 @@ const char* batchnorm_refusal_of(const tamd_graph* g, const HNode& n, std::vecto
 // a BatchNorm node of a uint8 graph as ONE launch through its C byte maps: chan_lut_u8 (chan_lut.hip), or prelu_u8's per-plane form
 // (prelu.hip) on planes of at least kBnPlaneForm bytes; TAMD_PIN=bn_form=0 | 1 forces the first | the second
 int plan_batchnorm_u8(tamd_graph* g, HNode& n, std::vector<Step>* out);
+// instancenorm_refusal (node_rules.h) asked of a node of this graph, gamma / beta payloads included: validate_graph and plan_instancenorm_u8
+const char* instancenorm_refusal_of(const tamd_graph* g, const HNode& n);
+// the plain or leaky ReLU that is the only reader of InstanceNorm node ni's output (no graph output) and is composed into the plane's
+// map, -1: none (or TAMD_PIN=instnorm_relu=0); which form runs on planes of that many bytes: 0 instnorm_stats_u8 + chan_lut_u8, 1 instnorm_u8
+// (TAMD_PIN=instnorm_form; the measured default is in graph_plan_maps.hip)
+int instancenorm_relu_next(const tamd_graph* g, size_t ni);
+int instancenorm_form(size_t plane_bytes);
+// an InstanceNorm node of a uint8 graph (instnorm.hip), `relu` (may be null) inside: two launches or one
+int plan_instancenorm_u8(tamd_graph* g, HNode& n, const HNode* relu, std::vector<Step>* out);
 // the scalar and the unary Eltwise, int8 and uint8 graphs alike: one lut_u8 launch through tamd_eltwise_table's bytes
 int plan_eltwise_table(tamd_graph* g, HNode& n, std::vector<Step>* out);
 // A byte-pure chain (graph_plan_maps.hip): nodes[] in node order, each a table node (Sigmoid / Clip / HardSwish / Mish, scalar or unary

@@ -84,6 +84,7 @@ int tamd_op_supported(int op, int dtype)
     if (op == TAMD_OP_SLICE) return slice_on_device(dtype);        // the onnx form, uint8 (which forms and extents: tamd_node_supported)
     if (op == TAMD_OP_TRANSPOSE) return transpose_on_device(dtype);      // int8 / uint8 (which ranks and orders: tamd_node_supported)
     if (op == TAMD_OP_CROP) return crop_on_device(dtype);          // a box of raw bytes, uint8 (which forms and boxes: tamd_node_supported)
+    if (op == TAMD_OP_INSTANCENORM) return instancenorm_on_device(dtype);  // a byte map per plane, computed on the device, uint8 (which shapes and values: tamd_node_supported)
     if (op == TAMD_OP_BATCHNORM) return batchnorm_on_device(dtype);  // a byte map per channel, uint8 (which ranks and statistics: tamd_node_supported)
     if (op == TAMD_OP_DEPTHTOSPACE) return depthtospace_on_device(dtype);      // raw bytes shuffled, int8 / uint8 (which shapes: tamd_node_supported)
     if (op == TAMD_OP_RESIZE) return resize_on_device(dtype);      // nearest by byte map, int8 / uint8 (which scales and shapes: tamd_node_supported)
@@ -289,6 +290,19 @@ int tamd_node_supported(const tamd_node_desc* n, const tamd_tensor_desc* in, int
         for (int i = 0; i < in[0].dim_num; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
         return 1;
     }
+    case TAMD_OP_INSTANCENORM: {
+        if (n_in != 3 || !in) return 0;
+        InStat st[2];
+        for (int k = 0; k < 2; k++) st[k] = InStat{in[k + 1].dtype, in[k + 1].ttype == TAMD_TT_CONST, elems(in[k + 1]), (const float*)in[k + 1].data};
+        const bool have_q = in[0].quant_num == 1 && in[0].scales && out[0].quant_num == 1 && out[0].scales;
+        if (instancenorm_refusal((const tamd_instancenorm_param*)n->param, dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num,
+                                 (size_t)out[0].quant_num, st, have_q, have_q ? in[0].scales[0] : 0.f, have_q ? out[0].scales[0] : 0.f,
+                                 have_q && out[0].zero_points ? out[0].zero_points[0] : 0))
+            return 0;
+        if (out[0].dim_num != in[0].dim_num) return 0;
+        for (int i = 0; i < in[0].dim_num; i++) if (out[0].dims[i] != in[0].dims[i]) return 0;
+        return 1;
+    }
     case TAMD_OP_PRELU: {
         if (n_in < 2 || !in) return 0;
         if (prelu_refusal(dt, n_in, in[0].dim_num, in[0].dims, in[0].ttype == TAMD_TT_CONST, (size_t)in[0].quant_num, (size_t)out[0].quant_num, in[1].dtype,
@@ -365,6 +379,7 @@ int tamd_graph_add_node(tamd_graph* g, const tamd_node_desc* d)
         case TAMD_OP_DEPTHTOSPACE: n.p.d2s = *(const tamd_depthtospace_param*)d->param; break;
         case TAMD_OP_RESIZE: n.p.resize = *(const tamd_resize_param*)d->param; break;
         case TAMD_OP_BATCHNORM: n.p.bn = *(const tamd_batchnorm_param*)d->param; break;
+        case TAMD_OP_INSTANCENORM: n.p.inorm = *(const tamd_instancenorm_param*)d->param; break;
         default: break;
         }
     }

@@ -268,6 +268,7 @@ int infer_shapes(tamd_graph* g)
             y.dims.assign(cg.out_dims, cg.out_dims + 4);
             break;
         }
+        case TAMD_OP_INSTANCENORM: y.dims = x.dims; y.dtype = x.dtype; break;   // instancenorm.c: the input's shape; gamma and beta are fp32, the data is not
         case TAMD_OP_BATCHNORM: y.dims = x.dims; y.dtype = x.dtype; break;      // batchnorm.c: the input's shape; the statistics are fp32, the data is not
         case TAMD_OP_DEPTHTOSPACE: {      // depthtospace.c infer_shape: (N, C / r^2, H * r, W * r).  What the device does not run is refused HERE, by name
             DepthToSpaceGeom dg;
@@ -385,6 +386,10 @@ int validate_graph(tamd_graph* g)
         }
         if (n.op == TAMD_OP_TRANSPOSE) {
             const char* why = transpose_refusal_of(g, n, true, nullptr, nullptr);
+            if (why) return bad(n, why);
+        }
+        if (n.op == TAMD_OP_INSTANCENORM) {
+            const char* why = instancenorm_refusal_of(g, n);
             if (why) return bad(n, why);
         }
         if (n.op == TAMD_OP_BATCHNORM) {

@@ -1,5 +1,5 @@
 // The byte-map node planners: nodes that move or map bytes without arithmetic between tensors -- Sigmoid / Clip / HardSwish / Mish by
-// table (plan_lut), the scalar and the unary Eltwise by table (plan_eltwise_table), byte-pure chains of such nodes as ONE table (bytemap_chain_from, plan_bytemap_chain), PReLU, nearest Interp, the uint8 Slice, the uint8 Crop (alone, inside the Interp's launch, or with both inside the Eltwise's), Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
+// table (plan_lut), the scalar and the unary Eltwise by table (plan_eltwise_table), byte-pure chains of such nodes as ONE table (bytemap_chain_from, plan_bytemap_chain), the uint8 BatchNorm and InstanceNorm (a byte map per channel / per plane, the latter computed on the device), PReLU, nearest Interp, the uint8 Slice, the uint8 Crop (alone, inside the Interp's launch, or with both inside the Eltwise's), Transpose, Split, ShuffleChannel and Concat + ShuffleChannel.  plan_lut, plan_prelu,
 // plan_interp and plan_transpose serve int8 (NHWC) and uint8 (NCHW) graphs alike; the channel maps have an int8 form (chan_map_i8, called by plan_i8, declared in
 // graph_plan.h) and a uint8 form (chan_map_u8, called by plan_u8, declared in graph.h).  Each hands its launches back in `out`.
 #include "graph.h"
@@ -159,6 +159,102 @@ int plan_batchnorm_u8(tamd_graph* g, HNode& n, std::vector<Step>* out)
         ChanLutU8Args a{};
         a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr; a.total = x.elems(); a.C = C; a.HW = (int)hw; a.tables = dtables;
         out->push_back(make_step(n.name, "chan_lut_u8", 0, 2.0 * (double)x.elems(), [a](hipStream_t s) { return launch_chan_lut_u8(a, s); }, {access_of(x)}, {access_of(y)}, false));
+    }
+    return 0;
+}
+
+// ---- uint8 InstanceNorm: a byte map per PLANE, computed on the device (instnorm.hip) ----
+const char* instancenorm_refusal_of(const tamd_graph* g, const HNode& n)
+{
+    if (n.in.size() != 3 || n.out.empty()) return "InstanceNorm takes three inputs: the data, gamma and beta";
+    const HTensor& x = g->tensors[n.in[0]];
+    const HTensor& y = g->tensors[n.out[0]];
+    InStat st[2];
+    for (int k = 0; k < 2; k++) {
+        const HTensor& t = g->tensors[n.in[k + 1]];
+        const bool whole = t.dtype == TAMD_DT_FP32 && t.data.size() >= t.elems() * 4;
+        st[k] = InStat{t.dtype, t.ttype == TAMD_TT_CONST, t.elems(), whole ? (const float*)t.data.data() : nullptr};
+    }
+    const bool have_q = x.scales.size() == 1 && y.scales.size() == 1;
+    return instancenorm_refusal(&n.p.inorm, x.dtype, (int)n.in.size(), (int)x.dims.size(), x.dims.data(), x.ttype == TAMD_TT_CONST, x.scales.size(), y.scales.size(), st, have_q,
+                                have_q ? x.scales[0] : 0.f, have_q ? y.scales[0] : 0.f, have_q && !y.zps.empty() ? y.zps[0] : 0);
+}
+
+// conv -> InstanceNorm -> ReLU is the universal generator block, and the uint8 ReLU is one byte to one byte (relu_kernel_ref_uint8.c):
+// where a plain or leaky ReLU is the InstanceNorm output's only reader and that tensor is no graph output, the ReLU is composed into
+// the plane's map on the device and the tensor between is never written.  The ReLU node's index, -1: none (TAMD_PIN=instnorm_relu=0)
+int instancenorm_relu_next(const tamd_graph* g, size_t ni)
+{
+    const HNode& n = g->nodes[ni];
+    if (n.op != TAMD_OP_INSTANCENORM || n.out.size() != 1 || !tamd_pin_int("instnorm_relu", 1) || count_consumers(g, n.out[0]) != 1) return -1;
+    for (auto& o : g->outputs) if (o.tensor == n.out[0]) return -1;
+    for (size_t nj = ni + 1; nj < g->nodes.size(); nj++) {
+        const HNode& r = g->nodes[nj];
+        if (r.op != TAMD_OP_RELU || r.in.size() != 1 || r.out.size() != 1 || r.in[0] != n.out[0]) continue;
+        const HTensor& y = g->tensors[r.out[0]];
+        if (y.scales.size() != 1 || y.dims != g->tensors[n.out[0]].dims || y.dtype != TAMD_DT_UINT8 || y.is_view) return -1;
+        return (int)nj;
+    }
+    return -1;
+}
+
+// Which form runs where nothing is pinned, as measured (profiles/instnorm.txt, the committed kernels): as launches the one-launch form is
+// ahead with the ranges apart on planes of 256, 1024 and 4096 bytes (6.31 against 8.30, 12.27 against 14.37, 41.85 against 43.52 us; at
+// batch 8 x 128 planes of 1024 bytes 15.18 against 17.66 us) -- it saves the second launch and the round trip of the maps -- and BEHIND with
+// the ranges apart on planes of 16384 bytes (163.1 against 161.3 us), where its apply step runs on 32 waves instead of the whole device.
+// Through the plugin it is ahead with the ranges apart at (1,128,32,32) (72.0 - 73.8 against 74.7 - 74.9 us); at (1,64,64,64) and
+// (1,32,128,128) the ranges overlap.  So one launch is the default up to the largest plane at which it was measured ahead, and two launches
+// stay the default above it, where nothing between 4096 and 16384 bytes was measured
+static const size_t kInstNormOneLaunchMaxPlane = 4096;
+int instancenorm_form(size_t plane_bytes) { return tamd_pin_int("instnorm_form", plane_bytes <= kInstNormOneLaunchMaxPlane ? 1 : 0) == 1 ? 1 : 0; }
+
+// form 0: instnorm_stats_u8 writes the planes' maps into a scratch buffer planned here, chan_lut_u8 (C := N * C) applies them;
+// form 1: instnorm_u8 does both.  relu (may be null): the ReLU node composed into the map; the launch then writes ITS output
+int plan_instancenorm_u8(tamd_graph* g, HNode& n, const HNode* relu, std::vector<Step>* out)
+{
+    const char* why = instancenorm_refusal_of(g, n);
+    if (why) { set_error("instancenorm %s: %s", n.name.c_str(), why); return -1; }
+    HTensor& x = g->tensors[n.in[0]];
+    HTensor& mid = g->tensors[n.out[0]];
+    HTensor& y = relu ? g->tensors[relu->out[0]] : mid;
+    const HTensor& gm = g->tensors[n.in[1]];
+    const HTensor& bt = g->tensors[n.in[2]];
+    if (x.is_view || y.is_view || !x.nchw_raw || !y.nchw_raw) { set_error("instancenorm %s on a concat view is not supported in a uint8 graph", n.name.c_str()); return -1; }
+    if (x.dims != y.dims || x.dims != mid.dims || x.dtype != y.dtype) { set_error("instancenorm %s: output shape / type mismatch", n.name.c_str()); return -1; }
+    const size_t C = (size_t)x.dims[1];
+    if (gm.data.size() < C * 4 || bt.data.size() < C * 4) { set_error("instancenorm %s: gamma / beta have no values", n.name.c_str()); return -1; }
+    std::vector<float> hg((const float*)gm.data.data(), (const float*)gm.data.data() + C), hb((const float*)bt.data.data(), (const float*)bt.data.data() + C);
+    float *dg = nullptr, *db = nullptr;
+    if (upload(g, hg, &dg) || upload(g, hb, &db)) return -1;
+    InstNormU8Args a{};
+    a.x = (const uint8_t*)x.dptr; a.y = (uint8_t*)y.dptr;
+    a.planes = (long)x.dims[0] * x.dims[1]; a.C = x.dims[1]; a.HW = x.dims[2] * x.dims[3];
+    a.gamma = dg; a.beta = db; a.eps = n.p.inorm.eps;
+    auto q_of = [](const HTensor& t) { return U8Q{t.scales[0], t.zps.empty() ? 0 : t.zps[0]}; };      // (one pair each: the refusal, instancenorm_relu_next)
+    if (y.scales.size() != 1) { set_error("instancenorm %s: the ReLU's output needs per-tensor quant params", n.name.c_str()); return -1; }
+    a.in = q_of(x); a.out = q_of(mid);
+    if (relu) { a.relu.on = 1; a.relu.slope = relu->p.relu.negative_slope; a.relu.out = q_of(y); }
+    const std::string node = relu ? n.name + "+" + relu->name : n.name;
+    const double chain = 2.0 * (double)x.elems();
+    if (instancenorm_form((size_t)a.HW) == 1) {
+        out->push_back(make_step(node, "instnorm_u8", 0, 3.0 * (double)x.elems() + (double)y.elems(), [a](hipStream_t s) { return launch_instnorm_u8(a, s); }, {access_of(x)},
+                                 {access_of(y)}, false));
+    } else {
+        const size_t dwords = (size_t)a.planes * 64;
+        unsigned* dtables = nullptr;
+        if (upload(g, std::vector<unsigned>(dwords, 0u), &dtables)) return -1;      // the scratch maps: written by every run before they are read
+        a.tables = dtables;
+        const Access scratch = access_of_bytes(dtables, dwords * 4);
+        out->push_back(make_step(node, "instnorm_stats_u8", 0, chain + (double)dwords * 4, [a](hipStream_t s) { return launch_instnorm_stats_u8(a, s); }, {access_of(x)},
+                                 {scratch}, false));
+        ChanLutU8Args l{};
+        l.x = a.x; l.y = a.y; l.total = x.elems(); l.C = (int)a.planes; l.HW = a.HW; l.tables = dtables;
+        out->push_back(make_step(node, "chan_lut_u8", 0, 2.0 * (double)x.elems(), [l](hipStream_t s) { return launch_chan_lut_u8(l, s); }, {access_of(x), scratch},
+                                 {access_of(y)}, false));
+    }
+    if (relu) {
+        if (g->fused_away.size() != g->tensors.size()) g->fused_away.assign(g->tensors.size(), 0);
+        g->fused_away[n.out[0]] = 1;                                                // never written
     }
     return 0;
 }
@@ -1131,4 +1227,16 @@ extern "C" int tamd_graph_bytemap_chain(const tamd_graph* g, int node, int* node
     for (size_t k = 0; k < c.nodes.size() && (int)k < cap; k++) nodes[k] = c.nodes[k];
     memcpy(table, c.table, 256);
     return (int)c.nodes.size();
+}
+
+extern "C" int tamd_graph_instancenorm_plan(const tamd_graph* g, int node, int* form, int* relu_node)
+{
+    using namespace tamd;
+    if (!g || node < 0 || node >= (int)g->nodes.size() || !form || !relu_node) return -1;
+    const HNode& n = g->nodes[(size_t)node];
+    if (n.op != TAMD_OP_INSTANCENORM || instancenorm_refusal_of(g, n)) return -1;
+    const HTensor& x = g->tensors[n.in[0]];
+    *form = instancenorm_form((size_t)x.dims[2] * (size_t)x.dims[3]);
+    *relu_node = instancenorm_relu_next(g, (size_t)node);
+    return 0;
 }

@@ -905,6 +905,12 @@ int plan_u8(tamd_graph* g)
         const int ej = crop_topdown_next(g, ci);
         if (ej > (int)ci && !fused[ej] && !gate_lut[ej] && !topdown[ej]) { topdown[ej] = (int)ci + 1; fused[ci] = 1; }
     }
+    // InstanceNorm -> ReLU as the InstanceNorm's launches (instancenorm_relu_next): in_relu[instancenorm node] = the ReLU's node + 1, which is skipped
+    std::vector<int> in_relu(g->nodes.size(), 0);
+    for (size_t ni = 0; ni < g->nodes.size(); ni++) {
+        const int rj = instancenorm_relu_next(g, ni);
+        if (rj > (int)ni && !fused[rj]) { in_relu[ni] = rj + 1; fused[rj] = 1; }
+    }
     // byte-pure chains (bytemap_chain_from, graph_plan_maps.hip) as one lut_u8 launch each at the LAST member's position:
     // chain_at[last member] = the chain's index + 1, the other members are skipped.  Every tensor owns its buffer here: only views are out
     std::vector<ByteChain> chains;
@@ -950,6 +956,7 @@ int plan_u8(tamd_graph* g)
             rc = crop_interp[ni] ? plan_interp(g, g->nodes[crop_interp[ni] - 1], &out, &n) : plan_crop_u8(g, n, &out);
             break;
         case TAMD_OP_PRELU: rc = plan_prelu(g, n, &out); break;
+        case TAMD_OP_INSTANCENORM: rc = plan_instancenorm_u8(g, n, in_relu[ni] ? &g->nodes[in_relu[ni] - 1] : nullptr, &out); break;      // instnorm.hip: two launches, or one
         case TAMD_OP_BATCHNORM: rc = plan_batchnorm_u8(g, n, &out); break;      // chan_lut_u8, or prelu_u8's per-plane form on large planes
         case TAMD_OP_PERMUTE:
             if (!skip_perm[ni]) rc = plan_permute_u8(n, x, y, &out);      // else folded into the concat that reads it

@@ -660,6 +660,23 @@ struct U8Q { float scale; int zp; };
 // (relu_kernel_ref_uint8.c:48-95 on that byte), so the bytes equal the two-launch sequence
 struct U8Relu { int on; float slope; U8Q out; };
 
+// uint8 InstanceNorm over a dense NCHW tensor (instnorm.hip): a wave per plane p = n * C + c of HW bytes computes the plane's two
+// sequential fp32 sums, a and b, and the plane's 256-entry byte map (tamd_instancenorm_plane is the specification).
+// instnorm_stats_u8 stores the map as tables[p][64] dwords for a chan_lut_u8 launch with C := planes; instnorm_u8 keeps it in a
+// register per lane and maps its own plane to y.  relu.on: the ReLU node behind, composed into the map (fused_relu on the map's byte)
+struct InstNormU8Args {
+    const uint8_t* x; uint8_t* y;      // both 16-byte aligned (y: instnorm_u8 only)
+    long planes;                       // N * C
+    int C, HW;
+    const float* gamma; const float* beta;      // [C] each
+    float eps;
+    U8Q in, out;
+    U8Relu relu;
+    unsigned* tables;                  // [planes][64] (instnorm_stats_u8 only)
+};
+hipError_t launch_instnorm_stats_u8(const InstNormU8Args& a, hipStream_t s);
+hipError_t launch_instnorm_u8(const InstNormU8Args& a, hipStream_t s);
+
 struct U8PoolFuse {            // a 2x2 / stride 2 / unpadded MAX-pool node applied to the conv's final bytes in the conv epilogue
     int on;                    // the kernel then enumerates output pixels window-major: j = 4 * window + 2 * dy + dx (so the four
                                // pixels of a window sit in four neighbouring lanes); needs OH, OW even and OH*OW % 8 == 0

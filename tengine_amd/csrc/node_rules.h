@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "chanmap_tables.h"
+#include "instnorm_tables.h"
 #include "interp_tables.h"
 #include "lut_tables.h"
 #include "prelu_tables.h"
@@ -595,6 +596,45 @@ inline const char* prelu_refusal(int dtype, int input_num, int in_dim_num, const
     if (dtype == TAMD_DT_INT8 && slope_elems != (size_t)in_dims[1]) return "an int8 PReLU needs one slope per channel";
     if (dtype == TAMD_DT_UINT8 && slope_elems != (size_t)in_dims[1] && slope_elems != 1) return "a uint8 PReLU needs one slope per channel, or one for all";
     if (slope_data && !prelu_slopes_finite((const unsigned short*)slope_data, slope_elems)) return "PReLU: a slope widens to inf or NaN";
+    return nullptr;
+}
+
+// InstanceNorm: the uint8 kernel of the reference (instancenorm_ref.c:101-183; instnorm.hip).  run() has an fp32 and a uint8 branch and
+// nothing for int8; fp32 graphs keep the node on the CPU device
+inline bool instancenorm_on_device(int dtype) { return dtype == TAMD_DT_UINT8; }
+// gamma or beta of an InstanceNorm node (inputs 1, 2); data: its payload where the caller has it
+struct InStat { int dtype; bool is_const; size_t elems; const float* data; };
+// One InstanceNorm node: nullptr when the device runs it, else the reason.  st[2]: gamma, beta.  in_scale / out_scale / out_zp: the
+// quantisation values where the caller has them (have_q); without them, or without both payloads, the bound is not checked and prerun
+// refuses by name what a support query let through.
+//  - 4-D only: ref_instancenorm_uint8 reads dims[0 .. 3] whatever the rank
+//  - eps <= 0 or not finite: a constant plane has var 0 and a = gamma / sqrt(eps)
+//  - the bound (instnorm_tables.h): where (255 * in_scale * max|gamma| / sqrt(eps) + max|beta|) / out_scale + |out_zp| reaches 2^30 a
+//    plane may exist whose value leaves int before the reference's conversion, which is undefined there.  (The device conversion
+//    saturates whatever the bound says.)
+inline const char* instancenorm_refusal(const tamd_instancenorm_param* p, int dtype, int input_num, int x_dim_num, const int* x_dims, bool x_const, size_t x_quant,
+                                        size_t out_quant, const InStat* st, bool have_q, float in_scale, float out_scale, int out_zp)
+{
+    if (!p) return "InstanceNorm needs its parameter";
+    if (dtype == TAMD_DT_INT8) return "InstanceNorm does not run on the device in int8 graphs: the reference has no int8 kernel";
+    if (!instancenorm_on_device(dtype)) return "InstanceNorm runs on the device in uint8 graphs only";
+    if (input_num != 3) return "InstanceNorm takes three inputs: the data, gamma and beta";
+    if (x_dim_num != 4) return "InstanceNorm runs on the device on a 4-D tensor only";
+    if (x_const) return "InstanceNorm: the data tensor must not be a constant";
+    if (x_quant != 1 || out_quant != 1) return "InstanceNorm needs per-tensor quant params on both sides";
+    if (x_dims[0] < 1 || x_dims[1] < 1) return "InstanceNorm: batch and channels must be at least 1";
+    if (x_dims[2] < 1 || x_dims[3] < 1) return "InstanceNorm: a plane is empty";
+    if ((double)x_dims[2] * x_dims[3] > (double)(0x7fffffffL - 64) || (double)x_dims[0] * x_dims[1] > (double)0x7fffffffL) return "InstanceNorm: a plane of more than 2^31 bytes";
+    if (!(p->eps > 0.f) || !isfinite(p->eps)) return "InstanceNorm: eps must be finite and positive";
+    const size_t C = (size_t)x_dims[1];
+    for (int k = 0; k < 2; k++)
+        if (st[k].dtype != TAMD_DT_FP32 || !st[k].is_const || st[k].elems != C) return "InstanceNorm: gamma and beta must be fp32 constants of C elements";
+    if (!st[0].data || !st[1].data) return nullptr;
+    for (int k = 0; k < 2; k++)
+        for (size_t c = 0; c < C; c++) if (!isfinite(st[k].data[c])) return "InstanceNorm: gamma and beta must be finite";
+    if (!have_q) return nullptr;
+    if (!(instancenorm_bound(st[0].data, st[1].data, C, p->eps, in_scale, out_scale, out_zp) < 1073741824.0))
+        return "InstanceNorm: a value could leave int before the reference's conversion (the bound on |y / out_scale + out_zp| reaches 2^30)";
     return nullptr;
 }
 

@@ -84,6 +84,7 @@ int map_op(uint32_t t)
     case 54: return TAMD_OP_RESIZE;
     case 55: return TAMD_OP_SHUFFLECHANNEL;
     case 56: return TAMD_OP_CROP;
+    case 66: return TAMD_OP_INSTANCENORM;             // TM2_OPTYPE_INSTANCENORM: TM2_InstanceNormParam {eps}; inputs [x, gamma, beta]
     case 70: return TAMD_OP_HARDSWISH;
     case 71: return TAMD_OP_INTERP;
     case 77: return TAMD_OP_TRANSPOSE;
@@ -184,6 +185,7 @@ extern "C" tamd_graph* tamd_graph_load_tm2(const void* mem, size_t size)
                 break;
             }
             case TAMD_OP_FC: p.fc.num_output = r.i32(po); break;
+            case TAMD_OP_INSTANCENORM: p.inorm.eps = r.f32(po); break;      // TM2_InstanceNormParam: eps at offset 0
             case TAMD_OP_BATCHNORM: p.bn.rescale_factor = r.f32(po); p.bn.eps = r.f32(po + 4); p.bn.caffe_flavor = r.i32(po + 8); break;      // TM2_BatchNormParam :407-412
             case TAMD_OP_RELU: p.relu.negative_slope = r.f32(po); break;
             case TAMD_OP_ELTWISE:

@@ -56,6 +56,7 @@ extern "C" {
 #include "permute_param.h"
 #include "pooling_param.h"
 #include "priorbox_param.h"
+#include "instancenorm_param.h"
 #include "resize_param.h"
 #include "shuffle_channel_param.h"
 #include "slice_param.h"
@@ -120,6 +121,10 @@ const OpRow kOps[] = {
     // the nearest up-sampling of an ONNX Upsample and caffe's Resize layer (csrc/interp.hip, csrc/resize.hip): the nearest mode of the two
     // quantised kernels of the reference, batch 1.  An fp32 graph keeps the node on the CPU device (which nodes: tamd_node_supported)
     {OP_RESIZE, TAMD_OP_RESIZE, true},
+    // the per-image normalisation of image-to-image generators (csrc/instnorm.hip): the uint8 kernel of the reference, a byte map per
+    // plane computed on the device; int8 (no kernel in the reference) and fp32 graphs keep the node on the CPU device (which shapes and
+    // values: tamd_node_supported)
+    {OP_INSTANCENORM, TAMD_OP_INSTANCENORM, true},
 };
 
 const OpRow* find_op(int op)
@@ -183,6 +188,7 @@ union NodeParams {
     tamd_upsample_param ups; tamd_permute_param perm; tamd_softmax_param softmax; tamd_reshape_param reshape; tamd_priorbox_param priorbox;
     tamd_clip_param clip; tamd_hardswish_param hardswish; tamd_interp_param interp; tamd_split_param split;
     tamd_shufflechannel_param shuffle; tamd_slice_param slice; tamd_crop_param crop; tamd_depthtospace_param d2s; tamd_resize_param resize; tamd_transpose_param transpose; tamd_batchnorm_param bn;
+    tamd_instancenorm_param inorm;
 };
 
 bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void** param)
@@ -251,6 +257,11 @@ bool translate_node(struct graph* ir, struct node* n, NodeParams* s, const void*
     case TAMD_OP_BATCHNORM: {        // batchnorm_param.h, field for field
         const struct batchnorm_param* p = (const struct batchnorm_param*)n->op.param_mem;
         s->bn = {p->rescale_factor, p->eps, p->caffe_flavor};
+        break;
+    }
+    case TAMD_OP_INSTANCENORM: {     // instancenorm_param.h, field for field
+        const struct instancenorm_Param* p = (const struct instancenorm_Param*)n->op.param_mem;
+        s->inorm = tamd_instancenorm_param{p->eps};
         break;
     }
     case TAMD_OP_RESIZE: {           // resize_param.h, field for field: the in-memory parameter, `type` included (a file never carries it)
@@ -570,7 +581,7 @@ static bool node_supported(struct graph* ir, struct node* n)
     // (descriptors alone, but for a PReLU's slope: its values decide -- one that widens to inf or NaN keeps the node on the CPU device --
     // and for the quantisation values on both sides of a Slice or a Transpose: a pair whose byte map the reference cannot compute does the same;
     // an Eltwise with a constant scalar or of a unary type is such a byte map too, of those values and the constant's)
-    const bool values = op == TAMD_OP_SLICE || op == TAMD_OP_TRANSPOSE || op == TAMD_OP_ELTWISE || op == TAMD_OP_BATCHNORM;      // (BatchNorm: the four statistics too)
+    const bool values = op == TAMD_OP_SLICE || op == TAMD_OP_TRANSPOSE || op == TAMD_OP_ELTWISE || op == TAMD_OP_BATCHNORM || op == TAMD_OP_INSTANCENORM;      // (BatchNorm: the four statistics too; InstanceNorm: gamma and beta)
     for (int k = 0; k < n->input_num; k++) in.push_back(describe_tensor(get_ir_graph_tensor(ir, n->input_tensors[k]), values || (op == TAMD_OP_PRELU && k == 1)));
     for (int k = 0; k < n->output_num; k++) out.push_back(describe_tensor(get_ir_graph_tensor(ir, n->output_tensors[k]), values));
     NodeParams params;

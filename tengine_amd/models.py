@@ -124,6 +124,18 @@ class _B:
         self.g.add_node(name, "DepthToSpace", [x], [y], block_size=r)
         return y
 
+    def instancenorm(self, name, x, eps=1e-5):
+        """the per-image normalisation of image-to-image generators (tm2 operator 66): inputs [x, gamma, beta], seeded gamma around 1 and
+        beta around 0; the output has x's shape"""
+        c = self.dims(x)[1]
+        rng = self._rng()
+        gamma = rng.uniform(0.5, 1.5, size=(c,)).astype(np.float32)
+        beta = rng.uniform(-0.5, 0.5, size=(c,)).astype(np.float32)
+        ins = [x, self.g.add_const(name + "/gamma", gamma, DT_FP32), self.g.add_const(name + "/beta", beta, DT_FP32)]
+        y = self.g.add_tensor(name + "/0", list(self.dims(x)), DT_FP32)
+        self.g.add_node(name, "InstanceNorm", ins, [y], eps=float(eps))
+        return y
+
     def resize(self, name, x, scale_h=2.0, scale_w=None):
         """nearest up-sampling as an ONNX Upsample / a caffe Resize layer becomes it (tm2 operator 54), batch 1:
         (1, C, H, W) -> (1, C, (int)(H * scale_h), (int)(W * scale_w)).  The file's scale_x holds scale_h and scale_y holds scale_w: that is
@@ -365,6 +377,18 @@ def mssd_fp32(batch=1, res=300, classes=21, tail=False, priorbox=False, detectio
     return b.finish(outs)
 
 
+def generator_block_fp32(batch=1, channels=32, res=128, cin=None, slope=0.0, eps=1e-5):
+    """the block image-to-image generators repeat (fast style transfer, CycleGAN / pix2pix, AnimeGAN): conv3x3 -> InstanceNorm -> ReLU
+    (slope > 0: leaky) -> conv3x3, on (batch, cin or channels, res, res)"""
+    b = _B("generator_block", [batch, cin or channels, res, res])
+    x = b.conv("conv1", b.cur, channels, 3, 1, 1)
+    x = b.instancenorm("in1", x, eps)
+    x = b.relu("relu1", x, slope)
+    x = b.conv("conv2", x, channels, 3, 1, 1)
+    b.g.output_nodes = [len(b.g.nodes) - 1]
+    return b.g
+
+
 # --------------------------------------------------------------------------------------
 # fp32 forward (calibration only)
 # --------------------------------------------------------------------------------------
@@ -420,6 +444,8 @@ def fp32_forward(g: Graph, x: np.ndarray):
             y = torch.where(a < 0, a * p.get("negative_slope", 0.0), a)
         elif op == "ReLU6":
             y = torch.clamp(a, 0, 6)
+        elif op == "InstanceNorm":
+            y = F.instance_norm(a, weight=vals[n.inputs[1]], bias=vals[n.inputs[2]], eps=p.get("eps", 1e-5))
         elif op == "Eltwise":
             t = p["type"]
             if len(n.inputs) == 1:      # the unary types (eltwise_ref.c): value ranges for calibration

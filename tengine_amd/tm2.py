@@ -33,6 +33,7 @@ OPTYPE = {
     "DetectionOutput": 7, "FullyConnected": 11, "InputOp": 12, "Permute": 15, "Pooling": 16, "PriorBox": 18, "ReLU": 20, "ReLU6": 21,
     "Reshape": 23, "Slice": 27, "Softmax": 28, "Split": 29, "Upsample": 51, "Resize": 54, "ShuffleChannel": 55, "Crop": 56,
     "Sigmoid": 37, "HardSwish": 70, "Interp": 71, "Transpose": 77, "DepthToSpace": 80, "Clip": 87, "Mish": 97,
+    "InstanceNorm": 66,      # TM2_InstanceNormParam {eps}; inputs [x, gamma, beta], gamma and beta fp32 constants of C elements
     "PReLU": 17,             # no parameter blob; inputs [data, slope], the slope an fp16 constant in quantised files
 }
 OPNAME = {v: k for k, v in OPTYPE.items()}
@@ -113,6 +114,8 @@ def _pack_param(op: str, p: Dict) -> Optional[bytes]:
         return struct.pack("<I10i", p["alg"], p["kernel_h"], p["kernel_w"], p["stride_h"], p["stride_w"],
                            p.get("global", 0), p.get("caffe_flavor", 0), p.get("pad_h0", 0),
                            p.get("pad_w0", 0), p.get("pad_h1", 0), p.get("pad_w1", 0))
+    if op == "InstanceNorm":            # TM2_InstanceNormParam {eps}; the default is instancenorm.c's init_op
+        return struct.pack("<f", p.get("eps", 1e-5))
     if op == "BatchNormalization":      # TM2_BatchNormParam :407-412
         return struct.pack("<2fi", p.get("rescale_factor", 1.0), p.get("eps", 1e-5), p.get("caffe_flavor", 0))
     if op == "FullyConnected":   # TM2_FCParam :474-477
@@ -157,6 +160,8 @@ def _unpack_param(op: str, b: bytes, off: int) -> Dict:
         k = ["alg", "kernel_h", "kernel_w", "stride_h", "stride_w", "global", "caffe_flavor", "pad_h0",
              "pad_w0", "pad_h1", "pad_w1"]
         return dict(zip(k, struct.unpack_from("<I10i", b, off)))
+    if op == "InstanceNorm":
+        return {"eps": struct.unpack_from("<f", b, off)[0]}
     if op == "BatchNormalization":
         return dict(zip(["rescale_factor", "eps", "caffe_flavor"], struct.unpack_from("<2fi", b, off)))
     if op == "FullyConnected":
